@@ -8,7 +8,9 @@ One "step" = one pass of the hot path over one batch of synthetic chunks that al
   [-> all_gather of the token streams over RCCL when N > 1].
 value = (non-pad generated tokens summed over ALL ranks) / (max over ranks of the timed region / steps).
 
-Besides the contract fields the JSON line carries
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps, writes the outputs of the last timed
+step when --dump-outputs DIR is given, and prints the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  With --full the JSON line also carries
   roofline      the dominant kernel (decode cross-attention) AS THE TIMED REGION LAUNCHES IT: rows per launch and
                 in-situ microseconds from device-side timestamps taken in an EXTRA decode pass (never the timed one),
                 next to the stand-alone full-batch probe and to the step-level figure (SURVEY 8d bytes per token step /
@@ -19,8 +21,13 @@ Besides the contract fields the JSON line carries
                 (osuT5-large / base over 32 three-minute songs with resident cross K/V, bf16 and e4m3; DiT-B), each with
                 its own roofline_step, the end-to-end rate through `model_generate` including H2D / D2H, per-stage ms.
 
-Contract: python bench.py --gpus N --steps K --warmup W ; for N > 1 launched by torch.distributed.run,
-one rank per GPU.  Rank 0 prints ONE JSON line.
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] ; for N > 1 launched by
+torch.distributed.run, one rank per GPU.  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: rank 0 writes what the timed path returned in its LAST timed step, before anything else runs:
+  DIR/tokens.npy           float64 (N x chunks, 1 + new_tokens): the greedy token ids of every chunk of every rank
+  DIR/cross_kv_sample.npy  float32 (1048576,): a fixed sample (numpy seed 0, sorted flat indices) of rank 0's cross K/V
+Inputs (weights, audio, prompt) are seeded, so two builds run with the same arguments see the same inputs.
 """
 from __future__ import annotations
 
@@ -61,6 +68,10 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--batch", type=int, default=32, help="chunks per GPU")
     ap.add_argument("--new-tokens", type=int, default=384)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline, CPU baselines, aux configurations (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dit", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip config 1 / end-to-end / in-situ passes")
@@ -71,7 +82,28 @@ def parse():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="only form the process group (RCCL on a GPU box, gloo without one), all_gather the rank ids, print "
                          "{selftest, n_gpus, rccl_ranks} and exit: the launch path of --gpus N without the workload")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+KV_SAMPLE = 1 << 20     # cross K/V elements in cross_kv_sample.npy (4 MB as float32)
+
+
+def dump_outputs(out_dir: str, tokens: "torch.Tensor", kv: "torch.Tensor") -> dict:
+    """--dump-outputs: the arrays of the last timed step as DIR/<name>.npy; returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = kv.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(KV_SAMPLE, n), replace=False)).astype(np.int64)
+    arrays = {"tokens": tokens.cpu().numpy().astype(np.float64),
+              "cross_kv_sample": kv.reshape(-1)[torch.from_numpy(idx).to(kv.device)].float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def _free_port() -> int:
@@ -335,6 +367,28 @@ def main():
         n_tok_total = float(n_tok)
     ms_per_step = elapsed / args.steps * 1e3
     value = n_tok_total / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:            # the last timed step's results, before any other pass reuses the buffers
+        dump_outputs(args.dump_outputs, gathered if use_dist else tokens, kv)
+
+    line = {
+        "metric": "beatmap event-tokens/sec (mel + osuT5 encoder + greedy AR decode), whole job",
+        "value": round(value, 1), "unit": "event-tokens/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic 16 kHz audio (noise + tones), random-init weights",
+        "config": {"workload": f"osuT5-{args.size} {args.dtype}, batch={B} x 10 s chunks per GPU, {new} greedy tokens "
+                               f"per chunk, mel+encoder+cross-KV+AR decode (BASELINE configs[1])",
+                   "chunks_per_gpu": B, "new_tokens": new, "src_frames": SRC_FRAMES, "vocab": tok.vocab_size_out,
+                   "parallelism": f"chunk-sharded x{world}, all_gather of token streams" + (" (+ diffusion coordinates in aux)" if args.full else "")},
+        "rccl_ranks": dist.get_world_size() if use_dist else 0,   # size of the RCCL group the token all_gather ran over (0: no group)
+        "full": bool(args.full),
+    }
+    if not args.full and not args.headline_only:   # a plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     runtime_env = {k: os.environ.get(k) for k in ("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "GPU_MAX_HW_QUEUES", "HIP_FORCE_DEV_KERNARG")}
     if args.headline_only:
@@ -849,18 +903,7 @@ def main():
                     aux.setdefault("errors", []).append(f"cpu_baseline[{key}]: {e!r}")
                     print(f"cpu baseline for {key} failed: {e!r}", file=sys.stderr)
 
-    line = {
-        "metric": "beatmap event-tokens/sec (mel + osuT5 encoder + greedy AR decode), whole job",
-        "value": round(value, 1), "unit": "event-tokens/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic 16 kHz audio (noise + tones), random-init weights",
-        "config": {"workload": f"osuT5-{args.size} {args.dtype}, batch={B} x 10 s chunks per GPU, {new} greedy tokens "
-                               f"per chunk, mel+encoder+cross-KV+AR decode (BASELINE configs[1])",
-                   "chunks_per_gpu": B, "new_tokens": new, "src_frames": SRC_FRAMES, "vocab": tok.vocab_size_out,
-                   "parallelism": f"chunk-sharded x{world}, all_gather of token streams (+ diffusion coordinates in aux)"},
-        "rccl_ranks": dist.get_world_size() if use_dist else 0,   # size of the RCCL group the token all_gather ran over (0: no group)
-        "roofline": roofline, "cpu_baseline": cpu, "aux": aux,
-    }
+    line.update(roofline=roofline, cpu_baseline=cpu, aux=aux)
     print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()

@@ -3,7 +3,7 @@
 # Every run sits under its own `timeout`: a flag can hang the host's completion wait (ROC_SYSTEM_SCOPE_SIGNAL=0 does).
 # usage (GPU box, repo root):  bash tools/runtime_flags_ab.sh ["FLAG=V FLAG2=V" ...]     (no argument: the recorded matrix)
 cd "$(dirname "$0")/.."
-Q="--steps 3 --warmup 1 --no-cpu-baseline --no-dit --no-extras --no-config5"
+Q="--steps 3 --warmup 1 --full --no-cpu-baseline --no-dit --no-extras --no-config5"
 run() {
   echo -n "$1 :: "
   env $1 timeout 120 python bench.py $Q 2>/dev/null | python -c "
