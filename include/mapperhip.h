@@ -69,9 +69,6 @@ int mh_abi_version(void);
  *   "decode_chains"      MH_DECODE_CHAINS      0    independent row chains of a decode step (0 = automatic)
  *   "decode_prefill"     MH_DECODE_PREFILL     1    batched prompt prefill (0: token by token)
  *   "decode_gemv_cols"   MH_DECODE_GEMV_COLS   0    valid columns per 16-column tile of the decode GEMVs (0 = automatic)
- *   "decode_fused_proj"  MH_DECODE_FUSED_PROJ  1    decode attention kernels project their own q / k / v (0: stand-alone
- *                                                   GEMV launches; fp32 summation order of the projections differs;
- *                                                   2: stand-alone QKV GEMV, cross-attention keeps its own projection)
  *   "gemm_glds"          MH_GEMM_GLDS          3    bf16 GEMM operands by LDS-DMA: 3 = three-stage kernel (256x128 tiles, 128x128
  *                                                   below half a wave of them), 2 = 256x128 only, 1 = two-stage 128x128,
  *                                                   0 = register staging
@@ -84,11 +81,13 @@ int mh_abi_version(void);
  *                                                   full (0 = never; bit-identical to the 256x128 three-stage kernel)
  *   "gemm_2stage_max_k"  MH_GEMM_2STAGE_MAX_K  512  bf16 GEMM with K <= this: 128x128 tile on two LDS stages, two workgroups per CU
  *                                                   (0 = never; bit-identical)
- * (gemm_tile128_min and dit_split3_min_rows are documented next to their definitions in csrc/api.hip: 12 options in all.
+ * (gemm_tile128_min and dit_split3_min_rows are documented next to their definitions in csrc/api.hip: 11 options in all.
  * Round 5 removed the measured-slower variants decode_overlap, decode_fold_oproj, decode_cu_split, decode_self_rows,
  * mx8_waves = 4, dit_s3_fused_ln, the debugging aid gemm_lds_pad, the variant switches attn_flash2, dit_s3_presplit and
  * mx8_fused_quant (the faster form is the only one left) and turned the thresholds attn_small_max_wgs, gemm_tile256_min,
- * mx8_tile256_min into constants; their measurements stay in profiles/r02_* .. r04_*.)
+ * mx8_tile256_min into constants; their measurements stay in profiles/r02_* .. r04_*.  The decode option for stand-alone
+ * q / k / v and cross-query projection GEMVs went later (tried / rejected): the decode attention kernels
+ * always project their own.)
  * Unknown names return MH_ERR_ARG (set) / -1 (get). */
 int mh_set_option(const char* name, long value);
 long mh_get_option(const char* name);
@@ -453,7 +452,9 @@ int mh_t5_quantize_cross_kv(const MhT5Config* cfg, const void* cross_kv, int B, 
  *   forced      optional int32 [B, max_length]: teacher forcing -- when non-NULL the id appended at
  *               column c is forced[b][c] (argmax is still computed and written to `tokens`)
  * The loop is captured into a hipGraph per step shape and replayed; the host polls a device
- * "all finished" flag every `poll_every` steps (one 4-byte D2H on `stream`), otherwise no sync. */
+ * "all finished" flag every `poll_every` steps (one 4-byte D2H on `stream`), otherwise no sync.
+ * The token step (mh_t5_generate, mh_t5_step, mh_t5_cross_attn_probe) needs d_model a multiple of 128 in [128, 1024]:
+ * other shapes return MH_ERR_ARG. */
 int mh_t5_generate(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B,
                    const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
                    const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
@@ -522,8 +523,8 @@ int mh_t5_decoder_forward(const MhT5Config* cfg, const MhT5Weights* w, const voi
 /* Measurement hook (bench.py `roofline`): launches the dominant decode kernel -- cross-attention over
  * the encoder keys, algorithmic bytes per launch = B*H*src_len*64*2*sizeof(elem) -- `reps` times
  * back to back between two HIP events on `stream`, cycling through the decoder layers as a decode
- * step does.  With `w` given it is the kernel the decode step really launches (the cross-attention that also
- * projects its own query from the residual row); w == NULL times the stand-alone attention kernel.
+ * step does: the kernel the decode step really launches (the cross-attention that also projects its own query from
+ * the residual row), so `w` is required (NULL: MH_ERR_ARG).
  * ms_out (HOST float[1]) = average milliseconds per launch.  Synchronises `stream`. */
 int mh_t5_cross_attn_probe(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B, int reps,
                            float* ms_out, void* workspace, int64_t workspace_bytes, void* stream);

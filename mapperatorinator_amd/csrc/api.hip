@@ -39,7 +39,6 @@ static OptionSlot g_options[OPT_COUNT] = {
     {"decode_chains", "MH_DECODE_CHAINS", 0, false},             // independent row chains of the decode step (0 = automatic)
     {"decode_prefill", "MH_DECODE_PREFILL", 1, false},           // 1: batched prompt prefill, 0: feed the prompt token by token
     {"decode_gemv_cols", "MH_DECODE_GEMV_COLS", 0, false},       // valid weight rows per 16-column MFMA tile of the decode GEMVs (0 = automatic)
-    {"decode_fused_proj", "MH_DECODE_FUSED_PROJ", 1, false},     // 1: attention kernels project their own q / k / v, 0: stand-alone GEMVs
     {"gemm_tile128_min", "MH_GEMM_TILE128_MIN", 192, false},     // the 128x128 GEMM tile is used from this many tiles on (else 64x64 / smaller)
     {"dit_split3_min_rows", "MH_DIT_SPLIT3_MIN_ROWS", 2048, false},   // DiT denoiser batches of >= this many rows (N*T) run their big GEMMs as bf16 x 3 (0 = never)
     {"gemm_glds", "MH_GEMM_GLDS", 3, false},                     // bf16 GEMM operands by LDS-DMA (global_load_lds): 3 = three-stage kernel, 256x128 tiles or 128x128 where fewer than 128 of the big ones exist; 2 = 256x128 only; 1 = two-stage 128x128 only; 0 = register staging

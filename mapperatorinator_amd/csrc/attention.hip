@@ -757,21 +757,17 @@ int attention_general(const AttnArgs& a, int B, int H, int dtype, hipStream_t s)
   if (dtype == MH_BF16 && a.out_rs % 16 == 0 && a.out_bs % 16 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0) {
     // bf16: transposed-S kernel, 128 queries per workgroup (the 64-query kernel below only for outputs it cannot store 8 bytes at a time)
     const bool simple = a.band == 0 && !a.causal && a.key_mask == nullptr;
-#ifndef MH_F2_QB_SIMPLE
-#define MH_F2_QB_SIMPLE 2      // query blocks (of 16) per wave of the encoder form (A/B builds: 1 = 64 queries per workgroup, three workgroups per CU)
-#endif
-    constexpr int QBS = MH_F2_QB_SIMPLE;
-    const int nqt = ceil_div(a.Lq, simple ? 64 * QBS : 128);
+    const int nqt = ceil_div(a.Lq, 128);
     const long total = (long)nqt * H * B;
     MH_REQUIRE(total < (1L << 30), "attention: too many workgroups");
     const int per_xcd = (int)((total + 7) / 8);
     const size_t smem = (size_t)4 * 64 * (64 * 2 + 16);        // two buffers of (K tile | V^T tile)
     if (a.bias && simple)
-      hipLaunchKernelGGL((flash2_bf16_kernel<QBS, true, true>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
+      hipLaunchKernelGGL((flash2_bf16_kernel<2, true, true>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
     else if (a.bias)
       hipLaunchKernelGGL((flash2_bf16_kernel<2, true, false>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
     else if (simple)
-      hipLaunchKernelGGL((flash2_bf16_kernel<QBS, false, true>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
+      hipLaunchKernelGGL((flash2_bf16_kernel<2, false, true>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
     else
       hipLaunchKernelGGL((flash2_bf16_kernel<2, false, false>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
     return check_launch("flash2_bf16_kernel");

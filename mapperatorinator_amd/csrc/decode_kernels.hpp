@@ -5,8 +5,7 @@
 // residual] -> [RMSNorm + this head's query projection + cross-attention over the 1251 encoder keys: THE HBM-bound
 // kernel, B*H*L*64*2 elements per layer per step] -> [O GEMV + residual] -> [RMSNorm + wi GEMV + gated GELU] -> [wo GEMV
 // + residual]; then final RMSNorm + lm_head GEMV and the sampler (t5.hip).  Every kernel reads the current position
-// from device memory, so a chain's step is one replayable hipGraph.  (Option decode_fused_proj = 0 / 2 runs the q / k / v
-// and cross-query projections as stand-alone GEMVs in front of dec_self_attn_kernel / dec_cross_attn_kernel instead.)
+// from device memory, so a chain's step is one replayable hipGraph.
 //
 // What shapes these kernels (measured): a dependent kernel costs ~3.3 us before it does anything (launch,
 // first-load latency, store flush), so each does its whole job in one or two memory round trips; the CU's load path is
@@ -45,22 +44,6 @@ __device__ unsigned long long g_stamps[16 * 16 * 2];   // [kernel id][stamp][sum
 enum { KID_GEMV = 0 /* + EPI * 2 + (NWV == 8) */, KID_SELF = 10, KID_CROSS = 11, KID_SAMPLE = 12 };
 
 // ---- 8-element chunk helpers ----------------------------------------------------------------
-template <typename T> __device__ inline void load8(const T* p, float (&o)[8]);
-template <> __device__ inline void load8<bf16_t>(const bf16_t* p, float (&o)[8]) {
-  const uint4 v = *reinterpret_cast<const uint4*>(p);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = __uint_as_float(w[i] << 16);
-    o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-template <> __device__ inline void load8<float>(const float* p, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
 // streaming (non-temporal) variants for data that is read once per launch (K/V rows of the decode attention):
 // `global_load_dwordx4 ... nt` keeps the 1.5 GB/step K/V stream from evicting the decoder weights (226 MB) out of
 // the 256 MB Infinity Cache between token steps.
@@ -137,15 +120,9 @@ __device__ inline void store16_wt(void* p, u32x4_t v) { asm volatile("global_sto
 __device__ inline void store8_wt(void* p, u32x2_t v) { asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory"); }
 // n consecutive fp32 values (n = 4 or 8) -> one write-through store of n T elements when the destination is aligned to
 // the piece, else element by element
-#ifndef MH_PACK_ATTN
-#define MH_PACK_ATTN 1     // (0: A/B builds only -- attention outputs / cache rows as 64 two-byte stores)
-#endif
-#ifndef MH_PACK_STORES
-#define MH_PACK_STORES 1   // (0: A/B builds only -- element-wise write-through stores)
-#endif
 template <typename TO>
 __device__ inline void store_piece_wt(TO* dst, const float* v, int n, int nvalid) {
-  const bool whole = MH_PACK_STORES && nvalid == n && (reinterpret_cast<uintptr_t>(dst) & (n * sizeof(TO) - 1)) == 0;
+  const bool whole = nvalid == n && (reinterpret_cast<uintptr_t>(dst) & (n * sizeof(TO) - 1)) == 0;
   if (whole && sizeof(TO) == 4 && n == 4) {
     store16_wt(dst, u32x4_t{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])});
   } else if (whole && sizeof(TO) == 2 && n == 8) {
@@ -163,7 +140,6 @@ template <typename T>
 __device__ inline void store_head_row_wt(T* dst, float val, float* patch) {
   const int lane = threadIdx.x & 63;
   constexpr int N = 16 / (int)sizeof(T);
-  if (!MH_PACK_ATTN) { store_wt(dst + lane, Elem<T>::from_f32(val)); return; }
   patch[lane] = val;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -179,7 +155,6 @@ __device__ inline void store_head_row_wt(T* dst, float val, float* patch) {
 template <typename T>
 __device__ inline void store_head_row_from_lds_wt(T* dst, const float* src, int t) {   // t = thread index relative to the first storing thread
   constexpr int N = 16 / (int)sizeof(T);
-  if (!MH_PACK_ATTN) { if (t >= 0 && t < 64) store_wt(dst + t, Elem<T>::from_f32(src[t])); return; }
   if (t >= 0 && t < 64 / N) {
     float v[8];
 #pragma unroll
@@ -206,7 +181,7 @@ __device__ inline void store_head_row_from_lds_wt(T* dst, const float* src, int 
 //     whole-line loads was built and measured: the extra LDS write / barrier / read costs what the loads save (o-projection
 //     3.61 us alone, 4.12 beside a second chain; whole step 37.4 k vs 38.1 k tok/s without it) -- not kept.
 enum { PRO_PLAIN = 0, PRO_RMSNORM = 1, PRO_LAYERNORM = 2 };   // (LAYERNORM: HF Whisper's affine nn.LayerNorm, library arch 2)
-enum { SK_STORE = 0, SK_QKV = 1, SK_GEGLU = 2, SK_RESID = 3, SK_LOGITS = 4, SK_GELU_ERF = 5 };   // (GELU_ERF: the Whisper family's fc1)
+enum { SK_GEGLU = 2, SK_RESID = 3, SK_LOGITS = 4, SK_GELU_ERF = 5 };   // (GELU_ERF: the Whisper family's fc1)
 
 struct SkinnyP {
   const void* A; int lda;      // PRO_PLAIN: T [B, lda];  PRO_RMSNORM: fp32 residual stream [B, lda]
@@ -214,11 +189,11 @@ struct SkinnyP {
   const void* W; int ldw;      // [N, ldw] element type T
   int B, N, K;
   int nv;                      // real columns per 16-column tile: 16, 8 or 4 (GEGLU: 8 gate + 8 linear)
-  void* out; int ldo;          // STORE: T [B, ldo]; GEGLU: T [B, ldo] (N/2 cols); LOGITS: f32 [B, ldo]
+  void* out; int ldo;          // GEGLU / GELU_ERF: T [B, ldo] (GEGLU: N/2 cols); LOGITS: f32 [B, ldo]
   float* h; int ldh;           // RESID: h[b][n] += acc
-  void* kc; void* vc;          // QKV: this layer's self-attention caches [B][H][tgt_len][64]
-  int H, tgt_len, inner;
-  const int* pos;
+  void* kc; void* vc;          // (unused: kept so that the kernel-argument layout stays put)
+  int H, tgt_len, inner;       // (unused)
+  const int* pos;              // (unused)
   const float* bias;           // kernel template BIAS (the Whisper family's biased projections): fp32 [N], else unused
   const float* ln_b;           // PRO_LAYERNORM: the LayerNorm bias fp32 [K] (ln_w = its weight, eps = its epsilon)
 };
@@ -320,16 +295,8 @@ constexpr int kGemvCH = 8;   // k-blocks per wave whose loads are in flight at o
 // (12 dwords: the 13th and 14th preload slots do not arrive on this firmware -- the kernel body re-loads them)
 #define MH_GEMV_LEAD_PARAMS const void *A_, const void *W_, float *h_, const float *lnw_, int K_, int B_, int N_, int nv_
 #define MH_GEMV_LEAD_ARGS(p) (p).A, (p).W, (p).h, (p).ln_w, (p).K, (p).B, (p).N, (p).nv
-#ifndef MH_GEMV_WPE
-#define MH_GEMV_WPE 4
-#endif
-#if MH_GEMV_WPE
-#define MH_GEMV_WPE_ATTR __attribute__((amdgpu_waves_per_eu(NWV / 4, MH_GEMV_WPE)))   // registers are free here: never trade a load for one
-#else
-#define MH_GEMV_WPE_ATTR
-#endif
 template <typename T, int MF, int NWV, int PRO, int EPI, bool BIAS = false>
-__global__ __launch_bounds__(NWV * 64) MH_GEMV_WPE_ATTR
+__global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV / 4, 4)))   // registers are free here: never trade a load for one
 void gemv_kernel(MH_GEMV_LEAD_PARAMS, SkinnyP p) {
   p.A = A_; p.W = W_; p.h = h_; p.ln_w = lnw_; p.K = K_; p.lda = K_; p.ldw = K_; p.B = B_; p.N = N_; p.nv = nv_;
   if (EPI == SK_RESID) p.ldh = N_;   // the residual stream is dense [B, N] (checked on the host)
@@ -347,17 +314,11 @@ void gemv_kernel(MH_GEMV_LEAD_PARAMS, SkinnyP p) {
   // trick with the k-block -> wave assignment unchanged: RMSNorm + wi + gated GELU 5.80 -> 4.33 us alone, 6.80 -> 5.20 us
   // beside a second chain.  Loading the 16-row WEIGHT tile of that GEMV as lines as well was measured and lost (6.90 /
   // 8.69 us: 16 more LDS operations per wave than the load path saves) -- weights keep fragment-shaped loads.
-#ifndef MH_GEMV_LINES
-#define MH_GEMV_LINES 1   // (0: A/B builds only)
-#endif
-  constexpr bool LINES = (MF == 1 && PRO == PRO_PLAIN && MH_GEMV_LINES);
+  constexpr bool LINES = (MF == 1 && PRO == PRO_PLAIN);
   constexpr int CP = CH / 2;                 // k-block pairs per wave and pass
   constexpr int PATCH = 16 * 144;            // 16 rows x (128 + 16) bytes: rows 16 bytes apart in the bank row
-#ifndef MH_GEMV_RLINES
-#define MH_GEMV_RLINES 1   // (0: A/B builds only)
-#endif
   constexpr bool NORM = PRO != PRO_PLAIN, LN = PRO == PRO_LAYERNORM;
-  constexpr bool RLINES = (MF == 1 && NORM && sizeof(T) == 2 && MH_GEMV_RLINES);
+  constexpr bool RLINES = (MF == 1 && NORM && sizeof(T) == 2);
   __shared__ __attribute__((aligned(16))) unsigned char Lw[(LINES || RLINES) ? NWV * PATCH : 16];
   __shared__ f32x4_t red[NWV * MF * 64];
   __shared__ float ssw[NORM ? NWV : 1][MF * 16];
@@ -616,7 +577,6 @@ void gemv_kernel(MH_GEMV_LEAD_PARAMS, SkinnyP p) {
   if (!(PROBE & 8)) __syncthreads();
   MH_STAMP(KID, 2);     // all waves done
 
-  const int pos = (EPI == SK_QKV) ? *p.pos : 0;
   const float* redf = reinterpret_cast<const float*>(red);
 #pragma unroll
   for (int u = 0; u < UPW; ++u) {
@@ -638,23 +598,10 @@ void gemv_kernel(MH_GEMV_LEAD_PARAMS, SkinnyP p) {
     } else if (EPI == SK_GEGLU) {
       const float lin = __shfl_down(v, 8, 16);   // the linear half of the pair sits 8 tile columns to the right
       if (ok) store_wt(reinterpret_cast<T*>(p.out) + (long)row * p.ldo + ocol, Elem<T>::from_f32(gelu_tanh(v) * lin));
-    } else if (EPI == SK_STORE) {
-      if (ok) store_wt(reinterpret_cast<T*>(p.out) + (long)row * p.ldo + ocol, Elem<T>::from_f32(v));
     } else if (EPI == SK_LOGITS) {
       if (ok) store_wt(reinterpret_cast<float*>(p.out) + (long)row * p.ldo + ocol, v);
     } else if (EPI == SK_RESID) {
       if (ok) store_wt(p.h + (long)row * p.ldh + ocol, oldh[u] + v);
-    } else if (EPI == SK_QKV) {
-      if (ok) {
-        const int part = ocol / p.inner, c = ocol - part * p.inner;
-        if (part == 0) {
-          store_wt(reinterpret_cast<T*>(p.out) + (long)row * p.ldo + c, Elem<T>::from_f32(v));
-        } else {
-          const int hh = c >> 6, dd = c & 63;
-          T* cache = reinterpret_cast<T*>(part == 1 ? p.kc : p.vc);
-          store_wt(cache + (((long)row * p.H + hh) * p.tgt_len + pos) * 64 + dd, Elem<T>::from_f32(v));
-        }
-      }
     }
   }
   MH_STAMP(KID, 3);     // epilogue stores issued
@@ -766,7 +713,7 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
 }
 
 struct SelfAttnP {
-  const void* q; int ldq;         // T [B, inner]
+  const void* q; int ldq;         // (unused: kept so that the kernel-argument layout stays put)
   const void* kc; const void* vc; // [B][H][tgt_len][64]
   const float* bias;              // fp32 [H][tgt_len] by distance pos - j
   const uint8_t* prompt_mask; int P;
@@ -780,7 +727,7 @@ struct SelfAttnP {
   const float* qkv_bias; const float* rope; float scale; int window;
 };
 
-// merge the 4 waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
+// merge the NW waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
 template <typename T, int NW = 4>
 __device__ inline void block_merge(const Partial& st, float (*sm)[66], float& m, float& l, float& a) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -808,32 +755,8 @@ __device__ inline void block_merge(const Partial& st, float (*sm)[66], float& m,
   }
 }
 
-// one workgroup (4 waves) per (b, h); keys 0..pos interleaved over the 32 key groups of the block
-template <typename T>
-__global__ __launch_bounds__(256) void dec_self_attn_kernel(SelfAttnP p) {
-  __shared__ float sm[4][66];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int pair = blockIdx.x;
-  const int b = pair / p.H, h = pair % p.H;
-  const int pos = *p.pos;
-  const int c8 = (lane & 7) * 8, g = lane >> 3;
-  float q[8];
-  load8<T>(reinterpret_cast<const T*>(p.q) + (long)b * p.ldq + h * 64 + c8, q);
-  const T* kb = reinterpret_cast<const T*>(p.kc) + ((long)b * p.H + h) * p.tgt_len * 64;
-  const T* vb = reinterpret_cast<const T*>(p.vc) + ((long)b * p.H + h) * p.tgt_len * 64;
-  Partial st;
-  partial_init(st);
-  attend_keys<T, 4>(st, q, kb, vb, wid * 8 + g, pos + 1, 32, p.bias + (long)h * p.tgt_len, pos,
-                    p.prompt_mask ? p.prompt_mask + (long)b * p.P : nullptr, p.P, 1.0f);
-  partial_merge_groups<T>(st);
-  float m, l, a;
-  block_merge<T>(st, sm, m, l, a);
-  if (threadIdx.x < 64)   // (sm[0] was last read by this very wave)
-    store_head_row_wt<T>(reinterpret_cast<T*>(p.out) + (long)b * p.ldo + h * 64, l > 0.f ? a / l : 0.f, &sm[0][0]);
-}
-
 struct CrossAttnP {
-  const void* q; int ldq;   // T [B, inner]   (kernel without its own projection)
+  const void* q; int ldq;   // (unused: kept so that the kernel-argument layout stays put)
   const void* k; const void* v;  // this layer's [B][H][L][64]
   void* out; int ldo;       // T [B, inner]
   int B, H, L;
@@ -857,32 +780,6 @@ __device__ inline void cross_pair_of_block(const CrossAttnP& p, int blk, int& b,
     b = blk / p.H;
     h = blk % p.H;
   }
-}
-
-// one 16-wave workgroup per (b, h): the waves interleave 8-key rows of the 1251 encoder keys, partial (max, sum, acc)
-// merged through LDS in wave order -- the reduction order of a row never depends on the batch.  Used when the query was
-// projected by its own GEMV (option decode_fused_proj = 0).
-template <typename T, int U>
-__global__ __launch_bounds__(1024) void dec_cross_attn_kernel(CrossAttnP p) {
-  constexpr int NW = 16;
-  __shared__ float sm[NW][66];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int b, h;
-  cross_pair_of_block(p, blockIdx.x, b, h);
-  const int c8 = (lane & 7) * 8, g = lane >> 3;
-  float q[8];
-  load8<T>(reinterpret_cast<const T*>(p.q) + (long)b * p.ldq + h * 64 + c8, q);
-  const int kvb = p.kv_B > 0 ? b % p.kv_B : (p.kv_B < 0 ? b / -p.kv_B : b);
-  const T* kb = reinterpret_cast<const T*>(p.k) + ((long)kvb * p.H + h) * p.L * 64;
-  const T* vb = reinterpret_cast<const T*>(p.v) + ((long)kvb * p.H + h) * p.L * 64;
-  Partial st;
-  partial_init(st);
-  attend_keys<T, U>(st, q, kb, vb, wid * 8 + g, p.L, 8 * NW, nullptr, 0, nullptr, 0, 1.0f);
-  partial_merge_groups<T>(st);
-  float m, l, a;
-  block_merge<T, NW>(st, sm, m, l, a);
-  if (threadIdx.x < 64)
-    store_head_row_wt<T>(reinterpret_cast<T*>(p.out) + (long)b * p.ldo + h * 64, l > 0.f ? a / l : 0.f, &sm[0][0]);
 }
 
 // ---- attention kernels that project their own query (and the new self-attention key / value) --------------------
@@ -957,13 +854,6 @@ struct NormRow {
     __syncthreads();
   }
 };
-template <typename T>
-__device__ inline void norm_row_to_lds(const HeadProjP& hp, int b, float* xn, float* red16) {
-  NormRow<T> nr;
-  nr.issue(hp, b);
-  nr.finish(hp, xn, red16);
-}
-
 
 // NP projections of 64 outputs each: out[p][o] = T-rounded sum_k xn[k] * W[(row0[p] + o) * ldw + k].
 // 1024 threads: 16 consecutive lanes per output, KC 8-element chunks per lane (d = 128 KC), chunk c of lane ks = elements
@@ -1014,14 +904,12 @@ struct HeadProj {
   }
 };
 
-// cross-attention of one (b, h) with its own query projection; 16 waves, one key split (the default configuration
-// of dec_cross_attn_kernel, same key interleave and merge order)
+// cross-attention of one (b, h) with its own query projection: one 16-wave workgroup, the waves interleave 8-key rows of the
+// 1251 encoder keys, partial (max, sum, acc) merged through LDS in wave order -- the reduction order of a row never depends
+// on the batch
 // F8: K / V are the e4m3 copy (64-byte rows, 8 bytes per lane; the scales multiply the scores and the output)
 template <typename T, int KC, int U, bool F8 = false, bool WH = false, bool LN = false>
-#ifndef MH_CROSS_WPE_MIN
-#define MH_CROSS_WPE_MIN 8     // (A/B builds: 4 = up to 128 VGPRs, one 16-wave workgroup per CU)
-#endif
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(MH_CROSS_WPE_MIN, 8)))   // <= 64 VGPRs: 2 workgroups per CU
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)))   // <= 64 VGPRs: 2 workgroups per CU
 void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_, const void* k_, const void* v_, int H_, int L_, int d_,
                              int kvB_, CrossAttnP p, HeadProjP hp) {   // leading scalars: preloaded kernel arguments (see gemv_kernel)
   hp.h = h_; hp.ln_w = lnw_; hp.W = W_; hp.ldh = d_; hp.ldw = d_; hp.d = d_;

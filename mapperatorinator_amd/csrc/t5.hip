@@ -42,6 +42,13 @@ int check_cfg(const MhT5Config* c, const char* who) {
                "%s: MX-fp8 encoder operands need bf16 storage, the T5 backbone and d_model / d_ff multiples of 128", who);
   return MH_OK;
 }
+// the token step's attention kernels project their own q (/ k / v) from the whole residual row: d_model = 128 KC, KC in 1..8
+// (mh_t5_generate, mh_t5_step, mh_t5_cross_attn_probe; the encoder, cross K/V and teacher-forced forward take any shape check_cfg does)
+int check_decode_shape(const MhT5Config* c, const char* who) {
+  MH_REQUIRE(c->d_model % 128 == 0 && c->d_model >= 128 && c->d_model <= 1024,
+             "%s: the decode step needs d_model a multiple of 128 in [128, 1024] (got %d)", who, c->d_model);
+  return MH_OK;
+}
 inline bool enc_mx(const MhT5Config* c) { return c->enc_operand_dtype == MH_MX8; }
 inline int64_t mx_operand_bytes(int64_t rows, int K) { return align256(rows * K) + align256(rows * mx8_scale_row_bytes(K)); }
 // the pre-norm of a block: T5LayerNorm / nn.RMSNorm (arch 0 / 1) or the affine nn.LayerNorm of HF Whisper (arch 2, bias != NULL there)
@@ -967,23 +974,42 @@ int skinny_resid(const dec::SkinnyP& p, hipStream_t s) {
 constexpr int kMaxChains = 8;
 
 struct DecBuffers {
-  float* h; void* q; void* attn; void* ff; float* logits; int chain;
+  float* h; void* attn; void* ff; float* logits; int chain;
   void* self_k; void* self_v;  // [n_dec][B][H][tgt][64]
   uint8_t* finished; int32_t* finish_col; int32_t* last_ts; DecState* st;
 };
 
-template <typename T>
-int launch_cross(const dec::CrossAttnP& ca, hipStream_t s) {
-  // two keys in flight per 8-lane group (measured stand-alone, B=32 base bf16: U=2 5.08, U=4 4.64, U=8 3.37 TB/s)
-  hipLaunchKernelGGL((dec::dec_cross_attn_kernel<T, 2>), dim3(ca.B * ca.H), dim3(1024), 0, s, ca);
-  return check_launch("dec_cross_attn_kernel");
+// The decode workspace of B rows (mh_t5_decode_workspace_bytes): the one description of its slabs, read by mh_t5_generate,
+// mh_t5_step, mh_t5_cross_attn_probe and mh_t5_reorder_cache.  base == NULL: sizes only (every pointer NULL).
+struct DecodeLayout {
+  DecBuffers bf;                      // the whole batch; bf.st = the first of kMaxChains states, align256(sizeof(DecState)) apart
+  int32_t* pos_off; float* proc; float* hist_scores;
+  int64_t end;                        // the batched prompt prefill's region starts here
+};
+DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
+  const int64_t es = es_of(c->dtype), inner = (int64_t)c->n_heads * 64, V = c->vocab_out;
+  const int64_t cache = (int64_t)c->n_dec_layers * B * inner * c->tgt_len * es;
+  Arena ar(base, INT64_MAX);
+  DecodeLayout ly{};
+  ly.bf.h = (float*)ar.take((int64_t)B * c->d_model * 4);
+  ly.bf.attn = ar.take(B * inner * es);
+  ly.bf.ff = ar.take((int64_t)B * c->d_ff * es);
+  ly.bf.logits = (float*)ar.take(B * V * 4);
+  ly.bf.self_k = ar.take(cache);
+  ly.bf.self_v = ar.take(cache);
+  ly.bf.finished = (uint8_t*)ar.take(B);
+  ly.bf.finish_col = (int32_t*)ar.take((int64_t)B * 4);
+  ly.bf.last_ts = (int32_t*)ar.take((int64_t)B * 4);
+  ly.pos_off = (int32_t*)ar.take((int64_t)B * 4);
+  ly.bf.st = (DecState*)ar.take((int64_t)align256(sizeof(DecState)) * kMaxChains);
+  ly.proc = (float*)ar.take(B * V * 4);                 // processed scores
+  ly.hist_scores = (float*)ar.take(B * V * 4 * 2);      // LookbackBias history
+  ly.end = ar.off;
+  return ly;
 }
 
-// attention kernels that project their own q (/ k / v): see decode_kernels.hpp.  d_model = 128 KC, KC in 1..8; option
-// decode_fused_proj = 0 runs the stand-alone QKV and cross-Q GEMV launches instead (same results up to fp32 summation
-// order of the projections; both forms are covered by the GPU tests).
-bool fused_proj_enabled(int d) { return option(OPT_DECODE_FUSED_PROJ) != 0 && d % 128 == 0 && d >= 128 && d <= 1024; }
-
+// attention kernels that project their own q (/ k / v): see decode_kernels.hpp.  d_model = 128 KC, KC in 1..8
+// (check_decode_shape).
 #define MH_SELF_LEAD_ARGS hp.h, hp.ln_w, hp.W, sa.pos, sa.kc, sa.vc, sa.H, hp.d
 #define MH_CROSS_LEAD_ARGS hp.h, hp.ln_w, hp.W, ca.k, ca.v, ca.H, ca.L, hp.d, ca.kv_B
 template <typename T, int KC>
@@ -1010,24 +1036,21 @@ int launch_self_qkv_d(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int in
     default: return launch_self_qkv<T, 8>(sa, hp, inner, s);
   }
 }
-#ifndef MH_CROSS_U
-#define MH_CROSS_U 1     // keys in flight per 8-lane group of the fused cross-attention kernel (A/B builds: 2, 4)
-#endif
 template <typename T, int KC>
 int launch_cross_q(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d, "decode: dense residual rows / projection weights expected");
   // one key in flight per 8-lane group: 64 VGPRs without spills (two 16-wave workgroups per CU); U = 2 measured the
-  // same bandwidth in the stand-alone kernel
+  // same bandwidth
   if (ca.scale != 0.f) {   // the Whisper family: biased Wq, scaled scores
     MH_REQUIRE(ca.kscale == nullptr, "decode: the fp8 cross K/V copy is not wired for the Whisper family");
-    if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, MH_CROSS_U, false, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
-    else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, MH_CROSS_U, false, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
   } else if (ca.kscale != nullptr) {
     if constexpr (sizeof(T) == 2)
-      hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, MH_CROSS_U, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+      hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
     else { set_error("decode: the fp8 cross K/V copy needs bf16 storage"); return MH_ERR_ARG; }
   } else {
-    hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, MH_CROSS_U>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
   }
   return check_launch("dec_cross_attn_q_kernel");
 }
@@ -1062,90 +1085,40 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
   const int d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff, L = c->src_len, tgt = c->tgt_len;
   const int es = (int)sizeof(T);
   const int* posp = &bf.st->pos;
-  const bool wh = c->arch >= 1, hf = c->arch == 2;   // (arch 2: affine LayerNorm prologues, the identity rotary table the host packs)
-  if (wh) MH_REQUIRE(fused_proj_enabled(d) && option(OPT_DECODE_FUSED_PROJ) == 1 && w->dec_rope,
-                     "decode: the Whisper family runs on the fused attention kernels (d_model a multiple of 128 <= 1024) and needs its rotary table");
+  // arch 1 / 2: the Whisper family (VarWhisperDecoderLayer, modeling_varwhisper.py:633-741); arch 2: affine LayerNorm
+  // prologues, the identity rotary table the host packs.  Every arch runs the same six dependent kernels per layer.
+  const bool wh = c->arch >= 1, hf = c->arch == 2;
+  MH_REQUIRE(!wh || w->dec_rope, "decode: the Whisper family needs its rotary table");
   for (int l = 0; l < c->n_dec_layers; ++l) {
     const long cache_off = (long)l * Bfull * H * tgt * 64 * es;
-    dec::SkinnyP sk{};
-    if (wh) {
-      // ---- VarWhisperDecoderLayer (modeling_varwhisper.py:633-741), one token: the same six dependent kernels -------
+    MH_REQUIRE(!hf || (w->dec_ln1_b[l] && w->dec_ln2_b[l] && w->dec_ln3_b[l]), "decode: arch 2 needs the LayerNorm biases of layer %d", l);
+    // self attention (+ q / k / v projection and self-KV append)
+    dec::SelfAttnP sa{};
+    sa.kc = (char*)bf.self_k + cache_off; sa.vc = (char*)bf.self_v + cache_off; sa.prompt_mask = prompt_mask; sa.P = P;
+    sa.out = bf.attn; sa.ldo = inner; sa.B = B; sa.H = H; sa.tgt_len = tgt; sa.pos = posp;
+    if (wh) {   // biased fused Wqkv, RoPE, scaled scores, optional window
       const bool local = is_local_layer(c, l);
-      dec::SelfAttnP sa{};
-      sa.kc = (char*)bf.self_k + cache_off; sa.vc = (char*)bf.self_v + cache_off; sa.prompt_mask = prompt_mask; sa.P = P;
-      sa.out = bf.attn; sa.ldo = inner; sa.B = B; sa.H = H; sa.tgt_len = tgt; sa.pos = posp;
       sa.qkv_bias = w->dec_qkv_b[l]; sa.rope = (local && w->dec_rope_local) ? w->dec_rope_local : w->dec_rope;
       sa.scale = c->attn_scale; sa.window = local ? c->local_window : 0;
-      dec::HeadProjP hp{};
-      hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln1[l]; hp.eps = c->eps; hp.W = w->dec_qkv[l]; hp.ldw = d; hp.d = d;
-      hp.ln_b = hf ? w->dec_ln1_b[l] : nullptr;
-      MH_REQUIRE(!hf || (w->dec_ln1_b[l] && w->dec_ln2_b[l] && w->dec_ln3_b[l]), "decode: arch 2 needs the LayerNorm biases of layer %d", l);
-      MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s));
-      sk = dec::SkinnyP{};
-      sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_o[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
-      sk.bias = w->dec_o_b[l];
-      MH_TRY(skinny_resid<T>(sk, s));
-      dec::CrossAttnP ca{};
-      const long kv_layer = (long)kvB * H * L * 64 * es;
-      ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer; ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer;
-      ca.out = bf.attn; ca.ldo = inner; ca.B = B; ca.H = H; ca.L = L; ca.kv_B = kv_group > 1 ? -kv_group : (kvB < Bfull ? kvB : 0);
-      ca.q_bias = w->dec_cq_b[l]; ca.scale = c->attn_scale;
-      MH_REQUIRE(!kv8, "decode: the fp8 cross K/V copy is not wired for the Whisper family");
-      if (g_timing.buf) {
-        ca.tstamp = g_timing.buf + 2L * bf.chain * g_timing.ring * c->n_dec_layers;
-        ca.pos = posp; ca.ts_ring = g_timing.ring; ca.ts_layers = c->n_dec_layers; ca.ts_layer = l;
-      }
-      hp = dec::HeadProjP{};
-      hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
-      hp.ln_b = hf ? w->dec_ln2_b[l] : nullptr;
-      MH_TRY(launch_cross_q_d<T>(ca, hp, s));
-      sk = dec::SkinnyP{};
-      sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_co[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
-      sk.bias = w->dec_co_b[l];
-      MH_TRY(skinny_resid<T>(sk, s));
-      sk = dec::SkinnyP{};
-      sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_ln3[l]; sk.eps = c->eps; sk.W = w->dec_wi[l]; sk.ldw = d; sk.B = B;
-      sk.N = dff; sk.K = d; sk.out = bf.ff; sk.ldo = dff; sk.bias = w->dec_fc1_b[l];
-      if (hf) { sk.ln_b = w->dec_ln3_b[l]; MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(sk, s))); }
-      else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(sk, s)));
-      sk = dec::SkinnyP{};
-      sk.A = bf.ff; sk.lda = dff; sk.W = w->dec_wo[l]; sk.ldw = dff; sk.B = B; sk.N = d; sk.K = dff; sk.h = bf.h; sk.ldh = d;
-      sk.bias = w->dec_fc2_b[l];
-      MH_TRY(skinny_resid<T>(sk, s));
-      continue;
+    } else {    // T5: the shared relative position bias
+      sa.bias = w->dec_rel_bias;
     }
-    // self attention
-    const bool fused = fused_proj_enabled(d);                                  // cross-attention projects its own query
-    const bool fused_self = fused && option(OPT_DECODE_FUSED_PROJ) == 1;       // (2: stand-alone QKV GEMV, fused cross-attention)
-    dec::SelfAttnP sa{};
-    sa.q = bf.q; sa.ldq = inner; sa.kc = (char*)bf.self_k + cache_off; sa.vc = (char*)bf.self_v + cache_off;
-    sa.bias = w->dec_rel_bias; sa.prompt_mask = prompt_mask;
-    sa.P = P; sa.out = bf.attn; sa.ldo = inner; sa.B = B; sa.H = H; sa.tgt_len = tgt; sa.pos = posp;
-    if (fused_self) {
-      dec::HeadProjP hp{};
-      hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln1[l]; hp.eps = c->eps; hp.W = w->dec_qkv[l]; hp.ldw = d; hp.d = d;
-      MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s));
-    } else {
-      sk = dec::SkinnyP{};
-      sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_ln1[l]; sk.eps = c->eps; sk.W = w->dec_qkv[l]; sk.ldw = d; sk.B = B;
-      sk.N = 3 * inner; sk.K = d; sk.out = bf.q; sk.ldo = inner; sk.kc = (char*)bf.self_k + cache_off;
-      sk.vc = (char*)bf.self_v + cache_off; sk.H = H; sk.tgt_len = tgt; sk.inner = inner; sk.pos = posp;
-      MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_QKV>(sk, s)));
-      hipLaunchKernelGGL(dec::dec_self_attn_kernel<T>, dim3(B * H), dim3(256), 0, s, sa);
-      MH_TRY(check_launch("dec_self_attn_kernel"));
-    }
-    sk = dec::SkinnyP{};
-    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_o[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h;
-    sk.ldh = d;
-    MH_TRY((skinny<T, dec::PRO_PLAIN, dec::SK_RESID>(sk, s)));
-    // cross attention
+    dec::HeadProjP hp{};
+    hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln1[l]; hp.eps = c->eps; hp.W = w->dec_qkv[l]; hp.ldw = d; hp.d = d;
+    hp.ln_b = hf ? w->dec_ln1_b[l] : nullptr;
+    MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s));
+    dec::SkinnyP sk{};
+    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_o[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
+    sk.bias = wh ? w->dec_o_b[l] : nullptr;
+    MH_TRY(skinny_resid<T>(sk, s));
+    // cross attention (+ query projection)
     dec::CrossAttnP ca{};
     const long kv_layer = (long)kvB * H * L * 64 * es;
-    ca.q = bf.q; ca.ldq = inner; ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer;
-    ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer; ca.out = bf.attn; ca.ldo = inner;
-    ca.B = B; ca.H = H; ca.L = L; ca.kv_B = kv_group > 1 ? -kv_group : (kvB < Bfull ? kvB : 0);
+    ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer; ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer;
+    ca.out = bf.attn; ca.ldo = inner; ca.B = B; ca.H = H; ca.L = L; ca.kv_B = kv_group > 1 ? -kv_group : (kvB < Bfull ? kvB : 0);
+    if (wh) { ca.q_bias = w->dec_cq_b[l]; ca.scale = c->attn_scale; }
     if (kv8) {
-      MH_REQUIRE(fused, "decode: the fp8 cross K/V copy needs decode_fused_proj = 1 and d_model a multiple of 128 <= 1024");
+      MH_REQUIRE(!wh, "decode: the fp8 cross K/V copy is not wired for the Whisper family");
       const long slab = (long)kvB * H * L * 64;
       ca.k = (const char*)kv8 + (long)(l * 2 + 0) * slab; ca.v = (const char*)kv8 + (long)(l * 2 + 1) * slab;
       ca.kscale = kv8_scales + (long)(l * 2 + 0) * kvB * H; ca.vscale = kv8_scales + (long)(l * 2 + 1) * kvB * H;
@@ -1154,30 +1127,30 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
       ca.tstamp = g_timing.buf + 2L * bf.chain * g_timing.ring * c->n_dec_layers;
       ca.pos = posp; ca.ts_ring = g_timing.ring; ca.ts_layers = c->n_dec_layers; ca.ts_layer = l;
     }
-    if (fused) {
-      dec::HeadProjP hp{};
-      hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
-      MH_TRY(launch_cross_q_d<T>(ca, hp, s));
-    } else {
-      sk = dec::SkinnyP{};
-      sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_ln2[l]; sk.eps = c->eps; sk.W = w->dec_cq[l]; sk.ldw = d; sk.B = B;
-      sk.N = inner; sk.K = d; sk.out = bf.q; sk.ldo = inner;
-      MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_STORE>(sk, s)));
-      MH_TRY(launch_cross<T>(ca, s));
-    }
+    hp = dec::HeadProjP{};
+    hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
+    hp.ln_b = hf ? w->dec_ln2_b[l] : nullptr;
+    MH_TRY(launch_cross_q_d<T>(ca, hp, s));
     sk = dec::SkinnyP{};
-    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_co[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h;
-    sk.ldh = d;
-    MH_TRY((skinny<T, dec::PRO_PLAIN, dec::SK_RESID>(sk, s)));
-    // feed forward
+    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_co[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
+    sk.bias = wh ? w->dec_co_b[l] : nullptr;
+    MH_TRY(skinny_resid<T>(sk, s));
+    // feed forward: T5 gated GELU (wi_0 / wi_1 interleaved, N = 2 d_ff), the Whisper family's biased fc1 + erf GELU
     sk = dec::SkinnyP{};
     sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_ln3[l]; sk.eps = c->eps; sk.W = w->dec_wi[l]; sk.ldw = d; sk.B = B;
-    sk.N = 2 * dff; sk.K = d; sk.out = bf.ff; sk.ldo = dff;
-    MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GEGLU>(sk, s)));
+    sk.K = d; sk.out = bf.ff; sk.ldo = dff;
+    if (!wh) {
+      sk.N = 2 * dff;
+      MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GEGLU>(sk, s)));
+    } else {
+      sk.N = dff; sk.bias = w->dec_fc1_b[l];
+      if (hf) { sk.ln_b = w->dec_ln3_b[l]; MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(sk, s))); }
+      else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(sk, s)));
+    }
     sk = dec::SkinnyP{};
-    sk.A = bf.ff; sk.lda = dff; sk.W = w->dec_wo[l]; sk.ldw = dff; sk.B = B; sk.N = d; sk.K = dff; sk.h = bf.h;
-    sk.ldh = d;
-    MH_TRY((skinny<T, dec::PRO_PLAIN, dec::SK_RESID>(sk, s)));
+    sk.A = bf.ff; sk.lda = dff; sk.W = w->dec_wo[l]; sk.ldw = dff; sk.B = B; sk.N = d; sk.K = dff; sk.h = bf.h; sk.ldh = d;
+    sk.bias = wh ? w->dec_fc2_b[l] : nullptr;
+    MH_TRY(skinny_resid<T>(sk, s));
   }
   dec::SkinnyP sk{};
   sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_final_ln; sk.eps = c->eps; sk.W = w->lm_head; sk.ldw = d; sk.B = B;
@@ -1248,18 +1221,7 @@ int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64
 extern "C" int64_t mh_t5_decode_workspace_bytes(const MhT5Config* c, int B) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   if (!c || B <= 0) return -1;
-  const int64_t es = es_of(c->dtype);
-  const int inner = c->n_heads * 64;
-  int64_t t = 0;
-  t += align256((int64_t)B * c->d_model * 4);                                     // h
-  t += align256((int64_t)B * inner * es) * 2;                                     // q, attn
-  t += align256((int64_t)B * c->d_ff * es);                                       // ff
-  t += align256((int64_t)B * c->vocab_out * 4);                                   // logits
-  t += align256((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es) * 2;      // self K, V caches
-  t += align256(B) + align256((int64_t)B * 4) * 3 + align256(sizeof(DecState)) * kMaxChains;   // flags / state (+ pos_off)
-  t += align256((int64_t)B * c->vocab_out * 4) * 3;                               // processed scores + LookbackBias history
-  t += prefill_layout(c, B, c->tgt_len - 1, nullptr, 0, nullptr);                  // batched prompt prefill
-  return t;
+  return decode_layout(c, B, nullptr).end + prefill_layout(c, B, c->tgt_len - 1, nullptr, 0, nullptr);   // + batched prompt prefill
 }
 
 namespace mh {
@@ -1601,6 +1563,7 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
                               void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   MH_TRY(check_cfg(c, "mh_t5_generate"));
+  MH_TRY(check_decode_shape(c, "mh_t5_generate"));
   MH_REQUIRE(w && cross_kv && prompt && eos_table && sp && tokens && n_steps_out && workspace,
              "mh_t5_generate: null argument");
   MH_REQUIRE(stream != nullptr, "mh_t5_generate: needs a non-default stream (hipGraph capture)");
@@ -1623,23 +1586,8 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
   hipStream_t s = (hipStream_t)stream;
   const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
 
-  Arena ar(workspace, workspace_bytes);
-  DecBuffers all;
-  all.h = (float*)ar.take((int64_t)B * d * 4);
-  all.q = ar.take((int64_t)B * inner * es);
-  all.attn = ar.take((int64_t)B * inner * es);
-  all.ff = ar.take((int64_t)B * c->d_ff * es);
-  all.logits = (float*)ar.take((int64_t)B * V * 4);
-  all.self_k = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
-  all.self_v = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
-  all.finished = (uint8_t*)ar.take(B);
-  all.finish_col = (int32_t*)ar.take((int64_t)B * 4);
-  all.last_ts = (int32_t*)ar.take((int64_t)B * 4);
-  int32_t* pos_off = (int32_t*)ar.take((int64_t)B * 4);
-  DecState* st_all = (DecState*)ar.take((int64_t)align256(sizeof(DecState)) * kMaxChains);
-  float* proc = (float*)ar.take((int64_t)B * V * 4);
-  float* hist_scores = (float*)ar.take((int64_t)B * V * 4 * 2);
-  MH_REQUIRE(ar.ok() && hist_scores, "mh_t5_generate: arena overflow");
+  const DecodeLayout ly = decode_layout(c, B, workspace);
+  const DecBuffers& all = ly.bf;
   // a CFG pair spans both halves of the batch and the (batch-wide) conditional temperature reads row 0's history: one chain
   const int n_chains = (cfg || (sp->n_cond > 0 && !sp->cond_per_row)) ? 1 : pick_chains(B);
   const int rows_per = ceil_div(B, n_chains);
@@ -1666,9 +1614,8 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
   {
     if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {
       PrefillBuf pb;
-      const int64_t used_dec = ar.off;
-      prefill_layout(c, B, P - 1, (char*)workspace + used_dec, workspace_bytes - used_dec, &pb);
-      MH_REQUIRE(used_dec + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= workspace_bytes,
+      prefill_layout(c, B, P - 1, (char*)workspace + ly.end, workspace_bytes - ly.end, &pb);
+      MH_REQUIRE(ly.end + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= workspace_bytes,
                  "mh_t5_generate: workspace too small for the prompt prefill");
       MH_TRY(prefill_prompt(c, w, cross_kv, B, kvB, prompt, prompt_mask, P, P - 1, all.self_k, all.self_v, pb, s));
       start_pos = P - 1;
@@ -1691,14 +1638,13 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     DecBuffers bf = all;
     bf.chain = ci;
     bf.h = all.h + (long)b0 * d;
-    bf.q = (char*)all.q + (long)b0 * inner * es;
     bf.attn = (char*)all.attn + (long)b0 * inner * es;
     bf.ff = (char*)all.ff + (long)b0 * c->d_ff * es;
     bf.logits = all.logits + (long)b0 * V;
     bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
     bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
     bf.finished = all.finished + b0;
-    bf.st = (DecState*)((char*)st_all + (long)ci * align256(sizeof(DecState)));
+    bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
     states[ci] = bf.st;
     const void* ckv = (const char*)cross_kv + (long)b0 * H * c->src_len * 64 * es;
     const uint8_t* pm = prompt_mask ? prompt_mask + (long)b0 * P : nullptr;
@@ -1708,10 +1654,10 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     smp.forced = forced; smp.eos_table = eos_table; smp.finished = all.finished; smp.finish_col = all.finish_col;
     smp.last_ts_val = all.last_ts; smp.logits_dump = logits_dump; smp.dec_embed = w->dec_embed; smp.h = bf.h;
     smp.d = d; smp.sp = *sp; smp.st = bf.st; smp.B = B; smp.P = P; smp.b0 = b0;
-    smp.proc = proc; smp.hist_scores = hist_scores; smp.pair = cfg ? B / 2 : 0; smp.chain_rows = Bc;
+    smp.proc = ly.proc; smp.hist_scores = ly.hist_scores; smp.pair = cfg ? B / 2 : 0; smp.chain_rows = Bc;
     if (c->arch == 2) {
       smp.dec_pos = w->dec_pos;
-      smp.pos_off = c->dec_pos_from_mask ? pos_off : nullptr;
+      smp.pos_off = c->dec_pos_from_mask ? ly.pos_off : nullptr;
       smp.prompt_mask = prompt_mask;
     }
 
@@ -1936,19 +1882,14 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
                                       float* ms_out, void* workspace, int64_t workspace_bytes, void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   MH_TRY(check_cfg(c, "mh_t5_cross_attn_probe"));
-  MH_REQUIRE(cross_kv && ms_out && workspace && B > 0 && B <= 64 && reps > 0, "mh_t5_cross_attn_probe: bad argument");
+  MH_TRY(check_decode_shape(c, "mh_t5_cross_attn_probe"));
+  MH_REQUIRE(w && cross_kv && ms_out && workspace && B > 0 && B <= 64 && reps > 0, "mh_t5_cross_attn_probe: bad argument");
   MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_cross_attn_probe: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, L = c->src_len, d = c->d_model;
-  Arena ar(workspace, workspace_bytes);
-  float* h = (float*)ar.take((int64_t)B * d * 4);
-  void* q = ar.take((int64_t)B * inner * es);
-  void* attn = ar.take((int64_t)B * inner * es);
-  if (hipMemsetAsync(q, 0, (size_t)B * inner * es, s) != hipSuccess) return check_launch("probe memset");
+  const DecodeLayout ly = decode_layout(c, B, workspace);
+  float* h = ly.bf.h;
   if (hipMemsetAsync(h, 0, (size_t)B * d * 4, s) != hipSuccess) return check_launch("probe memset");
-  // the kernel the decode step launches: with weights given and the fused projections on, the cross-attention that
-  // also projects its query (dec_cross_attn_q_kernel); otherwise the stand-alone dec_cross_attn_kernel
-  const bool with_q = w != nullptr && fused_proj_enabled(d);
   const long kv_layer = (long)B * H * L * 64 * es;
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return check_launch("event create");
@@ -1958,16 +1899,12 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
     for (int r = 0; r < reps && rc == MH_OK; ++r) {
       const int l = r % c->n_dec_layers;
       dec::CrossAttnP ca{};
-      ca.q = q; ca.ldq = inner; ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer;
-      ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer; ca.out = attn; ca.ldo = inner;
+      ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer;
+      ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer; ca.out = ly.bf.attn; ca.ldo = inner;
       ca.B = B; ca.H = H; ca.L = L;
-      if (with_q) {
-        dec::HeadProjP hp{};
-        hp.h = h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
-        rc = c->dtype == MH_BF16 ? launch_cross_q_d<bf16_t>(ca, hp, s) : launch_cross_q_d<float>(ca, hp, s);
-      } else {
-        rc = c->dtype == MH_BF16 ? launch_cross<bf16_t>(ca, s) : launch_cross<float>(ca, s);
-      }
+      dec::HeadProjP hp{};
+      hp.h = h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
+      rc = c->dtype == MH_BF16 ? launch_cross_q_d<bf16_t>(ca, hp, s) : launch_cross_q_d<float>(ca, hp, s);
     }
     if (pass == 1) (void)hipEventRecord(e1, s);
   }
@@ -1993,30 +1930,16 @@ extern "C" int mh_t5_step(const MhT5Config* c, const MhT5Weights* w, const void*
                           void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   MH_TRY(check_cfg(c, "mh_t5_step"));
+  MH_TRY(check_decode_shape(c, "mh_t5_step"));
   MH_REQUIRE(w && cross_kv && ids && logits && workspace, "mh_t5_step: null argument");
   MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step: batch %d not in [1, 64]", B);
   MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_step: %d rows are not whole groups of %d", B, kv_group);
   MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "mh_t5_step: position %d outside the cache (tgt_len %d)", pos, c->tgt_len);
   MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
-  Arena ar(workspace, workspace_bytes);
-  DecBuffers bf{};
-  bf.h = (float*)ar.take((int64_t)B * d * 4);
-  bf.q = ar.take((int64_t)B * inner * es);
-  bf.attn = ar.take((int64_t)B * inner * es);
-  bf.ff = ar.take((int64_t)B * c->d_ff * es);
-  float* ws_logits = (float*)ar.take((int64_t)B * V * 4);
-  (void)ws_logits;
-  bf.logits = logits;
-  bf.self_k = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
-  bf.self_v = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
-  bf.finished = (uint8_t*)ar.take(B);
-  bf.finish_col = (int32_t*)ar.take((int64_t)B * 4);
-  bf.last_ts = (int32_t*)ar.take((int64_t)B * 4);
-  bf.st = (DecState*)ar.take((int64_t)align256(sizeof(DecState)) * kMaxChains);
-  bf.chain = 0;
-  MH_REQUIRE(ar.ok(), "mh_t5_step: arena overflow");
+  const int d = c->d_model;
+  DecBuffers bf = decode_layout(c, B, workspace).bf;
+  bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
   MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "mh_t5_step: arch 2 needs decoder.embed_positions and the LayerNorm biases");
   const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
   const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
@@ -2044,12 +1967,10 @@ extern "C" int mh_t5_reorder_cache(const MhT5Config* c, int B, const int32_t* sr
   MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B) && scratch_bytes >= mh_t5_reorder_cache_scratch_bytes(c, B, n_pos),
              "mh_t5_reorder_cache: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
-  Arena ar(workspace, workspace_bytes);
-  ar.take((int64_t)B * d * 4); ar.take((int64_t)B * inner * es); ar.take((int64_t)B * inner * es); ar.take((int64_t)B * c->d_ff * es);
-  ar.take((int64_t)B * V * 4);
-  void* self_k = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
-  void* self_v = ar.take((int64_t)c->n_dec_layers * B * inner * c->tgt_len * es);
+  const int H = c->n_heads;
+  const DecBuffers bf = decode_layout(c, B, workspace).bf;   // (the self-attention caches)
+  void* self_k = bf.self_k;
+  void* self_v = bf.self_v;
   const long layer_stride = (long)B * H * c->tgt_len * 64;
   const dim3 grid(B * H, c->n_dec_layers, 2);
   if (c->dtype == MH_BF16) {

@@ -40,6 +40,18 @@ def test_argument_validation_without_gpu():
     cfg.d_kv = 64
     assert lib.mh_t5_encode_workspace_bytes(C.byref(cfg), 2) > 0
     assert lib.mh_t5_decode_workspace_bytes(C.byref(cfg), 2) > 0
+    # the token step needs d_model a multiple of 128 in [128, 1024]: refused before any other argument is looked at
+    dec = _lib.MhT5Config(96, 64, 256, 2, 2, 2, 10, 10, 388, 416, 251, 48, 0, 1e-6)
+    assert lib.mh_t5_generate(C.byref(dec), None, None, 1, None, None, 1, None, None, None, None, None, None, None, 0, 0, None) == -1
+    assert b"d_model" in lib.mh_last_error()
+    assert lib.mh_t5_step(C.byref(dec), None, None, 1, 1, None, 0, None, 0, None, None, 0, None) == -1
+    assert b"d_model" in lib.mh_last_error()
+    ms = C.c_float(0.0)
+    assert lib.mh_t5_cross_attn_probe(C.byref(dec), None, None, 1, 1, C.byref(ms), None, 0, None) == -1
+    assert b"d_model" in lib.mh_last_error()
+    # the probe times the kernel the decode step launches, which projects its own query: weights are required
+    assert lib.mh_t5_cross_attn_probe(C.byref(cfg), None, None, 1, 1, C.byref(ms), None, 0, None) == -1
+    assert b"d_model" not in lib.mh_last_error()
     dc = _lib.MhDiTConfig(128, 2, 2, 272, 300, 2, 128, 256, 544, 300)
     assert lib.mh_dit_workspace_bytes(C.byref(dc), 2, 96) > 0
 
