@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MH_ABI_VERSION 10
+#define MH_ABI_VERSION 11
 #define MH_MAX_LAYERS 32
 
 typedef enum MhStatus {
@@ -519,6 +519,35 @@ int64_t mh_t5_forward_workspace_bytes(const MhT5Config* cfg, int B, int T);
 int mh_t5_decoder_forward(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B,
                           const int32_t* ids, const uint8_t* mask, int T, float* logits, void* workspace,
                           int64_t workspace_bytes, void* stream);
+
+/* ABI 11: teacher-forced SCORING on the device -- what MaiMod (`Processor.ai_mod`, osuT5/osuT5/inference/processor.py:421-579)
+ * computes on the host from the logits `model_forward` (osuT5/osuT5/inference/server.py:159-181) copied to it:
+ *     probs = softmax(logits)                                   processor.py:519
+ *     entropy   = -sum(probs * log2(probs + 1e-10))             :520      (bits)
+ *     surprisal = -log2(probs[target] + 1e-10)                  :521      (bits)
+ *     relative  = surprisal / entropy where entropy > 0, else 0 :522
+ *     best_id   = argmax(logits), lowest index on ties          :525
+ *   and logprob = log_softmax(logits)[target] (natural log, no epsilon).
+ * mh_score_rows: logits fp32 [R rows, V columns] with `row_stride` floats between rows (>= V), target int32 [R]; the four
+ *   float outputs and best_id are [R].  A row whose target is negative or >= V is NOT SCORED: its floats are 0, its best_id
+ *   is -1, its logits are not read.  Sums run in a fixed order: two calls on the same input agree bit for bit.
+ * mh_t5_score: the decoder stack of mh_t5_decoder_forward (same ids / mask / cross_kv / T contract), then final norm, lm_head
+ *   and the row statistics for the positions whose targets[b, t] is in [0, vocab_out) only -- every other position is written
+ *   as not scored.  targets int32 [B, T]; outputs [B, T].  The scored positions are compacted on the device and go through the
+ *   lm_head `score_block_rows` (option, MH_SCORE_BLOCK_ROWS, default 1024) at a time: the workspace exceeds the forward's by
+ *   block * (vocab_out + d_model) * 4 + O(B T) bytes, B*T*vocab_out logits are never held.  A position's numbers are bit for bit
+ *   those of mh_score_rows on mh_t5_decoder_forward's logits, whatever the block size.
+ *   max_scored (an argument beyond the reference's call: the lm_head blocks are launched by the host, which cannot see a count
+ *   made on the device): an upper bound of the number of scored positions, if the caller knows one (it has the targets on the
+ *   host), so that no lm_head block is launched for positions that cannot exist; 0 = none (the outputs are only filled);
+ *   negative = unknown, up to B*T.  Scored positions behind the bound (in row-major (b, t) order) would be left as not scored:
+ *   pass the exact count or a negative value. */
+int mh_score_rows(const float* logits, int64_t row_stride, int R, int V, const int32_t* target, float* surprisal,
+                  float* entropy, float* relative, float* logprob, int32_t* best_id, void* stream);
+int64_t mh_t5_score_workspace_bytes(const MhT5Config* cfg, int B, int T);
+int mh_t5_score(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B, const int32_t* ids,
+                const uint8_t* mask, int T, const int32_t* targets, int max_scored, float* surprisal, float* entropy,
+                float* relative, float* logprob, int32_t* best_id, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Measurement hook (bench.py `roofline`): launches the dominant decode kernel -- cross-attention over
  * the encoder keys, algorithmic bytes per launch = B*H*src_len*64*2*sizeof(elem) -- `reps` times

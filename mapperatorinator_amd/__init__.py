@@ -38,14 +38,14 @@ from .event import ContextType, Event, EventRange, EventType  # noqa: F401,E402
 from .tokenizer import Tokenizer  # noqa: F401,E402
 
 __all__ = ["ContextType", "Event", "EventRange", "EventType", "Tokenizer", "MapperatorinatorHIP",
-           "model_generate", "DiTHIP", "create_diffusion", "MelSpectrogram", "configure_runtime"]
+           "model_generate", "model_forward", "model_score", "DiTHIP", "create_diffusion", "MelSpectrogram", "configure_runtime"]
 
 
 def __getattr__(name):  # torch-dependent pieces are imported lazily
     if name == "MapperatorinatorHIP":
         from .modeling import MapperatorinatorHIP
         return MapperatorinatorHIP
-    if name in ("model_generate", "get_eos_token_id"):
+    if name in ("model_generate", "model_forward", "model_score", "get_eos_token_id"):
         from . import server
         return getattr(server, name)
     if name in ("DiTHIP", "create_diffusion", "InpaintSpec", "SpacedDiffusionHIP"):

@@ -121,7 +121,7 @@ class MhSliderSet(C.Structure):
                 ("end_idx", VP), ("length", VP)]
 
 
-ABI_VERSION = 10  # MH_ABI_VERSION of include/mapperhip.h
+ABI_VERSION = 11  # MH_ABI_VERSION of include/mapperhip.h
 
 # every symbol include/mapperhip.h declares: (name, restype, argtypes)
 I, I64, F = C.c_int, C.c_int64, C.c_float
@@ -165,6 +165,9 @@ SYMBOLS = {
     "mh_t5_reorder_cache": (I, [C.POINTER(MhT5Config), I, VP, I, VP, I64, VP, I64, VP]),
     "mh_t5_forward_workspace_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
     "mh_t5_decoder_forward": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP, VP, I64, VP]),
+    "mh_score_rows": (I, [VP, I64, I, I, VP, VP, VP, VP, VP, VP, VP]),
+    "mh_t5_score_workspace_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
+    "mh_t5_score": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP, I, VP, VP, VP, VP, VP, VP, I64, VP]),
     "mh_t5_cross_attn_probe": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, I, C.POINTER(C.c_float), VP, I64, VP]),
     "mh_t5_decode_timing": (I, [VP, I]),
     "mh_t5_decode_chains": (I, [I]),

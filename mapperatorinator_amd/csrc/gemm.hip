@@ -1979,7 +1979,10 @@ bool prepare_type() {
 long splitk_threshold() { return option(OPT_GEMM_SPLITK_TILES); }
 
 template <typename T, int EPI>
-int dispatch_tile(const GemmP& p, hipStream_t s) {
+int dispatch_tile(const GemmP& p, hipStream_t s, int plan_M) {
+  // plan_M > 0: the tile is chosen as for a problem of plan_M rows (the caller runs a slice of a larger GEMM and wants the
+  // larger one's kernel, hence its summation order: mh_t5_score against mh_t5_decoder_forward)
+  const int pm = plan_M > 0 ? plan_M : p.M;
   if constexpr (std::is_same<T, float>::value && (EPI == MH_EPI_STORE_F32 || EPI == MH_EPI_QKV_VT ||
                                                   EPI == MH_EPI_GATE_RESID || EPI == MH_EPI_BIAS_GELU)) {
     // A pre-split as well: the three-stage LDS-DMA form.  128-row tiles only: the 256-row form needs two fragment sets of
@@ -1990,14 +1993,14 @@ int dispatch_tile(const GemmP& p, hipStream_t s) {
   }
   // tile by grid size: the chip has 256 CUs; a K step of a wave costs MI*NI MFMAs, so small problems want
   // many small tiles (DiT: M = 256 rows) and big ones the 128x128 tile (encoder: M = 40k rows)
-  const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-  const long tiles64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
+  const long tiles128 = (long)((pm + 127) / 128) * ((p.N + 127) / 128);
+  const long tiles64 = (long)((pm + 63) / 64) * ((p.N + 63) / 64);
   // exact-fp32 MFMA is 16x slower than bf16: an fp32 GEMM is compute-bound long before the big tile pays (measured on
   // the batched DiT, M = 8192: 64x64 tiles 667 ms vs 128x128 827 ms per 100 steps) -> 8x the bf16 threshold
   const long min128 = option(OPT_GEMM_TILE128_MIN) * (std::is_same<T, float>::value ? 8 : 1);
   if (tiles128 >= min128) {
     if constexpr (sizeof(T) == 2) {   // plain bf16 operands: the LDS-DMA forms (option gemm_glds = 0: register staging)
-      const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
+      const long tiles256 = (long)((pm + 255) / 256) * ((p.N + 127) / 128);
       const bool vec_ok = p.N % 4 == 0 && p.ldc % 4 == 0 && (p.gate == nullptr || p.gate_ld % 4 == 0) &&
                           (EPI != MH_EPI_GEGLU || p.N % 8 == 0) && p.K % 64 == 0;
       if (option(OPT_GEMM_GLDS) >= 3 && p.K <= option(OPT_GEMM_2STAGE_MAX_K) && !p.stats_out && vec_ok)
@@ -2009,7 +2012,7 @@ int dispatch_tile(const GemmP& p, hipStream_t s) {
         // enough 256 x 256 tiles to fill the chip: the two-stage kernel with 128 x 64 wave tiles
         // ... when its last round of workgroups is not mostly idle: one workgroup per CU, so 628 tiles (osuT5-large's N = 1024
         // projections) are three rounds at 82 % -- measured 276 us against 244 for the 256 x 128 tile, while 471 tiles (92 %) gain
-        const long tiles256sq = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
+        const long tiles256sq = (long)((pm + 255) / 256) * ((p.N + 255) / 256);
         const long min256sq = option(OPT_GEMM_TILE256SQ_MIN);
         const long rounds = (tiles256sq + 255) / 256;
         const bool full_rounds = min256sq == 1 || tiles256sq * 100 >= rounds * 256 * 88;     // (option value 1: always, for tests)
@@ -2024,25 +2027,25 @@ int dispatch_tile(const GemmP& p, hipStream_t s) {
     return launch_gemm<T, 64, 64, EPI>(p, s);
   } else {
     if (tiles64 >= 192) return launch_gemm<T, 64, 64, EPI>(p, s);
-    const long tiles32 = (long)((p.M + 31) / 32) * ((p.N + 31) / 32);
+    const long tiles32 = (long)((pm + 31) / 32) * ((p.N + 31) / 32);
     if (p.ascending_k || tiles32 >= splitk_threshold()) return launch_gemm<T, 32, 32, EPI>(p, s);
     return launch_gemm<T, 16, 16, EPI>(p, s);
   }
 }
 
 template <typename T>
-int dispatch_epi(const GemmP& p, int epi, hipStream_t s) {
+int dispatch_epi(const GemmP& p, int epi, hipStream_t s, int plan_M) {
   switch (epi) {
-    case MH_EPI_STORE: return dispatch_tile<T, MH_EPI_STORE>(p, s);
-    case MH_EPI_STORE_F32: return dispatch_tile<T, MH_EPI_STORE_F32>(p, s);
-    case MH_EPI_RESID: return dispatch_tile<T, MH_EPI_RESID>(p, s);
-    case MH_EPI_GEGLU: return dispatch_tile<T, MH_EPI_GEGLU>(p, s);
-    case MH_EPI_BIAS_GELU: return dispatch_tile<T, MH_EPI_BIAS_GELU>(p, s);
-    case MH_EPI_GATE_RESID: return dispatch_tile<T, MH_EPI_GATE_RESID>(p, s);
-    case MH_EPI_KV_SCATTER: return dispatch_tile<T, MH_EPI_KV_SCATTER>(p, s);
-    case MH_EPI_QKV_VT: return dispatch_tile<T, MH_EPI_QKV_VT>(p, s);
-    case MH_EPI_QKV_CACHE: return dispatch_tile<T, MH_EPI_QKV_CACHE>(p, s);
-    case MH_EPI_BIAS_GELU_ERF: return dispatch_tile<T, MH_EPI_BIAS_GELU_ERF>(p, s);
+    case MH_EPI_STORE: return dispatch_tile<T, MH_EPI_STORE>(p, s, plan_M);
+    case MH_EPI_STORE_F32: return dispatch_tile<T, MH_EPI_STORE_F32>(p, s, plan_M);
+    case MH_EPI_RESID: return dispatch_tile<T, MH_EPI_RESID>(p, s, plan_M);
+    case MH_EPI_GEGLU: return dispatch_tile<T, MH_EPI_GEGLU>(p, s, plan_M);
+    case MH_EPI_BIAS_GELU: return dispatch_tile<T, MH_EPI_BIAS_GELU>(p, s, plan_M);
+    case MH_EPI_GATE_RESID: return dispatch_tile<T, MH_EPI_GATE_RESID>(p, s, plan_M);
+    case MH_EPI_KV_SCATTER: return dispatch_tile<T, MH_EPI_KV_SCATTER>(p, s, plan_M);
+    case MH_EPI_QKV_VT: return dispatch_tile<T, MH_EPI_QKV_VT>(p, s, plan_M);
+    case MH_EPI_QKV_CACHE: return dispatch_tile<T, MH_EPI_QKV_CACHE>(p, s, plan_M);
+    case MH_EPI_BIAS_GELU_ERF: return dispatch_tile<T, MH_EPI_BIAS_GELU_ERF>(p, s, plan_M);
   }
   set_error("mh_gemm: unknown epilogue %d", epi);
   return MH_ERR_ARG;
@@ -2064,7 +2067,7 @@ int gemm_prepare() {
   return MH_OK;
 }
 
-int gemm(const MhGemm& g, hipStream_t s, bool ascending_k) {
+int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
   MH_REQUIRE(g.A && g.W && (g.C || (g.dtype == MH_MX8 && g.mx_out)), "mh_gemm: null operand");
   MH_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "mh_gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);
   MH_REQUIRE(g.dtype == MH_F32 || g.dtype == MH_BF16 || g.dtype == MH_MX8, "mh_gemm: bad dtype %d", g.dtype);
@@ -2155,13 +2158,13 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k) {
   // workgroups, the cause was never isolated in the ISA, and a later unrelated edit of this file brought the failure back.  A path
   // nothing uses and nobody can vouch for is refused, not shipped.
   MH_REQUIRE(!(g.ln_stats && g.w_split3), "mh_gemm: the fused LayerNorm-modulate prologue is not available with w_split3 (run mh_ln_modulate first)");
-  if (g.dtype == MH_BF16) return dispatch_epi<bf16_t>(p, g.epilogue, s);
-  return dispatch_epi<float>(p, g.epilogue, s);
+  if (g.dtype == MH_BF16) return dispatch_epi<bf16_t>(p, g.epilogue, s, plan_M);
+  return dispatch_epi<float>(p, g.epilogue, s, plan_M);
 }
 
 }  // namespace mh
 
 extern "C" int mh_gemm(const MhGemm* g, void* stream) {
   if (!g) { mh::set_error("mh_gemm: null descriptor"); return MH_ERR_ARG; }
-  return mh::gemm(*g, (hipStream_t)stream, false);
+  return mh::gemm(*g, (hipStream_t)stream, false, 0);
 }

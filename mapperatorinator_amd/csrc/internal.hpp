@@ -7,7 +7,9 @@ namespace mh {
 int gemm_prepare();  // one-time kernel attribute setup; call before any stream capture
 // ascending_k: never pick the 16x16 split-K tile, so the fp32 summation order (k ascending, one accumulator) and with it
 // every bit of the result is independent of M (the tile choice otherwise follows the grid size)
-int gemm(const MhGemm& g, hipStream_t s, bool ascending_k = false);
+// plan_M > 0: pick the tile as a GEMM of plan_M rows would (a row block of a larger problem keeps the larger problem's kernel,
+// so each row's result is bit for bit what the whole GEMM gives: mh_t5_score's LM head against mh_t5_decoder_forward's)
+int gemm(const MhGemm& g, hipStream_t s, bool ascending_k = false, int plan_M = 0);
 int rmsnorm(const float* x, int ldx, const float* w, void* y, int ldy, int rows, int d, float eps, int out_dtype,
             hipStream_t s);
 int layernorm(const float* x, int ldx, const float* w, const float* b, void* y, int ldy, int rows, int d, float eps, int out_dtype,
@@ -44,6 +46,18 @@ struct AttnArgs {
 int attention_general(const AttnArgs& a, int B, int H, int dtype, hipStream_t s);
 int transpose_v(const void* v, long v_bs_el, long v_hs_el, int Lk, void* vt, int Lkpad, int B, int H, int dtype,
                 hipStream_t s);
+
+// teacher-forced scoring (score.hip).  score_rows: the statistics of mh_score_rows; with `map` the logits row r belongs to
+// compacted entry base + r: it is skipped when base + r >= min(*count, cap), else target and outputs are indexed by map[base + r].
+int score_rows(const float* logits, int64_t row_stride, int R, int V, const int32_t* target, const int32_t* map,
+               const int32_t* count, int base, int cap, float* surprisal, float* entropy, float* relative, float* logprob,
+               int32_t* best_id, hipStream_t s);
+// map[j] = flat index of the j-th position (ascending) whose target is in [0, V), *count = how many; every output := not scored
+int score_compact(const int32_t* target, int n, int V, int32_t* map, int32_t* count, float* surprisal, float* entropy,
+                  float* relative, float* logprob, int32_t* best_id, hipStream_t s);
+// dst[r] = h[map[base + r]] for base + r < min(*count, cap), zeros otherwise (r < rows; d % 4 == 0)
+int score_gather(const float* h, int d, const int32_t* map, const int32_t* count, int base, int cap, float* dst, int rows,
+                 hipStream_t s);
 
 int slider_project(float* x0, const uint8_t* imask, const float* iref, int N, int T, const MhSliderSet& ss, hipStream_t s);
 int check_slider_set(const MhSliderSet* ss, int N);

@@ -1833,6 +1833,82 @@ extern "C" int mh_t5_decoder_forward(const MhT5Config* c, const MhT5Weights* w, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Teacher-forced scoring: the decoder stack exactly as mh_t5_decoder_forward runs it, then final norm -> lm_head -> row
+// statistics (score.hip) over the SCORED positions only, `score_block_rows` of them at a time through one fp32 logits scratch:
+// B*T*V logits never exist.  The scored positions are compacted on the device (row-major (b, t) order, no host round trip); the
+// LM-head GEMM of a block is planned as the whole [B*T, V] GEMM of the forward, so a position's logits -- and with them its
+// statistics -- are bit for bit those of mh_t5_decoder_forward + mh_score_rows.
+namespace mh {
+namespace {
+struct ScoreBuf { float* logits; float* hc; int32_t* map; int32_t* count; int C, ldv; };
+int64_t score_layout(const MhT5Config* c, int B, int T, void* base, int64_t size, ScoreBuf* out) {
+  Arena ar(base, size);
+  const int64_t rows = (int64_t)B * T;
+  long C = option(OPT_SCORE_BLOCK_ROWS);
+  C = C < 1 ? 1 : C;
+  ScoreBuf t;
+  t.C = (int)(C < rows ? C : rows);
+  // rows of the scratch start 16-byte aligned.  The forward stores its logits with ldc = V; the bf16 dispatch looks at ldc % 4
+  // (`vec_ok`, gemm.hip dispatch_tile) only in a conjunction with N % 4, and N = V in both calls, so the rounding cannot select
+  // another kernel than the forward's -- keep it that way (bit-equality with mh_t5_decoder_forward rests on the same kernel)
+  t.ldv = round_up(c->vocab_out, 4);
+  t.logits = (float*)ar.take((int64_t)t.C * t.ldv * 4);
+  t.hc = (float*)ar.take((int64_t)t.C * c->d_model * 4);
+  t.map = (int32_t*)ar.take(rows * 4);
+  t.count = (int32_t*)ar.take(4);
+  if (out) *out = t;
+  return ar.off;
+}
+}  // namespace
+}  // namespace mh
+
+extern "C" int64_t mh_t5_score_workspace_bytes(const MhT5Config* c, int B, int T) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  if (!c || B <= 0 || T <= 0) return -1;
+  return mh_t5_forward_workspace_bytes(c, B, T) + mh::score_layout(c, B, T, nullptr, 0, nullptr);
+}
+
+extern "C" int mh_t5_score(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, const int32_t* ids,
+                           const uint8_t* mask, int T, const int32_t* targets, int max_scored, float* surprisal, float* entropy,
+                           float* relative, float* logprob, int32_t* best_id, void* workspace, int64_t workspace_bytes,
+                           void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_score"));
+  MH_REQUIRE(w && cross_kv && ids && targets && surprisal && entropy && relative && logprob && best_id && workspace,
+             "mh_t5_score: null argument");
+  MH_REQUIRE(B > 0, "mh_t5_score: batch %d must be positive", B);
+  MH_REQUIRE(T >= 1 && T <= c->tgt_len, "mh_t5_score: T=%d not in [1, tgt_len=%d]", T, c->tgt_len);
+  MH_REQUIRE((int64_t)B * T <= INT32_MAX, "mh_t5_score: B*T = %lld positions exceed the int32 index range", (long long)B * T);
+  MH_REQUIRE(workspace_bytes >= mh_t5_score_workspace_bytes(c, B, T), "mh_t5_score: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int es = es_of(c->dtype);
+  const int64_t fwd = mh_t5_forward_workspace_bytes(c, B, T);
+  const int64_t cache = align256((int64_t)c->n_dec_layers * B * c->n_heads * 64 * c->tgt_len * es);
+  char* self_k = (char*)workspace;
+  char* self_v = self_k + cache;
+  PrefillBuf pb;
+  prefill_layout(c, B, T, self_v + cache, fwd - 2 * cache, &pb);
+  ScoreBuf sb;
+  score_layout(c, B, T, (char*)workspace + fwd, workspace_bytes - fwd, &sb);
+  MH_TRY(prefill_prompt(c, w, cross_kv, B, B, ids, mask, T, T, self_k, self_v, pb, s));
+  const int rows = B * T, d = c->d_model, V = c->vocab_out;
+  MH_TRY(score_compact(targets, rows, V, sb.map, sb.count, surprisal, entropy, relative, logprob, best_id, s));
+  const int cap = (max_scored >= 0 && max_scored < rows) ? max_scored : rows;   // negative: unknown, every position may be scored
+  for (int base = 0; base < cap; base += sb.C) {
+    // the block's hidden rows (zeros behind the end of the list) -> final norm (pb.n is free after the stack) -> logits -> statistics
+    MH_TRY(score_gather(pb.h, d, sb.map, sb.count, base, cap, sb.hc, sb.C, s));
+    MH_TRY(pre_norm(c, sb.hc, w->dec_final_ln, w->dec_final_ln_b, pb.n, sb.C, c->dtype, s));
+    MhGemm g{};
+    g.A = pb.n; g.lda = d; g.W = w->lm_head; g.ldw = d; g.C = sb.logits; g.ldc = sb.ldv; g.M = sb.C; g.N = V;
+    g.K = d; g.dtype = c->dtype; g.epilogue = MH_EPI_STORE_F32;
+    MH_TRY(gemm(g, s, false, rows));
+    MH_TRY(score_rows(sb.logits, sb.ldv, sb.C, V, targets, sb.map, sb.count, base, cap, surprisal, entropy, relative, logprob,
+                      best_id, s));
+  }
+  return MH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // In-situ timing of the dominant kernel.  `buf` (device, uint64 [n_chains][ring][n_dec_layers][2], pre-filled by the
 // caller with (UINT64_MAX, 0) pairs) makes every cross-attention launch of the following mh_t5_generate calls record its
 // earliest workgroup start and latest workgroup end in wall-clock ticks (hipDeviceAttributeWallClockRate kHz); slot =

@@ -354,6 +354,28 @@ class MapperatorinatorHIP:
     __call__ = forward
 
     @torch.no_grad()
+    def score(self, frames=None, decoder_input_ids=None, decoder_attention_mask=None, targets=None, encoder_outputs=None,
+              **conditioning):
+        """Teacher-forced scoring on the device: what MaiMod (`Processor.ai_mod`, processor.py:519-525) derives from
+        `forward`'s logits -- softmax, entropy and surprisal in bits with the reference's `+ 1e-10`, relative surprisal,
+        argmax -- without the (B, T, vocab) logits ever being held.  Same inputs as `forward`; `targets` (B, T) names the id
+        each position is scored against, negative = not scored, None = the next input id (`t5_engine.next_token_targets`).
+        Returns an object with `surprisal`, `entropy`, `relative`, `logprob` (fp32 (B, T)) and `best_id` (int64 (B, T)) on
+        the device; not-scored positions hold 0 / -1."""
+        if decoder_input_ids is None:
+            raise ValueError("decoder_input_ids is required")
+        eng = self.engine
+        ids = decoder_input_ids.to(eng.device, torch.int32).contiguous()
+        mask = (decoder_attention_mask.to(eng.device).to(torch.uint8).contiguous()
+                if decoder_attention_mask is not None else None)
+        row_bias = self._row_bias(ids.shape[0], conditioning) if encoder_outputs is None else None
+        eng._enter()
+        with torch.cuda.stream(eng.stream):
+            out = eng.score(self._cross_kv(frames, encoder_outputs, row_bias), ids, mask, targets)
+        eng._leave()
+        return types.SimpleNamespace(**out)
+
+    @torch.no_grad()
     def generate(self, inputs=None, frames=None, decoder_input_ids=None, decoder_attention_mask=None,
                  negative_prompt=None, negative_prompt_attention_mask=None, encoder_outputs=None, logits_processor=None,
                  eos_token_id=None, do_sample=False, num_beams=1, top_k=0, top_p=1.0, max_length=None,

@@ -350,6 +350,49 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     return result, stats
 
 
+def _forward_inputs(model, model_kwargs, generate_kwargs):
+    """The reference's `model_forward` preamble (osuT5/osuT5/inference/server.py:162-169): tensors to the model's device,
+    fp32 tensors other than the audio to the model's dtype, `inputs` renamed `frames`, `precision` / `cfg_scale` popped from
+    `generate_kwargs` (in place, as the reference does), `prepare_inputs_for_generation`."""
+    dev, dt = getattr(model, "device", None), getattr(model, "dtype", None)
+    kw = {k: v.to(dev) if isinstance(v, torch.Tensor) and dev is not None else v for k, v in model_kwargs.items()}
+    kw = {k: v.to(dt) if k != "inputs" and isinstance(v, torch.Tensor) and v.dtype == torch.float32 and dt is not None else v
+          for k, v in kw.items()}
+    kw["frames"] = kw.pop("inputs", None)
+    generate_kwargs.pop("precision", None)          # storage precision is the engine's, chosen when the model was built
+    cfg_scale = generate_kwargs.pop("cfg_scale", 1.0)
+    kw = model.prepare_inputs_for_generation(**kw)
+    if cfg_scale > 1.0:
+        # the reference appends HF's ClassifierFreeGuidanceLogitsProcessor here and calls it with the (already doubled)
+        # decoder_input_ids; the processor insists on scores.shape[0] == 2 * input_ids.shape[0] and raises ValueError, with or
+        # without a negative prompt (server.py:173-180).  There is no guided teacher-forced pass to reproduce: refuse alike.
+        raise ValueError("model_forward: cfg_scale > 1 is refused, as by the reference (its guidance processor rejects the "
+                         "batch: logits rows != 2 x input rows, server.py:173-180); teacher-forced scoring has no guidance")
+    return kw
+
+
+@torch.no_grad()
+def model_forward(model, model_kwargs, generate_kwargs):
+    """Drop-in for the reference's `model_forward(model, model_kwargs, generate_kwargs)` (server.py:159-181), the teacher-forced
+    pass behind `Processor.ai_mod`: fp32 logits (B, T, vocab) on the CPU.  `cfg_scale > 1` raises ValueError as it does there."""
+    kw = _forward_inputs(model, model_kwargs, generate_kwargs)
+    return model.forward(**kw).logits.to(torch.float32).cpu()
+
+
+@torch.no_grad()
+def model_score(model, model_kwargs, generate_kwargs, targets=None):
+    """Same inputs as `model_forward`; instead of the logits, the five per-position arrays MaiMod derives from them
+    (processor.py:519-525), computed on the device by `model.score`: dict of CPU tensors `surprisal`, `entropy`, `relative`,
+    `logprob` (fp32 (B, T)) and `best_id` (int64 (B, T)).  `targets` (B, T): the id scored at each position (negative = not
+    scored; None = the next input id).  Position t scores the event that FOLLOWS input t, so MaiMod's
+    `result[start + padding - 1:end + padding - 1]` (processor.py:511) slices these arrays exactly as it sliced the logits."""
+    kw = _forward_inputs(model, model_kwargs, generate_kwargs)
+    for k in ("input_ids", "past_key_values", "use_cache", "cache_position"):
+        kw.pop(k, None)
+    out = model.score(targets=targets, **kw)
+    return {k: getattr(out, k).cpu() for k in ("surprisal", "entropy", "relative", "logprob", "best_id")}
+
+
 # ---- request batching (SURVEY.md 8f rank 4, second half) ---------------------------------------------------------------
 class RequestBatcher:
     """The batching policy of the reference's `InferenceServer._batch_thread` (osuT5/osuT5/inference/server.py:343-424)

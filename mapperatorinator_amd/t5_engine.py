@@ -194,6 +194,17 @@ class PackedT5:
         return sum(t.numel() * t.element_size() for t in self._keep)
 
 
+def next_token_targets(ids: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Targets of next-token scoring: targets[b, t] = ids[b, t + 1]; the last column and every position whose TARGET column
+    is masked out (left padding) are -1 = not scored.  int32, on the device of `ids`."""
+    ids = ids.to(torch.int32)
+    targets = torch.full_like(ids, -1)
+    targets[:, :-1] = ids[:, 1:]
+    if mask is not None:
+        targets[:, :-1] = torch.where(mask[:, 1:].to(ids.device) != 0, targets[:, :-1], torch.full_like(targets[:, :-1], -1))
+    return targets
+
+
 class HostStager:
     """Host -> HBM copies that overlap the kernels of the batch before: the host tensor goes through a pinned buffer and
     a copy stream of its own, the consumer's stream waits on the returned event (nothing overlapped the H2D
@@ -359,6 +370,38 @@ class T5Engine:
                                             _lib.ptr(mask), T, logits.data_ptr(), ws.data_ptr(), ws.numel(), self._s())
         _lib.check(rc, "mh_t5_decoder_forward")
         return logits
+
+    def score(self, cross_kv: torch.Tensor, ids: torch.Tensor, mask: Optional[torch.Tensor] = None, targets=None):
+        """Teacher-forced scoring (mh_t5_score): ids int32 (B, T) on the device -> dict of device tensors `surprisal`, `entropy`,
+        `relative`, `logprob` (fp32 (B, T)) and `best_id` (int64 (B, T)); the logits never leave the LM-head block they are
+        computed in.  `targets` (B, T): the id each position is scored against, negative = not scored (zeros, best_id -1);
+        None = next-token scoring (`next_token_targets`).  A target >= vocab_out is refused here when the targets come from the
+        host; targets already on the device are not read back (the kernel leaves such a position unscored)."""
+        p = self.packed
+        B, T = ids.shape
+        if cross_kv.shape[2] != B:
+            raise ValueError(f"cross_kv holds {cross_kv.shape[2]} rows for {B} sequences")
+        max_scored = -1                                 # unknown: the targets live on the device and are not read back
+        if targets is None:
+            targets = next_token_targets(ids, mask)
+        else:
+            targets = torch.as_tensor(targets)
+            if tuple(targets.shape) != (B, T):
+                raise ValueError(f"targets must be ({B}, {T}), got {tuple(targets.shape)}")
+            if targets.device.type == "cpu":            # the host has them: check the range, count the scored positions for free
+                if targets.numel() and int(targets.max()) >= p.vocab_out:
+                    raise ValueError(f"target id {int(targets.max())} is outside the output vocabulary of {p.vocab_out}")
+                max_scored = int((targets >= 0).sum())
+        targets = targets.to(self.device, torch.int32).contiguous()
+        need = self.lib.mh_t5_score_workspace_bytes(C.byref(p.cfg), B, T)
+        ws = self._workspace("score", need)
+        f32 = [torch.empty((B, T), dtype=torch.float32, device=self.device) for _ in range(4)]
+        best = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        rc = self.lib.mh_t5_score(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), B, ids.data_ptr(), _lib.ptr(mask), T,
+                                  targets.data_ptr(), max_scored, f32[0].data_ptr(), f32[1].data_ptr(), f32[2].data_ptr(),
+                                  f32[3].data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(), self._s())
+        _lib.check(rc, "mh_t5_score")
+        return dict(surprisal=f32[0], entropy=f32[1], relative=f32[2], logprob=f32[3], best_id=best.to(torch.int64))
 
     def decode(self, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
                eos_table: torch.Tensor, sampling: _lib.MhSampling, forced: Optional[torch.Tensor] = None,
