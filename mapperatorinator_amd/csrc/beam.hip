@@ -374,12 +374,12 @@ extern "C" int mh_beam_step(const MhBeamStep* bs, void* stream) {
   while (k_pad < bs->K) k_pad <<= 1;
   const int64_t lds = mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8;
   MH_REQUIRE(lds > 0 && lds <= 120 * 1024, "mh_beam_step: num_beams x V = %d x %d (+ %d candidates) does not fit 120 KB of LDS", bs->num_beams, bs->V, bs->K);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess)
-      return check_launch("mh_beam_step: LDS attribute");
-    attr_set = true;
-  }
+  static PerDeviceOnce attr_set;
+  const int arc = attr_set.run([] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess
+               ? MH_OK : check_launch("mh_beam_step: LDS attribute");
+  });
+  if (arc != MH_OK) return arc;
   hipLaunchKernelGGL(beam_step_kernel, dim3(bs->G), dim3(kBeamThreads), (size_t)lds, (hipStream_t)stream, *bs);
   return check_launch("beam_step_kernel");
 }

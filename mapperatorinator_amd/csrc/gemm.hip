@@ -7,7 +7,7 @@
 // Both operands are K-contiguous ("B^T input"), which is the nn.Linear weight layout -- no transposes.
 #include <type_traits>
 
-#include "common.hpp"
+#include "internal.hpp"
 
 namespace mh {
 
@@ -111,6 +111,37 @@ __device__ inline void epilogue_store(const GemmP& p, int row, int col, float v,
 // layout comes from the SOURCE side: LDS chunk c of row r holds global chunk c ^ (r & 7) (still one whole line per row).
 __device__ __attribute__((aligned(16))) uint4 g_zero16 = {0, 0, 0, 0};   // source of K-tail chunks
 
+// XCD-aware super-tile order.  Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), each with
+// its own 4 MB L2: the bijective remap below gives every XCD a CONTIGUOUS range of a work list, and the work list
+// walks the tile grid in groups of GM row panels: inside a group the row panel is the fastest index, then the column
+// tile.  The ~64 tiles an XCD runs at once are GM A panels x a few W panels (<= ~3 MB, L2-resident), every W panel is
+// fetched once per GROUP instead of once per A panel (the cross-K/V GEMM re-streamed its 28 MB of weights 313 times:
+// 9.1 GB of L2 misses for 90 MB of operands).  GM is sized so that GM panels of A fit in ~2.5 MB.
+// `bid`: work-list index (blockIdx.x, or the tile number of a persistent kernel); `panel_bytes`: one A panel (BM rows of K).
+template <int BM, int BN>
+__device__ __forceinline__ void tile_origin(int bid, int M, int N, long panel_bytes, int& m0, int& n0) {
+  const int nbm = (M + BM - 1) / BM, nbn = (N + BN - 1) / BN;
+  const int nwg = nbm * nbn;
+  {
+    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));   // 2.5 MB of A panels
+  GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
+  const int per_group = GM * nbn;
+  const int grp = bid / per_group, rem = bid - grp * per_group;
+  const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;       // panels in this (possibly last, partial) group
+  const int bn = rem / gm;
+  m0 = (grp * GM + (rem - bn * gm)) * BM;
+  n0 = bn * BN;
+}
+
+typedef const __attribute__((address_space(1))) void* gptr_t;   // operands of __builtin_amdgcn_global_load_lds
+typedef __attribute__((address_space(3))) void* lptr_t;
+// Every wait of the LDS-DMA K loops is written out; a sched_barrier after each keeps hipcc from moving MFMAs (register-only, so a
+// "memory" clobber does not hold them) above the wait that makes their operands valid.
+#define MH_WAIT(str) do { asm volatile(str ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
 template <typename T, int BM, int BN, int EPI, bool S3 = false, bool GL = false>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmP p) {
   static_assert(!S3 || (std::is_same<T, float>::value && BM == 64 && BN == 64), "split-3 path: fp32, 64x64 tile");
@@ -139,31 +170,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = kSplitK ? 0 : wid >> 1, wc = kSplitK ? 0 : wid & 1;
 
-  // XCD-aware super-tile order.  Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), each with
-  // its own 4 MB L2: the bijective remap below gives every XCD a CONTIGUOUS range of a work list, and the work list
-  // walks the tile grid in groups of GM row panels: inside a group the row panel is the fastest index, then the column
-  // tile.  The ~64 tiles an XCD runs at once are GM A panels x a few W panels (<= ~3 MB, L2-resident), every W panel is
-  // fetched once per GROUP instead of once per A panel (the cross-K/V GEMM re-streamed its 28 MB of weights 313 times:
-  // 9.1 GB of L2 misses for 90 MB of operands).  GM is sized so that GM panels of A fit in ~2.5 MB.
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nwg = nbm * nbn;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int bm, bn;
-  {
-    const long panel_bytes = (long)BM * p.K * (long)sizeof(T);
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));   // 2.5 MB of A panels
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;       // panels in this (possibly last, partial) group
-    bn = rem / gm;
-    bm = grp * GM + (rem - bn * gm);
-  }
-  const int m0 = bm * BM, n0 = bn * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, p.M, p.N, (long)BM * p.K * (long)sizeof(T), m0, n0);
 
   const int cchunk = tid % CPR;   // 16-byte chunk within the K step
   const int crow = tid / CPR;     // 0..RPP-1
@@ -248,8 +256,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmP p) {
 
   // GL: K tile kt of both operands -> LDS stage `buf`: 4 + 4 wave instructions of 8 rows x 128 bytes each
   auto glds_tiles = [&](int buf, int kt) {
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int r8 = lane >> 3;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -790,6 +796,37 @@ __device__ __forceinline__ void g3_epilogue(const GemmP& p, f32x4_t (&acc)[4][MI
   }
 }
 
+// ---- fragment read + MMA of the LDS-DMA kernels with 64-column wave tiles (gemm_glds3_kernel, gemm_glds2s_kernel) ---------------
+// Fragments of K sub-step `ks` (32 of the 64 columns of a stage) for a wave tile of 16 MI rows x 64 columns; `stage` = LDS byte
+// address of the stage, a_off / b_off = this lane's row in the A / W tile.  The reads are inline
+// asm on purpose: hipcc's own counter bookkeeping puts lgkmcnt(0) in front of the first MFMA of a phase (it does not
+// count across the loop edge), which would make the 8 reads just issued for the NEXT phase finish before the MFMAs
+// of this one start.  With the reads invisible to it, the callers' waits are the only ones: lgkmcnt(8) = "everything but
+// the 8 newest reads has arrived" (LDS reads return in order).
+template <int MI>
+__device__ __forceinline__ void g3_ldfrag(uint32_t stage, uint32_t a_off, uint32_t b_off, int ks, int lgc, int sw, bf16x8_t (&af)[MI], bf16x8_t (&bf)[4]) {
+  static_assert(MI == 2 || MI == 4, "A row blocks of the wave tile");
+  const uint32_t coff = (uint32_t)(((ks * 4 + lgc) ^ sw) * 16);
+  const uint32_t pa = stage + a_off + coff, pb = stage + b_off + coff;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(af[0]) : "v"(pa));
+  asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[1]) : "v"(pa));
+  if constexpr (MI == 4) {
+    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[2]) : "v"(pa));
+    asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(af[3]) : "v"(pa));
+  }
+  asm volatile("ds_read_b128 %0, %1" : "=v"(bf[0]) : "v"(pb));
+  asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(bf[1]) : "v"(pb));
+  asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(bf[2]) : "v"(pb));
+  asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(bf[3]) : "v"(pb));
+}
+template <int MI>
+__device__ __forceinline__ void g3_mma(f32x4_t (&acc)[4][MI], const bf16x8_t (&af)[MI], const bf16x8_t (&bf)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int i = 0; i < MI; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[j][i], 0, 0, 0);
+}
+
 // ---- G3: bf16, 256 x 128 tile, 8 waves as 4(M) x 2(N), THREE LDS stages filled by LDS-DMA two K steps ahead --------------
 // The two-stage kernel above waits for the whole next stage at the end of every K step (vmcnt(0) + barrier): with the
 // 0.2 us of MFMA work a step holds, a step costs one loaded memory round trip (~2.2 us measured on the encoder GEMMs, two
@@ -811,33 +848,14 @@ __global__ __launch_bounds__(512) void gemm_glds3_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nwg = nbm * nbn;
-  int bid = blockIdx.x;
-  {   // block b runs on XCD b % 8: give every XCD a contiguous range of the work list (bijective)
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int bm, bn;
-  {   // groups of GM row panels (<= ~2.5 MB of A), inside a group the row panel runs fastest: W panels are fetched once per group
-    const long panel_bytes = (long)BM * p.K * (long)sizeof(T);
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;
-    bn = rem / gm;
-    bm = grp * GM + (rem - bn * gm);
-  }
-  const int m0 = bm * BM, n0 = bn * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, p.M, p.N, (long)BM * p.K * (long)sizeof(T), m0, n0);
   const int nk = (p.K + BK - 1) / BK;
 
   // K tile kt of both operands -> stage st: 4 (A) + 2 (B) wave instructions of 8 rows x 128 bytes.  K % 64 == 0 (dispatch
   // condition): no K tail, so a step is six loads from six per-lane pointers that advance by 128 bytes -- no scalar
   // loads and no branches inside the K loop (either would make hipcc's counter bookkeeping fall back to lgkmcnt(0) waits
   // in front of the MFMAs, serialising the fragment reads below with them).
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const char* srcp[NA + 2];
   {
     const int r8 = lane >> 3;
@@ -890,33 +908,10 @@ __global__ __launch_bounds__(512) void gemm_glds3_kernel(GemmP p) {
   asm volatile("" ::: "memory");
 
   const int frow = lane & 15, sw = frow & 7, lgc = lane >> 4;
-  // fragments of K sub-step `ks` (32 of the 64 columns of a stage) for this wave's 64 x 64 tile.  The reads are inline
-  // asm on purpose: hipcc's own counter bookkeeping puts lgkmcnt(0) in front of the first MFMA of a phase (it does not
-  // count across the loop edge), which would make the 8 reads just issued for the NEXT phase finish before the MFMAs
-  // of this one start.  With the reads invisible to it, the waits below are the only ones: lgkmcnt(8) = "everything but
-  // the 8 newest reads has arrived" (LDS reads return in order).
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
   const uint32_t a_off = (uint32_t)((wr * WM + frow) * kRowStride), b_off = (uint32_t)((BM + wc * WN + frow) * kRowStride);
-  auto ldfrag = [&](int st, int ks, bf16x8_t (&af)[MI], bf16x8_t (&bf)[NI]) {
-    const uint32_t coff = (uint32_t)(((ks * 4 + lgc) ^ sw) * 16);
-    const uint32_t pa = lds0 + st * kStage + a_off + coff, pb = lds0 + st * kStage + b_off + coff;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(af[0]) : "v"(pa));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[1]) : "v"(pa));
-    if constexpr (MI == 4) {
-      asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[2]) : "v"(pa));
-      asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(af[3]) : "v"(pa));
-    }
-    asm volatile("ds_read_b128 %0, %1" : "=v"(bf[0]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(bf[1]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(bf[2]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(bf[3]) : "v"(pb));
-  };
-  auto mma = [&](const bf16x8_t (&af)[MI], const bf16x8_t (&bf)[NI]) {
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int i = 0; i < MI; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[j][i], 0, 0, 0);
-  };
+  auto ldfrag = [&](int st, int ks, bf16x8_t (&af)[MI], bf16x8_t (&bf)[NI]) { g3_ldfrag<MI>(lds0 + st * kStage, a_off, b_off, ks, lgc, sw, af, bf); };
+  auto mma = [&](const bf16x8_t (&af)[MI], const bf16x8_t (&bf)[NI]) { g3_mma<MI>(acc, af, bf); };
   // Two phases per K step, each = 8 fragment reads in flight under 16 MFMAs of the fragments read one phase earlier:
   //   phase A: DMA of step kt + 2 | reads of (stage kt, ks 1) | MFMAs of (stage kt, ks 0) | lgkmcnt(0), vmcnt(6), barrier
   //   phase B: reads of (stage kt + 1, ks 0)                  | MFMAs of (stage kt, ks 1)
@@ -925,18 +920,15 @@ __global__ __launch_bounds__(512) void gemm_glds3_kernel(GemmP p) {
   bf16x8_t a0[MI], b0[NI], a1[MI], b1[NI];
   ldfrag(0, 0, a0, b0);
   int cur = 0, nxt2 = 2;
-  // every wait of the loop is written out; a sched_barrier after each keeps hipcc from moving MFMAs (register-only, so a
-  // "memory" clobber does not hold them) above the wait that makes their operands valid
-#define G3_WAIT(str) do { asm volatile(str ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
   for (int kt = 0; kt + 2 < nk; ++kt) {            // steady state: a DMA every step
     issue(nxt2);
     ldfrag(cur, 1, a1, b1);
-    if constexpr (MI == 4) G3_WAIT("s_waitcnt lgkmcnt(8)");               // a0 / b0 (read one phase ago) are in
-    else G3_WAIT("s_waitcnt lgkmcnt(6)");
+    if constexpr (MI == 4) MH_WAIT("s_waitcnt lgkmcnt(8)");               // a0 / b0 (read one phase ago) are in
+    else MH_WAIT("s_waitcnt lgkmcnt(6)");
     mma(a0, b0);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (MI == 4) G3_WAIT("s_waitcnt vmcnt(6) lgkmcnt(0)");      // a1 / b1 are in; stage kt + 1 of this wave has landed
-    else G3_WAIT("s_waitcnt vmcnt(4) lgkmcnt(0)");
+    if constexpr (MI == 4) MH_WAIT("s_waitcnt vmcnt(6) lgkmcnt(0)");      // a1 / b1 are in; stage kt + 1 of this wave has landed
+    else MH_WAIT("s_waitcnt vmcnt(4) lgkmcnt(0)");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     cur = cur == NST - 1 ? 0 : cur + 1;
@@ -948,11 +940,11 @@ __global__ __launch_bounds__(512) void gemm_glds3_kernel(GemmP p) {
   }
   if (nk > 1) {                                    // step nk - 2: nothing left to request, step nk - 1 must have landed
     ldfrag(cur, 1, a1, b1);
-    if constexpr (MI == 4) G3_WAIT("s_waitcnt lgkmcnt(8)");
-    else G3_WAIT("s_waitcnt lgkmcnt(6)");
+    if constexpr (MI == 4) MH_WAIT("s_waitcnt lgkmcnt(8)");
+    else MH_WAIT("s_waitcnt lgkmcnt(6)");
     mma(a0, b0);
     __builtin_amdgcn_sched_barrier(0);
-    G3_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");
+    MH_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     cur = cur == NST - 1 ? 0 : cur + 1;
@@ -962,13 +954,12 @@ __global__ __launch_bounds__(512) void gemm_glds3_kernel(GemmP p) {
     __builtin_amdgcn_sched_barrier(0);
   }
   ldfrag(cur, 1, a1, b1);                          // last step
-  if constexpr (MI == 4) G3_WAIT("s_waitcnt lgkmcnt(8)");
-  else G3_WAIT("s_waitcnt lgkmcnt(6)");
+  if constexpr (MI == 4) MH_WAIT("s_waitcnt lgkmcnt(8)");
+  else MH_WAIT("s_waitcnt lgkmcnt(6)");
   mma(a0, b0);
   __builtin_amdgcn_sched_barrier(0);
-  G3_WAIT("s_waitcnt lgkmcnt(0)");
+  MH_WAIT("s_waitcnt lgkmcnt(0)");
   mma(a1, b1);
-#undef G3_WAIT
 
   g3_epilogue<EPI, MI>(p, acc, m0, n0, wr, wc, lane);
 }
@@ -993,29 +984,10 @@ __global__ __launch_bounds__(512, 2) void gemm_glds2s_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nwg = nbm * nbn;
-  int bid = blockIdx.x;
-  {   // block b runs on XCD b % 8: give every XCD a contiguous range of the work list (bijective)
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int bm, bn;
-  {
-    const long panel_bytes = (long)BM * p.K * (long)sizeof(T);
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;
-    bn = rem / gm;
-    bm = grp * GM + (rem - bn * gm);
-  }
-  const int m0 = bm * BM, n0 = bn * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, p.M, p.N, (long)BM * p.K * (long)sizeof(T), m0, n0);
   const int nk = (p.K + BK - 1) / BK;
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const char* a_base = p.A + (long)m0 * p.lda_b;
   const char* w_base = p.W + (long)n0 * p.ldw_b;
   uint32_t soff[NA + NB];
@@ -1059,33 +1031,18 @@ __global__ __launch_bounds__(512, 2) void gemm_glds2s_kernel(GemmP p) {
   const int frow = lane & 15, sw = frow & 7, lgc = lane >> 4;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lptr_t)smem;
   const uint32_t a_off = (uint32_t)((wr * WM + frow) * kRowStride), b_off = (uint32_t)((BM + wc * WN + frow) * kRowStride);
-  auto ldfrag = [&](int st, int ks, bf16x8_t (&af)[MI], bf16x8_t (&bf)[NI]) {
-    const uint32_t coff = (uint32_t)(((ks * 4 + lgc) ^ sw) * 16);
-    const uint32_t pa = lds0 + st * kStage + a_off + coff, pb = lds0 + st * kStage + b_off + coff;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(af[0]) : "v"(pa));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[1]) : "v"(pa));
-    asm volatile("ds_read_b128 %0, %1" : "=v"(bf[0]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(bf[1]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(bf[2]) : "v"(pb));
-    asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(bf[3]) : "v"(pb));
-  };
-  auto mma = [&](const bf16x8_t (&af)[MI], const bf16x8_t (&bf)[NI]) {
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int i = 0; i < MI; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[j][i], 0, 0, 0);
-  };
-#define G2_WAIT(str) do { asm volatile(str ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+  auto ldfrag = [&](int st, int ks, bf16x8_t (&af)[MI], bf16x8_t (&bf)[NI]) { g3_ldfrag<MI>(lds0 + st * kStage, a_off, b_off, ks, lgc, sw, af, bf); };
+  auto mma = [&](const bf16x8_t (&af)[MI], const bf16x8_t (&bf)[NI]) { g3_mma<MI>(acc, af, bf); };
   bf16x8_t a0[MI], b0[NI], a1[MI], b1[NI];
   ldfrag(0, 0, a0, b0);
   int cur = 0;
   for (int kt = 0; kt + 1 < nk; ++kt) {
     issue(cur ^ 1);
     ldfrag(cur, 1, a1, b1);
-    G2_WAIT("s_waitcnt lgkmcnt(6)");               // a0 / b0 (read one phase ago) are in
+    MH_WAIT("s_waitcnt lgkmcnt(6)");               // a0 / b0 (read one phase ago) are in
     mma(a0, b0);
     __builtin_amdgcn_sched_barrier(0);
-    G2_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");      // a1 / b1 are in; this wave's pieces of step kt + 1 have landed
+    MH_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");      // a1 / b1 are in; this wave's pieces of step kt + 1 have landed
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     cur ^= 1;
@@ -1095,12 +1052,11 @@ __global__ __launch_bounds__(512, 2) void gemm_glds2s_kernel(GemmP p) {
     __builtin_amdgcn_sched_barrier(0);
   }
   ldfrag(cur, 1, a1, b1);                          // last step
-  G2_WAIT("s_waitcnt lgkmcnt(6)");
+  MH_WAIT("s_waitcnt lgkmcnt(6)");
   mma(a0, b0);
   __builtin_amdgcn_sched_barrier(0);
-  G2_WAIT("s_waitcnt lgkmcnt(0)");
+  MH_WAIT("s_waitcnt lgkmcnt(0)");
   mma(a1, b1);
-#undef G2_WAIT
   g3_epilogue<EPI, MI>(p, acc, m0, n0, wr, wc, lane);
 }
 
@@ -1130,29 +1086,10 @@ __global__ __launch_bounds__(512) void gemm_glds4_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 2, wc = wid & 3;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nwg = nbm * nbn;
-  int bid = blockIdx.x;
-  {   // block b runs on XCD b % 8: give every XCD a contiguous range of the work list (bijective)
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int bm, bn;
-  {   // groups of GM row panels (<= ~2.5 MB of A), inside a group the row panel runs fastest: W panels are fetched once per group
-    const long panel_bytes = (long)BM * p.K * (long)sizeof(T);
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;
-    bn = rem / gm;
-    bm = grp * GM + (rem - bn * gm);
-  }
-  const int m0 = bm * BM, n0 = bn * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, p.M, p.N, (long)BM * p.K * (long)sizeof(T), m0, n0);
   const int nk = (p.K + BK - 1) / BK;        // K % 64 == 0 (dispatch condition)
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   // sources: a block-uniform 64-bit base per operand (advanced by SALU every K step) + ONE 32-bit byte offset per lane and piece
   // -- 8 offset registers instead of 16 pointer registers, and no VALU in the K loop for them
   const char* a_base = p.A + (long)m0 * p.lda_b;
@@ -1229,7 +1166,6 @@ __global__ __launch_bounds__(512) void gemm_glds4_kernel(GemmP p) {
       for (int j = 0; j < NI; ++j)
         asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[j][i]) : "v"(bf[j]), "v"(af[i]));
   };
-#define G4_WAIT(str) do { asm volatile(str ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define G4_BARRIER() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
   bf16x8_t a0[MI], b0[NI], a1[MI], b1[NI];
   ldfrag(0, 0, a0, b0);
@@ -1238,7 +1174,7 @@ __global__ __launch_bounds__(512) void gemm_glds4_kernel(GemmP p) {
   for (int kt = 0; kt < nk; ++kt) {
     // ISSUE_A
     ldfrag(cur, 1, a1, b1);
-    G4_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");       // a0 / b0 / a1 / b1 are in; this wave's pieces of step kt + 1 have landed
+    MH_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");       // a0 / b0 / a1 / b1 are in; this wave's pieces of step kt + 1 have landed
     G4_BARRIER();
     // MFMA0
     mma(a0, b0);
@@ -1254,7 +1190,6 @@ __global__ __launch_bounds__(512) void gemm_glds4_kernel(GemmP p) {
   }
   if (wr == 0) G4_BARRIER();
 #undef G4_BARRIER
-#undef G4_WAIT
   // the MFMAs are asm: hipcc does not know that the accumulators come out of the matrix pipe.  It pads nothing in front of
   // their first read -- and it is free to move a v_accvgpr_read of an accumulator up to right behind the asm statement that last
   // wrote it, i.e. in between the final MFMAs (seen: the GEGLU epilogue read acc[0][0] there and got the value of a step ago).
@@ -1290,24 +1225,9 @@ __global__ __launch_bounds__(512) void gemm_s3g_kernel(GemmP p) {
   // stages and its epilogue were dead time (9 of 17 us per tile at K = 384): the NEXT tile's first two stages are requested
   // once the K loop is over (its last barrier retired every read of the stage buffers) and the epilogue has its OWN loads in
   // registers (the load counter is in-order: a bias load issued after the DMAs would wait for them), before the stores.
-  auto coords = [&](int t, int& m0_, int& n0_) {
-    int bid = t;
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const long panel_bytes = (long)BM * p.K * 4L;
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;
-    const int bn = rem / gm;
-    m0_ = (grp * GM + (rem - bn * gm)) * BM;
-    n0_ = bn * BN;
-  };
+  auto coords = [&](int t, int& m0_, int& n0_) { tile_origin<BM, BN>(t, p.M, p.N, (long)BM * p.K * 4L, m0_, n0_); };
   const int nk = p.K / 32;                       // one 128-byte block (32 values as hi | lo) per K step
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const char* srcp[NA + 2];
   auto setup = [&](int m0_, int n0_) {
     const int r8 = lane >> 3;
@@ -1375,7 +1295,6 @@ __global__ __launch_bounds__(512) void gemm_s3g_kernel(GemmP p) {
         acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.bh[j], f.ah[i], acc[j][i], 0, 0, 0);
       }
   };
-#define S3G_WAIT(str) do { asm volatile(str ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
   // step kt: [DMA of stage kt + 2] wait: stage kt + 1 landed, own LDS reads retired | barrier | reads of stage kt + 1 into
   // the OTHER register set | MFMAs on this set (read one step ago, retired by the wait above)
   Frags f0, f1;
@@ -1391,9 +1310,9 @@ __global__ __launch_bounds__(512) void gemm_s3g_kernel(GemmP p) {
   auto step = [&](Frags& cur, Frags& other, bool dma, bool more) {
     if (dma) {
       issue(nxt2);
-      if constexpr (MI == 4) S3G_WAIT("s_waitcnt vmcnt(6) lgkmcnt(0)"); else S3G_WAIT("s_waitcnt vmcnt(4) lgkmcnt(0)");
+      if constexpr (MI == 4) MH_WAIT("s_waitcnt vmcnt(6) lgkmcnt(0)"); else MH_WAIT("s_waitcnt vmcnt(4) lgkmcnt(0)");
     } else {
-      S3G_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");
+      MH_WAIT("s_waitcnt vmcnt(0) lgkmcnt(0)");
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1429,7 +1348,6 @@ __global__ __launch_bounds__(512) void gemm_s3g_kernel(GemmP p) {
     const bool dma = kt + 2 < nk, more = kt + 1 < nk;
     if ((kt & 1) == 0) step(f0, f1, dma, more); else step(f1, f0, dma, more);
   }
-#undef S3G_WAIT
 
   // ---- epilogue (4 consecutive columns per lane; loads pinned before the first store of a row block) ----
   const int l15 = lane & 15;
@@ -1594,29 +1512,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_mx8_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1;
 
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nwg = nbm * nbn;
-  int bid = blockIdx.x;
-  {   // block b runs on XCD b % 8: give every XCD a contiguous range of the work list (bijective)
-    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int bm, bn;
-  {   // groups of GM row panels (<= ~2.5 MB of A), inside a group the row panel runs fastest
-    const long panel_bytes = (long)BM * p.K;
-    int GM = (int)((5L << 19) / (panel_bytes > 0 ? panel_bytes : 1));
-    GM = GM < 2 ? 2 : (GM > 16 ? 16 : GM);
-    const int per_group = GM * nbn;
-    const int grp = bid / per_group, rem = bid - grp * per_group;
-    const int gm = (nbm - grp * GM) < GM ? (nbm - grp * GM) : GM;
-    bn = rem / gm;
-    bm = grp * GM + (rem - bn * gm);
-  }
-  const int m0 = bm * BM, n0 = bn * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, p.M, p.N, (long)BM * p.K, m0, n0);
   const int nk = p.K / 128;                  // K % 128 == 0 (dispatch condition)
 
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const char* srcp[NDMA];
   {
     const int r8 = lane >> 3;
@@ -1847,132 +1746,123 @@ __global__ __launch_bounds__(NW * 64) void gemm_mx8_kernel(GemmP p) {
   g3_epilogue<EPI, MI, MXO>(p, acc, m0, n0, wr, wc, lane);
 }
 
-template <int EPI, int MI, int NW, bool MXO = false>
-int launch_mx8(const GemmP& p, hipStream_t s) {
-  constexpr int BM = 16 * MI * (NW / 2);
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + 127) / 128;
-  hipLaunchKernelGGL((gemm_mx8_kernel<EPI, MI, NW, MXO>), dim3(nbm * nbn), dim3(NW * 64), 3 * (BM + 128) * 128, s, p);
-  return check_launch("gemm_mx8_kernel");
-}
+// ---- host side: ONE description per kernel family -----------------------------------------------------------------------------
+// Tile rows / columns, threads, dynamic LDS bytes, grid rule and the kernel itself.  Both the launch and the attribute set-up of
+// gemm_prepare() are generated from it (KernelList below), so a family's LDS size is written once.
+struct GridPerTile { static int grid(int tiles) { return tiles; } };   // one workgroup per tile
+constexpr int dma_stage_bytes(int BM, int BN) { return (BM + BN) * 128; }   // one (A tile, W tile) stage of the LDS-DMA kernels: 128-byte rows
+
+template <typename T, int BM_, int BN_, int EPI, bool S3 = false, bool GL = false>
+struct Tn : GridPerTile {
+  static constexpr int BM = BM_, BN = BN_, kThreads = 256;
+  static constexpr int kLds = 2 * (BM + BN) * (RowBytes<BM>::v + 16) + BM * 8 + 2048;   // two padded stages + LayerNorm statistics
+  static constexpr auto kernel() { return &gemm_tn_kernel<T, BM, BN, EPI, S3, GL>; }
+  static constexpr const char* kName = "gemm_tn_kernel";
+};
+template <int EPI, int MI>
+struct Glds3 : GridPerTile {
+  static constexpr int BM = 64 * MI, BN = 128, kThreads = 512, kLds = 3 * dma_stage_bytes(BM, BN);
+  static constexpr auto kernel() { return &gemm_glds3_kernel<EPI, MI>; }
+  static constexpr const char* kName = "gemm_glds3_kernel";
+};
 template <int EPI>
-bool prepare_mx8() {
-  bool ok = true;
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx8_kernel<EPI, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (128 + 128) * 128) == hipSuccess;
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx8_kernel<EPI, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 + 128) * 128) == hipSuccess;
-  if constexpr (EPI == MH_EPI_GEGLU || EPI == MH_EPI_BIAS_GELU) {   // ... and their forms that write the result as an MX-fp8 operand
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx8_kernel<EPI, 2, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (128 + 128) * 128) == hipSuccess;
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mx8_kernel<EPI, 4, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 + 128) * 128) == hipSuccess;
+struct Glds2s : GridPerTile {
+  static constexpr int BM = 128, BN = 128, kThreads = 512, kLds = 2 * dma_stage_bytes(BM, BN);
+  static constexpr auto kernel() { return &gemm_glds2s_kernel<EPI>; }
+  static constexpr const char* kName = "gemm_glds2s_kernel";
+};
+template <int EPI>
+struct Glds4 : GridPerTile {
+  static constexpr int BM = 256, BN = 256, kThreads = 512, kLds = 2 * dma_stage_bytes(BM, BN);
+  static constexpr auto kernel() { return &gemm_glds4_kernel<EPI>; }
+  static constexpr const char* kName = "gemm_glds4_kernel";
+};
+template <int EPI, int MI>
+struct S3g {
+  static constexpr int BM = 64 * MI, BN = 128, kThreads = 512, kLds = 3 * dma_stage_bytes(BM, BN);
+  static constexpr auto kernel() { return &gemm_s3g_kernel<EPI, MI>; }
+  static constexpr const char* kName = "gemm_s3g_kernel";
+  static int grid(int tiles) { return tiles < 256 ? tiles : 256; }   // persistent: one workgroup per CU walks the work list
+};
+template <int EPI, int MI, int NW, bool MXO = false>
+struct Mx8 : GridPerTile {
+  static constexpr int BM = 16 * MI * (NW / 2), BN = 128, kThreads = NW * 64, kLds = 3 * dma_stage_bytes(BM, BN);
+  static constexpr auto kernel() { return &gemm_mx8_kernel<EPI, MI, NW, MXO>; }
+  static constexpr const char* kName = "gemm_mx8_kernel";
+};
+
+// The kernels of one (operand class, epilogue).  A kernel is launched THROUGH its list, and gemm_prepare() walks the same lists:
+// what is not a member does not compile, so nothing can be launched that was not prepared.
+template <class... K>
+struct KernelList {
+  // > 64 KiB of dynamic LDS needs an explicit opt-in per kernel; done for every member, outside any stream capture (gemm_prepare())
+  static bool prepare() {
+    return (... && (hipFuncSetAttribute(reinterpret_cast<const void*>(K::kernel()), hipFuncAttributeMaxDynamicSharedMemorySize, K::kLds) == hipSuccess));
   }
-  return ok;
+  template <class Q>
+  static int launch(Q, const GemmP& p, hipStream_t s) {
+    static_assert((... || std::is_same<Q, K>::value), "kernel is not in the list that gemm_prepare() walks");
+    const int tiles = ((p.M + Q::BM - 1) / Q::BM) * ((p.N + Q::BN - 1) / Q::BN);
+    hipLaunchKernelGGL(Q::kernel(), dim3(Q::grid(tiles)), dim3(Q::kThreads), Q::kLds, s, p);
+    return check_launch(Q::kName);
+  }
+};
+template <class... A, class... B> constexpr KernelList<A..., B...> operator+(KernelList<A...>, KernelList<B...>) { return {}; }
+template <bool C, class L> constexpr auto when(L l) { if constexpr (C) return l; else return KernelList<>{}; }
+
+// ---- ONE list of epilogues per operand class: the dispatchers' switch, the prepare walk and the argument checks come from it ----
+template <int... E>
+struct EpiList {
+  static constexpr bool has(int epi) { return (... || (epi == E)); }
+  template <class F> static bool all(F&& f) { return (... && f(std::integral_constant<int, E>{})); }
+  // f(integral_constant<E>) of the member that equals epi; MH_ERR_ARG when there is none
+  template <class F> static int visit(int epi, F&& f) {
+    int rc = MH_ERR_ARG;
+    (void)(... || (epi == E && ((rc = f(std::integral_constant<int, E>{})), true)));
+    return rc;
+  }
+};
+using Epis = EpiList<MH_EPI_STORE, MH_EPI_STORE_F32, MH_EPI_RESID, MH_EPI_GEGLU, MH_EPI_BIAS_GELU, MH_EPI_GATE_RESID, MH_EPI_KV_SCATTER,
+                     MH_EPI_QKV_VT, MH_EPI_QKV_CACHE, MH_EPI_BIAS_GELU_ERF>;                                       // bf16 / fp32 operands
+using Mx8Epis = EpiList<MH_EPI_STORE, MH_EPI_STORE_F32, MH_EPI_RESID, MH_EPI_GEGLU, MH_EPI_BIAS_GELU, MH_EPI_GATE_RESID, MH_EPI_KV_SCATTER,
+                        MH_EPI_QKV_VT>;                                                                               // MX-fp8 operands
+using Bf16x3Epis = EpiList<MH_EPI_STORE_F32, MH_EPI_QKV_VT, MH_EPI_GATE_RESID, MH_EPI_BIAS_GELU>;                  // fp32 as bf16 x 3 (w_split3)
+using Mx8OutEpis = EpiList<MH_EPI_GEGLU, MH_EPI_BIAS_GELU>;     // ... whose result can leave as the next GEMM's MX-fp8 operand (g3_epilogue MXO)
+
+template <int EPI>
+constexpr auto mx8_kernels() {
+  return KernelList<Mx8<EPI, 2, 8>, Mx8<EPI, 4, 8>>{} + when<Mx8OutEpis::has(EPI)>(KernelList<Mx8<EPI, 2, 8, true>, Mx8<EPI, 4, 8, true>>{});
 }
+template <typename T, int EPI>
+constexpr auto tile_kernels() {   // every kernel dispatch_tile<T, EPI> can choose
+  return KernelList<Tn<T, 128, 128, EPI>, Tn<T, 64, 64, EPI>>{} +
+         when<EPI != MH_EPI_GEGLU>(KernelList<Tn<T, 32, 32, EPI>, Tn<T, 16, 16, EPI>>{}) +   // GEGLU pairs two 16-col blocks per wave
+         when<sizeof(T) == 2>(KernelList<Tn<T, 128, 128, EPI, false, true>, Glds3<EPI, 4>, Glds3<EPI, 2>, Glds4<EPI>, Glds2s<EPI>>{}) +
+         when<std::is_same<T, float>::value && Bf16x3Epis::has(EPI)>(KernelList<Tn<T, 64, 64, EPI, true>, S3g<EPI, 2>>{});
+}
+
 // tile-count thresholds that were run-time options until round 5 (measured: batched DiT-S bf16 171.6 ms at 192, 167.4 at 96, 168.6 at 48)
 constexpr long kMx8Tile256Min = 192, kGemmTile256Min = 96;
 template <int EPI>
 int dispatch_mx8(const GemmP& p, hipStream_t s) {
+  constexpr auto ks = mx8_kernels<EPI>();
   // fewer 256-row tiles than option mx8_tile256_min: the 128-row form doubles the workgroups
   const long tiles256 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-  if constexpr (EPI == MH_EPI_GEGLU || EPI == MH_EPI_BIAS_GELU) {
+  if constexpr (Mx8OutEpis::has(EPI)) {
     if (p.mxq) {   // the result leaves as the next GEMM's MX-fp8 operand
-      if (tiles256 < kMx8Tile256Min) return launch_mx8<EPI, 2, 8, true>(p, s);
-      return launch_mx8<EPI, 4, 8, true>(p, s);
+      if (tiles256 < kMx8Tile256Min) return ks.launch(Mx8<EPI, 2, 8, true>{}, p, s);
+      return ks.launch(Mx8<EPI, 4, 8, true>{}, p, s);
     }
   }
-  if (tiles256 < kMx8Tile256Min) return launch_mx8<EPI, 2, 8>(p, s);
-  return launch_mx8<EPI, 4, 8>(p, s);     // 256 x 128 tile as eight waves of 64 x 64 (two per SIMD); the four-wave 128 x 64 geometry measured 0.99-1.37 x the bf16 kernel against 1.07-1.46 x (profiles/r04_mx8_gemm_bench.txt) and was removed in round 5
+  if (tiles256 < kMx8Tile256Min) return ks.launch(Mx8<EPI, 2, 8>{}, p, s);
+  return ks.launch(Mx8<EPI, 4, 8>{}, p, s);     // 256 x 128 tile as eight waves of 64 x 64 (two per SIMD); the four-wave 128 x 64 geometry measured 0.99-1.37 x the bf16 kernel against 1.07-1.46 x (profiles/r04_mx8_gemm_bench.txt) and was removed in round 5
 }
 int dispatch_mx8_epi(const GemmP& p, int epi, hipStream_t s) {
-  switch (epi) {
-    case MH_EPI_STORE: return dispatch_mx8<MH_EPI_STORE>(p, s);
-    case MH_EPI_STORE_F32: return dispatch_mx8<MH_EPI_STORE_F32>(p, s);
-    case MH_EPI_RESID: return dispatch_mx8<MH_EPI_RESID>(p, s);
-    case MH_EPI_GEGLU: return dispatch_mx8<MH_EPI_GEGLU>(p, s);
-    case MH_EPI_BIAS_GELU: return dispatch_mx8<MH_EPI_BIAS_GELU>(p, s);
-    case MH_EPI_GATE_RESID: return dispatch_mx8<MH_EPI_GATE_RESID>(p, s);
-    case MH_EPI_KV_SCATTER: return dispatch_mx8<MH_EPI_KV_SCATTER>(p, s);
-    case MH_EPI_QKV_VT: return dispatch_mx8<MH_EPI_QKV_VT>(p, s);
+  if (!Mx8Epis::has(epi)) {
+    set_error("mh_gemm: epilogue %d is not built for MH_MX8 operands", epi);
+    return MH_ERR_ARG;
   }
-  set_error("mh_gemm: epilogue %d is not built for MH_MX8 operands", epi);
-  return MH_ERR_ARG;
-}
-
-template <int EPI, int MI>
-int launch_s3g(const GemmP& p, hipStream_t s) {
-  constexpr int BM = 64 * MI;
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + 127) / 128;
-  const int tiles = nbm * nbn;
-  hipLaunchKernelGGL((gemm_s3g_kernel<EPI, MI>), dim3(tiles < 256 ? tiles : 256), dim3(512), 3 * (BM + 128) * 128, s, p);
-  return check_launch("gemm_s3g_kernel");
-}
-
-template <int EPI, int MI>
-int launch_glds3(const GemmP& p, hipStream_t s) {
-  constexpr int BM = 64 * MI;
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + 127) / 128;
-  hipLaunchKernelGGL((gemm_glds3_kernel<EPI, MI>), dim3(nbm * nbn), dim3(512), 3 * (BM + 128) * 128, s, p);
-  return check_launch("gemm_glds3_kernel");
-}
-
-template <int EPI>
-int launch_glds2s(const GemmP& p, hipStream_t s) {
-  const int nbm = (p.M + 127) / 128, nbn = (p.N + 127) / 128;
-  hipLaunchKernelGGL((gemm_glds2s_kernel<EPI>), dim3(nbm * nbn), dim3(512), 2 * (128 + 128) * 128, s, p);
-  return check_launch("gemm_glds2s_kernel");
-}
-
-template <int EPI>
-int launch_glds4(const GemmP& p, hipStream_t s) {
-  const int nbm = (p.M + 255) / 256, nbn = (p.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_glds4_kernel<EPI>), dim3(nbm * nbn), dim3(512), 2 * (256 + 256) * 128, s, p);
-  return check_launch("gemm_glds4_kernel");
-}
-
-template <typename T, int BM, int BN, int EPI, bool S3 = false, bool GL = false>
-int launch_gemm(const GemmP& p, hipStream_t s) {
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  size_t smem = 2 * (size_t)(BM + BN) * (RowBytes<BM>::v + 16) + BM * 8 + 2048;   // + LayerNorm statistics
-  hipLaunchKernelGGL((gemm_tn_kernel<T, BM, BN, EPI, S3, GL>), dim3(nbm * nbn), dim3(256), smem, s, p);
-  return check_launch("gemm_tn_kernel");
-}
-
-// > 64 KiB of dynamic LDS needs an explicit opt-in per kernel; done once for every instantiation,
-// outside any stream capture (gemm_prepare()).
-template <typename T, int BM, int BN, int EPI>
-bool prepare_one() {
-  const size_t smem = 2 * (size_t)(BM + BN) * (RowBytes<BM>::v + 16) + BM * 8 + 2048;   // + LayerNorm statistics
-  bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T, BM, BN, EPI>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess;
-  if constexpr (sizeof(T) == 2 && BM == 128 && BN == 128)
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T, BM, BN, EPI, false, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess;
-  return ok;
-}
-template <typename T, int EPI>
-bool prepare_epi() {
-  bool ok = prepare_one<T, 128, 128, EPI>() && prepare_one<T, 64, 64, EPI>();
-  if constexpr (sizeof(T) == 2)
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds3_kernel<EPI, 4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (256 + 128) * 128) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds3_kernel<EPI, 2>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (128 + 128) * 128) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds4_kernel<EPI>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 256) * 128) == hipSuccess &&
-         hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds2s_kernel<EPI>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 128) * 128) == hipSuccess;
-  if constexpr (EPI != MH_EPI_GEGLU) ok = ok && prepare_one<T, 32, 32, EPI>() && prepare_one<T, 16, 16, EPI>();   // GEGLU pairs two 16-col blocks per wave
-  return ok;
-}
-template <int EPI>
-bool prepare_s3g() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_s3g_kernel<EPI, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             3 * (128 + 128) * 128) == hipSuccess;
-}
-
-template <typename T>
-bool prepare_type() {
-  return prepare_epi<T, MH_EPI_STORE>() && prepare_epi<T, MH_EPI_STORE_F32>() && prepare_epi<T, MH_EPI_RESID>() &&
-         prepare_epi<T, MH_EPI_GEGLU>() && prepare_epi<T, MH_EPI_BIAS_GELU>() && prepare_epi<T, MH_EPI_GATE_RESID>() &&
-         prepare_epi<T, MH_EPI_KV_SCATTER>() && prepare_epi<T, MH_EPI_QKV_VT>() && prepare_epi<T, MH_EPI_QKV_CACHE>() &&
-         prepare_epi<T, MH_EPI_BIAS_GELU_ERF>();
+  return Mx8Epis::visit(epi, [&](auto e) { return dispatch_mx8<decltype(e)::value>(p, s); });
 }
 
 // below this many 32x32 tiles the 16x16 split-K tile is used (option gemm_splitk_tiles, 0 = never)
@@ -1983,13 +1873,13 @@ int dispatch_tile(const GemmP& p, hipStream_t s, int plan_M) {
   // plan_M > 0: the tile is chosen as for a problem of plan_M rows (the caller runs a slice of a larger GEMM and wants the
   // larger one's kernel, hence its summation order: mh_t5_score against mh_t5_decoder_forward)
   const int pm = plan_M > 0 ? plan_M : p.M;
-  if constexpr (std::is_same<T, float>::value && (EPI == MH_EPI_STORE_F32 || EPI == MH_EPI_QKV_VT ||
-                                                  EPI == MH_EPI_GATE_RESID || EPI == MH_EPI_BIAS_GELU)) {
+  constexpr auto ks = tile_kernels<T, EPI>();
+  if constexpr (std::is_same<T, float>::value && Bf16x3Epis::has(EPI)) {
     // A pre-split as well: the three-stage LDS-DMA form.  128-row tiles only: the 256-row form needs two fragment sets of
     // 128 VGPRs beside 64 accumulators and hipcc spills fragments -- registers written by the inline-asm LDS reads, which it
     // believes valid and stores to scratch BEFORE the data has arrived (wrong results, found by the DiT-B 1024-point golden).
-    if (p.split3 & 2) return launch_s3g<EPI, 2>(p, s);
-    if (p.split3) return launch_gemm<T, 64, 64, EPI, true>(p, s);
+    if (p.split3 & 2) return ks.launch(S3g<EPI, 2>{}, p, s);
+    if (p.split3) return ks.launch(Tn<T, 64, 64, EPI, true>{}, p, s);
   }
   // tile by grid size: the chip has 256 CUs; a K step of a wave costs MI*NI MFMAs, so small problems want
   // many small tiles (DiT: M = 256 rows) and big ones the 128x128 tile (encoder: M = 40k rows)
@@ -2004,11 +1894,11 @@ int dispatch_tile(const GemmP& p, hipStream_t s, int plan_M) {
       const bool vec_ok = p.N % 4 == 0 && p.ldc % 4 == 0 && (p.gate == nullptr || p.gate_ld % 4 == 0) &&
                           (EPI != MH_EPI_GEGLU || p.N % 8 == 0) && p.K % 64 == 0;
       if (option(OPT_GEMM_GLDS) >= 3 && p.K <= option(OPT_GEMM_2STAGE_MAX_K) && !p.stats_out && vec_ok)
-        return launch_glds2s<EPI>(p, s);      // short K: two workgroups per CU, one's prologue / epilogue under the other's K loop
+        return ks.launch(Glds2s<EPI>{}, p, s);      // short K: two workgroups per CU, one's prologue / epilogue under the other's K loop
       if (option(OPT_GEMM_GLDS) >= 2 && tiles256 >= kGemmTile256Min && !p.stats_out && vec_ok) {
         // fewer 256-row tiles than half the CUs: the 128-row form of the same kernel doubles the workgroups (batched DiT-S bf16,
         // N = 384: 96 -> 192 workgroups, 153 -> 137 ms per 100 steps; at 192 tiles -- DiT-B, N = 768 -- it loses, 294 -> 308)
-        if (tiles256 < 128 && option(OPT_GEMM_GLDS) >= 3) return launch_glds3<EPI, 2>(p, s);
+        if (tiles256 < 128 && option(OPT_GEMM_GLDS) >= 3) return ks.launch(Glds3<EPI, 2>{}, p, s);
         // enough 256 x 256 tiles to fill the chip: the two-stage kernel with 128 x 64 wave tiles
         // ... when its last round of workgroups is not mostly idle: one workgroup per CU, so 628 tiles (osuT5-large's N = 1024
         // projections) are three rounds at 82 % -- measured 276 us against 244 for the 256 x 128 tile, while 471 tiles (92 %) gain
@@ -2016,62 +1906,76 @@ int dispatch_tile(const GemmP& p, hipStream_t s, int plan_M) {
         const long min256sq = option(OPT_GEMM_TILE256SQ_MIN);
         const long rounds = (tiles256sq + 255) / 256;
         const bool full_rounds = min256sq == 1 || tiles256sq * 100 >= rounds * 256 * 88;     // (option value 1: always, for tests)
-        if (min256sq > 0 && tiles256sq >= min256sq && full_rounds && option(OPT_GEMM_GLDS) >= 3) return launch_glds4<EPI>(p, s);
-        return launch_glds3<EPI, 4>(p, s);
+        if (min256sq > 0 && tiles256sq >= min256sq && full_rounds && option(OPT_GEMM_GLDS) >= 3) return ks.launch(Glds4<EPI>{}, p, s);
+        return ks.launch(Glds3<EPI, 4>{}, p, s);
       }
-      if (option(OPT_GEMM_GLDS) != 0) return launch_gemm<T, 128, 128, EPI, false, true>(p, s);
+      if (option(OPT_GEMM_GLDS) != 0) return ks.launch(Tn<T, 128, 128, EPI, false, true>{}, p, s);
     }
-    return launch_gemm<T, 128, 128, EPI>(p, s);
+    return ks.launch(Tn<T, 128, 128, EPI>{}, p, s);
   }
   if constexpr (EPI == MH_EPI_GEGLU) {
-    return launch_gemm<T, 64, 64, EPI>(p, s);
+    return ks.launch(Tn<T, 64, 64, EPI>{}, p, s);
   } else {
-    if (tiles64 >= 192) return launch_gemm<T, 64, 64, EPI>(p, s);
+    if (tiles64 >= 192) return ks.launch(Tn<T, 64, 64, EPI>{}, p, s);
     const long tiles32 = (long)((pm + 31) / 32) * ((p.N + 31) / 32);
-    if (p.ascending_k || tiles32 >= splitk_threshold()) return launch_gemm<T, 32, 32, EPI>(p, s);
-    return launch_gemm<T, 16, 16, EPI>(p, s);
+    if (p.ascending_k || tiles32 >= splitk_threshold()) return ks.launch(Tn<T, 32, 32, EPI>{}, p, s);
+    return ks.launch(Tn<T, 16, 16, EPI>{}, p, s);
   }
 }
 
 template <typename T>
 int dispatch_epi(const GemmP& p, int epi, hipStream_t s, int plan_M) {
-  switch (epi) {
-    case MH_EPI_STORE: return dispatch_tile<T, MH_EPI_STORE>(p, s, plan_M);
-    case MH_EPI_STORE_F32: return dispatch_tile<T, MH_EPI_STORE_F32>(p, s, plan_M);
-    case MH_EPI_RESID: return dispatch_tile<T, MH_EPI_RESID>(p, s, plan_M);
-    case MH_EPI_GEGLU: return dispatch_tile<T, MH_EPI_GEGLU>(p, s, plan_M);
-    case MH_EPI_BIAS_GELU: return dispatch_tile<T, MH_EPI_BIAS_GELU>(p, s, plan_M);
-    case MH_EPI_GATE_RESID: return dispatch_tile<T, MH_EPI_GATE_RESID>(p, s, plan_M);
-    case MH_EPI_KV_SCATTER: return dispatch_tile<T, MH_EPI_KV_SCATTER>(p, s, plan_M);
-    case MH_EPI_QKV_VT: return dispatch_tile<T, MH_EPI_QKV_VT>(p, s, plan_M);
-    case MH_EPI_QKV_CACHE: return dispatch_tile<T, MH_EPI_QKV_CACHE>(p, s, plan_M);
-    case MH_EPI_BIAS_GELU_ERF: return dispatch_tile<T, MH_EPI_BIAS_GELU_ERF>(p, s, plan_M);
+  if (!Epis::has(epi)) {
+    set_error("mh_gemm: unknown epilogue %d", epi);
+    return MH_ERR_ARG;
   }
-  set_error("mh_gemm: unknown epilogue %d", epi);
-  return MH_ERR_ARG;
+  return Epis::visit(epi, [&](auto e) { return dispatch_tile<T, decltype(e)::value>(p, s, plan_M); });
+}
+
+// the kernels' argument from the caller's descriptor; es = bytes per operand element
+GemmP make_params(const MhGemm& g, int es, bool ascending_k) {
+  GemmP p{};
+  p.A = (const char*)g.A; p.lda_b = (long)g.lda * es;
+  p.W = (const char*)g.W; p.ldw_b = (long)g.ldw * es;
+  p.C = g.C; p.ldc = g.ldc;
+  p.M = g.M; p.N = g.N; p.K = g.K;
+  p.bias = g.bias; p.gate = g.gate; p.gate_ld = g.gate_ld; p.rows_per_batch = g.rows_per_batch;
+  p.kv_B = g.kv_B; p.kv_H = g.kv_H; p.kv_L = g.kv_L;
+  p.C2 = g.C2; p.n_split = g.n_split; p.kv_Lpad = g.kv_Lpad;
+  p.C3 = g.C3; p.C4 = g.C4; p.cache_len = g.cache_len;
+  p.stats_out = g.stats_out; p.ln_stats = g.ln_stats; p.ln_strips = g.ln_strips; p.ln_shift = g.ln_shift;
+  p.ln_scale = g.ln_scale; p.ln_ld = g.ln_ld; p.ln_eps = g.ln_eps;
+  p.ascending_k = ascending_k;
+  p.split3 = g.w_split3;
+  if (g.dtype == MH_MX8) {
+    p.a_scale = g.a_scale; p.w_scale = g.w_scale; p.ks_b = mx8_scale_row_bytes(g.K);
+    if (g.mx_out) { p.mxq = g.mx_out; p.mxs = g.mx_out_scales; p.mxs_b = mx8_scale_row_bytes(g.epilogue == MH_EPI_GEGLU ? g.N / 2 : g.N); }
+  }
+  return p;
 }
 
 }  // namespace
 
 int gemm_prepare() {
-  static bool done = false;
-  if (done) return MH_OK;
-  if (!(prepare_type<bf16_t>() && prepare_type<float>() && prepare_s3g<MH_EPI_QKV_VT>() && prepare_s3g<MH_EPI_GATE_RESID>() &&
-        prepare_s3g<MH_EPI_BIAS_GELU>() && prepare_s3g<MH_EPI_STORE_F32>() && prepare_mx8<MH_EPI_STORE>() &&
-        prepare_mx8<MH_EPI_STORE_F32>() && prepare_mx8<MH_EPI_RESID>() && prepare_mx8<MH_EPI_GEGLU>() && prepare_mx8<MH_EPI_BIAS_GELU>() &&
-        prepare_mx8<MH_EPI_GATE_RESID>() && prepare_mx8<MH_EPI_KV_SCATTER>() && prepare_mx8<MH_EPI_QKV_VT>())) {
-    set_error("gemm_prepare: hipFuncSetAttribute failed: %s", hipGetErrorString(hipGetLastError()));
-    return MH_ERR_LAUNCH;
-  }
-  done = true;
-  return MH_OK;
+  static PerDeviceOnce once;
+  return once.run([] {
+    const bool ok = Epis::all([](auto e) { return tile_kernels<bf16_t, decltype(e)::value>().prepare() && tile_kernels<float, decltype(e)::value>().prepare(); }) &&
+                    Mx8Epis::all([](auto e) { return mx8_kernels<decltype(e)::value>().prepare(); });
+    if (!ok) {
+      set_error("gemm_prepare: hipFuncSetAttribute failed: %s", hipGetErrorString(hipGetLastError()));
+      return (int)MH_ERR_LAUNCH;
+    }
+    return (int)MH_OK;
+  });
 }
 
 int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
   MH_REQUIRE(g.A && g.W && (g.C || (g.dtype == MH_MX8 && g.mx_out)), "mh_gemm: null operand");
   MH_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "mh_gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);
   MH_REQUIRE(g.dtype == MH_F32 || g.dtype == MH_BF16 || g.dtype == MH_MX8, "mh_gemm: bad dtype %d", g.dtype);
-  if (g.dtype == MH_MX8) {
+  const bool mx = g.dtype == MH_MX8;
+  const int es = mx ? 1 : g.dtype == MH_BF16 ? 2 : 4;
+  if (mx) {
     // e4m3 elements (1 byte) + E8M0 scales: K steps of 128, vector epilogue; outputs are bf16 / fp32 as the epilogue says
     MH_REQUIRE(g.a_scale && g.w_scale, "mh_gemm: MH_MX8 needs a_scale and w_scale");
     MH_REQUIRE(g.K % 128 == 0 && g.lda % 16 == 0 && g.ldw % 16 == 0 && g.lda >= g.K && g.ldw >= g.K,
@@ -2081,34 +1985,15 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
     MH_REQUIRE(g.N % 4 == 0 && g.ldc % 4 == 0 && (g.gate == nullptr || g.gate_ld % 4 == 0) && (g.epilogue != MH_EPI_GEGLU || g.N % 32 == 0) &&
                    !g.stats_out && !g.ln_stats && !g.w_split3,
                "mh_gemm: MH_MX8 needs N, ldc (gate_ld) multiples of 4 and takes no LayerNorm fusion / split3");
-    if (g.epilogue == MH_EPI_GATE_RESID) MH_REQUIRE(g.gate && g.rows_per_batch > 0, "mh_gemm: GATE_RESID needs gate and rows_per_batch");
-    if (g.epilogue == MH_EPI_KV_SCATTER)
-      MH_REQUIRE(g.kv_B > 0 && g.kv_H > 0 && g.kv_L > 0 && g.M == g.kv_B * g.kv_L && g.N % (g.kv_H * 64) == 0, "mh_gemm: bad KV scatter geometry");
-    if (g.epilogue == MH_EPI_QKV_VT)
-      MH_REQUIRE(g.C2 && g.kv_H > 0 && g.kv_L > 0 && g.kv_Lpad >= g.kv_L && g.n_split > 0 && g.N - g.n_split == g.kv_H * 64 && g.M % g.kv_L == 0,
-                 "mh_gemm: bad QKV_VT geometry");
-    { int rc = gemm_prepare(); if (rc != MH_OK) return rc; }
-    GemmP q{};
-    q.A = (const char*)g.A; q.lda_b = g.lda; q.W = (const char*)g.W; q.ldw_b = g.ldw; q.C = g.C; q.ldc = g.ldc;
-    q.M = g.M; q.N = g.N; q.K = g.K; q.bias = g.bias; q.gate = g.gate; q.gate_ld = g.gate_ld; q.rows_per_batch = g.rows_per_batch;
-    q.kv_B = g.kv_B; q.kv_H = g.kv_H; q.kv_L = g.kv_L; q.C2 = g.C2; q.n_split = g.n_split; q.kv_Lpad = g.kv_Lpad;
-    q.a_scale = g.a_scale; q.w_scale = g.w_scale; q.ks_b = mx8_scale_row_bytes(g.K);
-    if (g.mx_out) {
-      const int width = g.epilogue == MH_EPI_GEGLU ? g.N / 2 : g.N;
-      MH_REQUIRE(g.epilogue == MH_EPI_GEGLU || g.epilogue == MH_EPI_BIAS_GELU, "mh_gemm: mx_out goes with MH_EPI_GEGLU / MH_EPI_BIAS_GELU");
-      MH_REQUIRE(g.mx_out_scales && width % 128 == 0 && g.ldc >= width && ((uintptr_t)g.mx_out % 4) == 0,
-                 "mh_gemm: mx_out needs mx_out_scales, an output width that is a multiple of 128 and ldc >= width (width=%d ldc=%d)", width, g.ldc);
-      q.mxq = g.mx_out; q.mxs = g.mx_out_scales; q.mxs_b = mx8_scale_row_bytes(width);
-    }
-    return dispatch_mx8_epi(q, g.epilogue, s);
+  } else {
+    const int vec = 16 / es;
+    MH_REQUIRE(g.K % vec == 0 && g.lda % vec == 0 && g.ldw % vec == 0,
+               "mh_gemm: K=%d lda=%d ldw=%d must be multiples of %d", g.K, g.lda, g.ldw, vec);
+    MH_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0, "mh_gemm: operands must be 16-byte aligned");
+    MH_REQUIRE(g.lda >= g.K && g.ldw >= g.K, "mh_gemm: leading dimension smaller than K");
+    if (g.epilogue == MH_EPI_GEGLU) MH_REQUIRE(g.N % 32 == 0, "mh_gemm: GEGLU needs N %% 32 == 0 (N=%d)", g.N);
   }
-  const int es = g.dtype == MH_BF16 ? 2 : 4;
-  const int vec = 16 / es;
-  MH_REQUIRE(g.K % vec == 0 && g.lda % vec == 0 && g.ldw % vec == 0,
-             "mh_gemm: K=%d lda=%d ldw=%d must be multiples of %d", g.K, g.lda, g.ldw, vec);
-  MH_REQUIRE(((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0, "mh_gemm: operands must be 16-byte aligned");
-  MH_REQUIRE(g.lda >= g.K && g.ldw >= g.K, "mh_gemm: leading dimension smaller than K");
-  if (g.epilogue == MH_EPI_GEGLU) MH_REQUIRE(g.N % 32 == 0, "mh_gemm: GEGLU needs N %% 32 == 0 (N=%d)", g.N);
+  // the epilogues' geometry, whatever the operand type
   if (g.epilogue == MH_EPI_GATE_RESID)
     MH_REQUIRE(g.gate && g.rows_per_batch > 0, "mh_gemm: GATE_RESID needs gate and rows_per_batch");
   if (g.epilogue == MH_EPI_KV_SCATTER)
@@ -2118,24 +2003,21 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
     MH_REQUIRE(g.C2 && g.kv_H > 0 && g.kv_L > 0 && g.kv_Lpad >= g.kv_L && g.n_split > 0 &&
                    g.N - g.n_split == g.kv_H * 64 && g.M % g.kv_L == 0,
                "mh_gemm: bad QKV_VT geometry");
-  if (g.epilogue == MH_EPI_QKV_CACHE)
+  if (g.epilogue == MH_EPI_QKV_CACHE && !mx)   // (not built for MH_MX8: refused by dispatch_mx8_epi)
     MH_REQUIRE(g.C2 && g.C3 && g.C4 && g.kv_H > 0 && g.kv_L > 0 && g.kv_Lpad >= g.kv_L && g.cache_len >= g.kv_L &&
                    g.n_split == g.kv_H * 64 && g.N == 3 * g.kv_H * 64 && g.M % g.kv_L == 0,
                "mh_gemm: bad QKV_CACHE geometry");
   { int rc = gemm_prepare(); if (rc != MH_OK) return rc; }
-  GemmP p;
-  p.ascending_k = ascending_k;
-  p.split3 = g.w_split3;
-  p.C3 = g.C3; p.C4 = g.C4; p.cache_len = g.cache_len;
-  p.C2 = g.C2; p.n_split = g.n_split; p.kv_Lpad = g.kv_Lpad;
-  p.A = (const char*)g.A; p.lda_b = (long)g.lda * es;
-  p.W = (const char*)g.W; p.ldw_b = (long)g.ldw * es;
-  p.C = g.C; p.ldc = g.ldc;
-  p.M = g.M; p.N = g.N; p.K = g.K;
-  p.bias = g.bias; p.gate = g.gate; p.gate_ld = g.gate_ld; p.rows_per_batch = g.rows_per_batch;
-  p.kv_B = g.kv_B; p.kv_H = g.kv_H; p.kv_L = g.kv_L;
-  p.stats_out = g.stats_out; p.ln_stats = g.ln_stats; p.ln_strips = g.ln_strips; p.ln_shift = g.ln_shift;
-  p.ln_scale = g.ln_scale; p.ln_ld = g.ln_ld; p.ln_eps = g.ln_eps;
+  const GemmP p = make_params(g, es, ascending_k);
+  if (mx) {
+    if (g.mx_out) {
+      const int width = g.epilogue == MH_EPI_GEGLU ? g.N / 2 : g.N;
+      MH_REQUIRE(Mx8OutEpis::has(g.epilogue), "mh_gemm: mx_out goes with MH_EPI_GEGLU / MH_EPI_BIAS_GELU");
+      MH_REQUIRE(g.mx_out_scales && width % 128 == 0 && g.ldc >= width && ((uintptr_t)g.mx_out % 4) == 0,
+                 "mh_gemm: mx_out needs mx_out_scales, an output width that is a multiple of 128 and ldc >= width (width=%d ldc=%d)", width, g.ldc);
+    }
+    return dispatch_mx8_epi(p, g.epilogue, s);
+  }
   if (g.stats_out)
     MH_REQUIRE((g.epilogue == MH_EPI_STORE_F32 || g.epilogue == MH_EPI_GATE_RESID) && g.N % 16 == 0,
                "mh_gemm: stats_out needs a fp32-output epilogue (STORE_F32 / GATE_RESID) and N %% 16 == 0");
@@ -2146,9 +2028,7 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
   if ((g.w_split3 & 2) == 0) MH_REQUIRE((g.w_split3 & 4) == 0, "mh_gemm: w_split3 & 4 (pre-split output) only with w_split3 & 2");
   if ((g.w_split3 & 2) && g.epilogue == MH_EPI_BIAS_GELU) MH_REQUIRE(g.w_split3 & 4, "mh_gemm: the A-pre-split BIAS_GELU form writes its output pre-split (w_split3 & 4)");
   if (g.w_split3)
-    MH_REQUIRE(g.dtype == MH_F32 && g.K % 32 == 0 && g.ldw % 32 == 0 &&
-                   (g.epilogue == MH_EPI_STORE_F32 || g.epilogue == MH_EPI_QKV_VT || g.epilogue == MH_EPI_GATE_RESID ||
-                    g.epilogue == MH_EPI_BIAS_GELU),
+    MH_REQUIRE(g.dtype == MH_F32 && g.K % 32 == 0 && g.ldw % 32 == 0 && Bf16x3Epis::has(g.epilogue),
                "mh_gemm: w_split3 is an fp32 path (K, ldw multiples of 32; STORE_F32 / QKV_VT / GATE_RESID / BIAS_GELU)");
   if (g.ln_stats)
     MH_REQUIRE(g.dtype == MH_F32 && g.ln_shift && g.ln_scale && g.ln_strips > 0 && g.rows_per_batch > 0 && g.ln_ld >= g.K,

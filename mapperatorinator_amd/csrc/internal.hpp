@@ -1,10 +1,32 @@
 // Cross-file internal entry points of libmapperhip (C++ side of the C ABI in include/mapperhip.h).
 #pragma once
+#include <mutex>
+#include <set>
+
 #include "common.hpp"
 
 namespace mh {
 
-int gemm_prepare();  // one-time kernel attribute setup; call before any stream capture
+// Set-up that is needed once per DEVICE (hipFuncSetAttribute is a property of the function on one device): run(f) calls f() for
+// the calling thread's current device unless an earlier call has returned MH_OK there, under a lock.  (Without a device the id
+// stays -1 and f() reports the failure in its own words.)
+class PerDeviceOnce {
+ public:
+  template <class F> int run(F&& f) {
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> g(mu_);
+    if (done_.count(dev)) return MH_OK;
+    const int rc = f();
+    if (rc == MH_OK) done_.insert(dev);
+    return rc;
+  }
+ private:
+  std::mutex mu_;
+  std::set<int> done_;
+};
+
+int gemm_prepare();  // kernel attribute setup, once per device; call before any stream capture
 // ascending_k: never pick the 16x16 split-K tile, so the fp32 summation order (k ascending, one accumulator) and with it
 // every bit of the result is independent of M (the tile choice otherwise follows the grid size)
 // plan_M > 0: pick the tile as a GEMM of plan_M rows would (a row block of a larger problem keeps the larger problem's kernel,

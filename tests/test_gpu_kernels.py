@@ -139,6 +139,31 @@ def test_gemm_lds_dma_tile_equals_register_staged_tile(shape):
     assert (outs[1][0].double() - ref).abs().max().item() < 2e-5 * math.sqrt(K) * 4 + 1e-4
 
 
+def test_gemm_large_lds_kernel_on_a_second_device():
+    """The opt-in to more than 64 KB of dynamic LDS is an attribute of a kernel ON ONE DEVICE: gemm_prepare() keeps its "done"
+    per device.  A bf16 GEMM that takes the three-stage 128 x 128 LDS-DMA kernel (96 KB) runs on device 0, then on device 1 of
+    the same process, and both are right against fp64 (the bound of test_gemm_store_and_transpose_detecting)."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one visible device")
+    import mapperatorinator_amd._lib as ML
+    L, _ = _lib()
+    M, N, K = 2600, 1100, 768
+    g = torch.Generator().manual_seed(5)
+    A, W = _bf16r(torch.randn(M, K, generator=g)), _bf16r(torch.randn(N, K, generator=g))
+    bias = torch.randn(N, generator=g)
+    ref = A.double() @ W.double().t() + bias.double()
+    old_min = ML.set_option("gemm_tile128_min", 1)
+    try:
+        for dev in (0, 1):
+            with torch.cuda.device(dev):
+                out = run_gemm(A, W, L.EPI_STORE_F32, L.MH_BF16, bias=bias)
+            err = (out.double() - ref).abs().max().item()
+            print(f"device {dev}: max |err| {err:.3e}")
+            assert err < (2e-5 * math.sqrt(K) * 4 + 1e-4) * max(1.0, ref.abs().max().item() / 10), (dev, err)
+    finally:
+        ML.set_option("gemm_tile128_min", old_min)
+
+
 def test_gemm_bf16x3_refuses_the_fused_layernorm_prologue():
     """LayerNorm + modulate fused into the bf16 x 3 GEMM's A load (an option of the batched DiT until round 5, measured slower
     than the stand-alone pass) once returned non-repeatable rows and did so again after an unrelated edit; the cause was never
