@@ -81,6 +81,8 @@ int mh_abi_version(void);
  *                                                   full (0 = never; bit-identical to the 256x128 three-stage kernel)
  *   "gemm_2stage_max_k"  MH_GEMM_2STAGE_MAX_K  512  bf16 GEMM with K <= this: 128x128 tile on two LDS stages, two workgroups per CU
  *                                                   (0 = never; bit-identical)
+ *   "beam_step_path"     MH_BEAM_STEP_PATH     0    mh_beam_step: 0 = LDS kernel where it fits, else the streaming kernel; 1 = LDS
+ *                                                   kernel or an error; 2 = streaming kernel everywhere (bit-identical)
  * (gemm_tile128_min and dit_split3_min_rows are documented next to their definitions in csrc/api.hip: 11 options in all.
  * Round 5 removed the measured-slower variants decode_overlap, decode_fold_oproj, decode_cu_split, decode_self_rows,
  * mx8_waves = 4, dit_s3_fused_ln, the debugging aid gemm_lds_pad, the variant switches attn_flash2, dit_s3_presplit and
@@ -476,7 +478,11 @@ int mh_t5_generate(const MhT5Config* cfg, const MhT5Weights* w, const void* cros
  * nb] = the row each new running beam continues (the argument of mh_t5_reorder_cache: MapperatorinatorCache.reorder_cache,
  * inference/cache_utils.py:16-20), `last` [G nb] = the token each running beam is fed next, `flags` [G][3] = (heuristic still
  * open, every candidate hit EOS / max_length, every finished slot filled) from which the host forms HF's loop condition.
- * num_beams in 2 .. 8, K <= 4096, 4 num_beams V + 8 K' bytes (K' = K rounded up to a power of two) within 120 KB of LDS. */
+ * Limits: num_beams in 2 .. 8, K <= 8192, any V (num_beams V < 2^31), greedy beams, no types_first lookback renormalisation.  Two
+ * kernels with the same contract and the same bits: where K <= 4096 and 4 num_beams V + 8 K' bytes (K' = K rounded up to a power of
+ * two) fit 120 KB of LDS the scores live in LDS; otherwise the streaming kernel keeps the K candidates in LDS only and recomputes a
+ * score from the logits in every pass (option "beam_step_path": 0 = that rule, 1 = the LDS kernel or MH_ERR_ARG, 2 = the streaming
+ * kernel everywhere). */
 typedef struct MhBeamStep {
   const float* logits;          /* [RE][V] fp32: RE = G nb rows, or 2 G nb under guidance ([negative rows | prompt rows]) */
   const uint8_t* eos_table;     /* [V] 1 = an EOS id (get_eos_token_id, server.py:72-80)                                    */
@@ -493,6 +499,9 @@ typedef struct MhBeamStep {
 } MhBeamStep;
 int64_t mh_beam_step_lds_bytes(int num_beams, int V);
 int mh_beam_step(const MhBeamStep* bs, void* stream);
+/* Which kernel mh_beam_step runs for this shape under the current "beam_step_path": 0 = refused (a limit above), 1 = LDS kernel, 2 =
+ * streaming kernel.  Additive at ABI 11 (one symbol, one option; no struct changes layout): a library without it is an older 11. */
+int mh_beam_step_path(int num_beams, int V, int K);
 
 /* Step-wise decode for host-driven search.  Replaces the per-position `self(**model_inputs)` of HF
  * `GenerationMixin._beam_search` (num_beams > 1: osuT5/osuT5/inference/processor.py:147,159; server.py:137) and

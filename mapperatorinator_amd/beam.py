@@ -15,8 +15,9 @@ vectorised `GenerationMixin._beam_search` -- transformers >= 4.50; line referenc
 
 The device side is the step-wise entry of the library (`mh_t5_step`: one decoder position for all (chunk, beam) rows, raw
 logits out; `mh_t5_reorder_cache`).  Round 6: for greedy beams the WHOLE bookkeeping above is one kernel per token, `mh_beam_step`
-(csrc/beam.hip: log_softmax, guidance, processors, top-K over beams x V by an in-LDS sort, EOS split, next-beam selection, finished-set
-merge, the early-stopping heuristic) -- `_beam_search_kernel` below; the host reads three flags per chunk and step.  The torch-op
+(csrc/beam.hip: log_softmax, guidance, processors, top-K over beams x V by a radix select + a sort of the K, EOS split, next-beam
+selection, finished-set merge, the early-stopping heuristic; 2 .. 8 beams, K <= 8192, any vocabulary: the scores live in LDS where
+they fit 120 KB, else a streaming kernel recomputes them from the logits, same bits) -- `_beam_search_kernel` below; the host reads three flags per chunk and step.  The torch-op
 form (`beam_search` with use_kernel=False; ~40 ATen launches per token) stays for beam-SAMPLE, whose continuations are drawn by
 torch.multinomial / an injected sampler, and as the cross-check of the kernel (tests run both against the reference goldens).  The logits processors of
 server.py:106-134 are applied here with torch ops (the in-kernel sampler of the greedy / sampling path selects per row and
@@ -117,11 +118,11 @@ class BeamProcessors:
 
 
 def kernel_path_available(sp, num_beams: int, vocab_out: int, n_eos: int) -> bool:
-    """mh_beam_step covers greedy beams (no beam-sample), 2 .. 8 beams, K <= 4096 candidates, beams x V scores + the K candidates
-    within 120 KB of LDS."""
+    """mh_beam_step covers greedy beams (no beam-sample), 2 .. 8 beams, K <= 8192 candidates and any vocabulary: the library says
+    which of its two kernels a shape runs (mh_beam_step_path; 0 = refused).  (The types_first lookback renormalisation is refused
+    by both forms of the search.)"""
     K = min(max(2, 1 + n_eos) * num_beams, num_beams * vocab_out)
-    k_pad = 1 << max(0, (K - 1).bit_length())
-    return (not sp.do_sample) and 2 <= num_beams <= 8 and K <= 4096 and num_beams * vocab_out * 4 + 16 + k_pad * 8 <= 120 * 1024
+    return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), int(K)) != 0
 
 
 @torch.no_grad()
@@ -252,11 +253,12 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     T5Engine.generate and the scheduler build), and cross_kv still has G rows.
     Returns int64 (G, P + new) on the engine's device: the best hypothesis per chunk, shorter ones filled the way HF does
     (`pad_token_id or eos_token_id[0]`: with pad id 0 that is the FIRST EOS id).
-    `use_kernel`: None = mh_beam_step whenever it covers the call (greedy beams, see kernel_path_available), False = the torch-op
+    `use_kernel`: None = mh_beam_step whenever it covers the call (greedy beams, 2 .. 8 of them, K <= 8192: kernel_path_available), False = the torch-op
     bookkeeping below, True = the kernel or an error."""
     can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(list(eos_ids))) and sample_fn is None
     if use_kernel is True and not can:
-        raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, > 8 beams, beams x V > 16384 or K > 4096)")
+        raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
+                                  "K = max(2, 1 + #eos) x beams > 8192)")
     if can and use_kernel is not False:
         return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping)
     dev, lib, p = engine.device, engine.lib, engine.packed

@@ -48,6 +48,7 @@ static OptionSlot g_options[OPT_COUNT] = {
     {"gemm_2stage_max_k", "MH_GEMM_2STAGE_MAX_K", 512, false},   // bf16 GEMM with K <= this: the two-stage 128 x 128 kernel (64 KB of LDS: two workgroups per CU) instead of the three-stage forms (0 = never).  Batched DiT-S bf16 (K = 384 on three of four projections): 130.3 -> 121.6 ms per 100 steps; at 1024 DiT-B (K = 768) 284.6 -> 287.7, at 4096 299.7
     {"dit_skinny_max_rows", "MH_DIT_SKINNY_MAX_ROWS", 512, false},   // fp32-semantics DiT with at most this many rows (N T: one chunk = 256): the four block GEMMs as one-round-trip 16 x 16 latency kernels with the LayerNorm taken from registers (dit.hip dit_skinny_kernel); 0 = the LDS-tiled GEMMs (different fp32 summation order)
     {"score_block_rows", "MH_SCORE_BLOCK_ROWS", 1024, false},   // mh_t5_score: scored positions per LM-head block (the fp32 logits scratch holds this many rows, whatever B and T); results do not depend on it.  The block's GEMM runs with the tile of the whole [B T, V] problem, so a small block leaves most CUs idle: whole pass at base dims bf16, B 32, T 2560, V 3837: 256 rows 53.9 ms, 512 48.1, 1024 44.7, 2048 43.6, 4096 43.4 (T 512, V 1849: 10.1 / 9.1 / 8.6 / 8.4 / 8.3); 1024 keeps the scratch at 16 MB for most of the gain
+    {"beam_step_path", "MH_BEAM_STEP_PATH", 0, false},   // mh_beam_step: 0 = the LDS kernel wherever num_beams x V scores + K <= 4096 candidates fit 120 KB, else the streaming kernel (scores recomputed from the logits in every pass; any V, K <= 8192); 1 = the LDS kernel or an error; 2 = the streaming kernel everywhere (tests and measurements: the two are bit-identical)
 };
 
 static thread_local const MhOptionSet* tl_option_set = nullptr;

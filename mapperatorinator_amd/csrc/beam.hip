@@ -12,6 +12,10 @@
 // version sorted all 8192 values: 86 us per token against ~15 us) --, the selection logic runs on that sorted list, the surviving hypotheses are copied from the IN state to the OUT state (ping-pong: every
 // workgroup reads what the previous step wrote).  Greedy beams only (do_sample = 0): beam-SAMPLE draws its continuations with
 // torch.multinomial / an injected sampler and stays on the host-side path.
+// Two kernels, one body (beam_step_kernel<kStream>): the LDS kernel keeps the num_beams x V accumulated scores in LDS (at most 120 KB
+// with the K <= 4096 candidates); the STREAMING kernel keeps per-beam softmax / processor state only (BeamRow) and recomputes a score
+// from the logits -- read once from HBM, from L2 afterwards -- in every pass that needs one, so any vocabulary and K <= 8192 fit.
+// Both evaluate a score with beam_score() and reduce a row in the same thread -> column order: same bits wherever both can run.
 #include <math.h>
 
 #include "internal.hpp"
@@ -26,7 +30,10 @@ __device__ inline bool beam_before(const BeamKV& a, const BeamKV& b) { return a.
 
 constexpr int kBeamThreads = 512;
 constexpr int kBeamWaves = kBeamThreads / 64;
-constexpr int kBeamMaxK = 4096;      // candidates per chunk the selection logic holds flags for
+constexpr int kBeamMaxK = 8192;      // candidates per chunk the selection logic holds flags for
+constexpr int kBeamLdsMaxK = 4096;   // ... of them under the LDS kernel
+constexpr int kBeamLdsBytes = 120 * 1024;   // LDS kernel: score array + candidates
+constexpr int kBeamMaxBeams = 8;
 
 // order-preserving integer image of a float (-0.0 folded onto +0.0, so equal floats have equal images)
 __device__ inline unsigned beam_okey(float x) {
@@ -72,6 +79,69 @@ __device__ inline unsigned long long beam_rank_key(float sc, int pos) {
   return ((unsigned long long)beam_okey(sc) << 32) | (unsigned)(0x7fffffff - pos);
 }
 
+// what one beam's row of accumulated scores depends on besides the logits: log-softmax maximum / log-sum-exp of the prompt row (and of
+// the negative row under guidance), MonotonicTimeShift bound, temperature of the step, running score
+struct BeamRow { float mp, lse_p, mn, lse_n, temp, rs; int ltv; };
+
+// accumulated score of column v of a beam from its raw logit(s): log_softmax -> guidance -> the processor list -> + running score.
+// THE definition for every pass of both kernels (nothing here may contract into an FMA: the guidance combine is spelled out, the
+// rest is subtract / add / divide)
+__device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, float lp, float ln, int v) {
+  const MhSampling& sp = p.sp;
+  float x = (lp - b.mp) - b.lse_p;
+  if (p.cfg) {   // HF ClassifierFreeGuidanceLogitsProcessor, first in the list, on the reference's row order: second + (first - second) * scale
+    const float xn = (ln - b.mn) - b.lse_n;
+    x = __fadd_rn(x, __fmul_rn(__fsub_rn(xn, x), p.cfg_scale));
+  }
+  if (b.ltv >= 0 && v >= sp.ts_start && v < sp.ts_start + b.ltv) x = -INFINITY;
+  if (sp.timeshift_bias != 0.f && v >= sp.ts_start && v < sp.ts_end) x += sp.timeshift_bias;
+  x = x / b.temp;
+  if (sp.lookback_mask_end > sp.ts_start && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
+  return x + b.rs;
+}
+
+// where a pass gets the chunk's scores from: the LDS array (kStream = false) or the logits + the beams' BeamRow (kStream = true)
+template <bool kStream> struct BeamSrc {
+  const MhBeamStep& p;
+  const float* val;         // LDS [nb V] (LDS kernel)
+  const BeamRow* rows;      // LDS [nb]
+  const float* lg_pos;      // the chunk's prompt rows of the logits, [nb][V]
+  const float* lg_neg;      // ... negative rows (guidance)
+};
+
+// One wave's sweep over columns base0 + lane, + step, ... < end of beam j: f(flat index, score, in range) runs for the WHOLE wave
+// (lanes past `end` get in range = false), so f may vote across the wave.  Four columns per lane are loaded before the first is used
+// (eight changed the streaming kernel's time by 1 %: it is bound by the 512 threads' arithmetic, not by the loads).
+template <bool kStream, typename F>
+__device__ inline void beam_sweep(const BeamSrc<kStream>& s, int j, int base0, int step, int end, F&& f) {
+  const int lane = threadIdx.x & 63, V = s.p.V;
+  constexpr int kU = 4;
+  BeamRow b;
+  if (kStream) b = s.rows[j];
+  for (int vb = base0; vb < end; vb += kU * step) {
+    float lp[kU], ln[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int v = vb + u * step + lane;
+      lp[u] = ln[u] = 0.f;
+      if (v < end) {
+        if (kStream) { lp[u] = s.lg_pos[(long)j * V + v]; if (s.p.cfg) ln[u] = s.lg_neg[(long)j * V + v]; }
+        else lp[u] = s.val[j * V + v];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      if (vb + u * step < end) {           // (wave-uniform)
+        const int v = vb + u * step + lane;
+        const bool ok = v < end;
+        const float x = !ok ? 0.f : kStream ? beam_score(s.p, b, lp[u], ln[u], v) : lp[u];
+        f(j * V + v, x, ok);
+      }
+    }
+  }
+}
+
+template <bool kStream>
 __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float red[kBeamThreads / 64];
@@ -81,18 +151,21 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
   __shared__ unsigned s_prefix;
   __shared__ int s_remaining;
   __shared__ uint8_t s_hit[kBeamMaxK];
-  __shared__ int s_sel_run[8], s_sel_fin[8];                        // selected candidate / merged-list positions (num_beams <= 8)
-  __shared__ float s_run_lp[8], s_fin_sc[8];
-  __shared__ int s_ltv[8];                                          // per beam: value of the last TIME_SHIFT after the last SOS (-1: none)
-  __shared__ float s_temp[8];
+  __shared__ int s_sel_run[kBeamMaxBeams], s_sel_fin[kBeamMaxBeams];   // selected candidate / merged-list positions (num_beams <= 8)
+  __shared__ float s_run_lp[kBeamMaxBeams], s_fin_sc[kBeamMaxBeams];
+  __shared__ BeamRow s_row[kBeamMaxBeams];                          // ltv: value of the last TIME_SHIFT after the last SOS (-1: none)
+  __shared__ int s_seg_above[kBeamMaxBeams * kBeamWaves], s_seg_ties[kBeamMaxBeams * kBeamWaves];   // compaction: per (beam, wave) slice
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nb = p.num_beams, V = p.V, T = p.cur_len, L = p.max_length, R = p.G * nb;
   const MhSampling& sp = p.sp;
   const int n = nb * V;
   int k_pad = 1;
   while (k_pad < p.K) k_pad <<= 1;
-  float* val = reinterpret_cast<float*>(smem);                                   // [n] accumulated scores, flat index j * V + v
-  BeamKV* arr = reinterpret_cast<BeamKV*>(smem + (((size_t)n * 4 + 15) & ~(size_t)15));   // [k_pad] the K best, sorted
+  float* val = reinterpret_cast<float*>(smem);                                   // LDS kernel: [n] accumulated scores, flat index j * V + v
+  BeamKV* arr = reinterpret_cast<BeamKV*>(smem + (kStream ? 0 : (((size_t)n * 4 + 15) & ~(size_t)15)));   // [k_pad] the K best, sorted
+  const float* lg_pos_g = p.logits + (long)(p.cfg ? R + g * nb : g * nb) * V;    // under guidance the prompt rows are the SECOND half
+  const float* lg_neg_g = p.logits + (long)g * nb * V;
+  const BeamSrc<kStream> scores{p, val, s_row, lg_pos_g, lg_neg_g};
 
   // ---- per-beam processor state from the beam's own sequence: MonotonicTimeShiftLogitsProcessor (logit_processors.py:136-183)
   // and the (Conditional)Temperature of the step (:47-82; row 0 of the WHOLE call picks it unless cond_per_row) ------------------
@@ -112,55 +185,70 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
       last_sos = max(last_sos, b);
     }
     if (lane == 0) {
-      s_ltv[j] = (sp.ts_end > sp.ts_start && last_ts != -1 && last_ts > last_sos) ? ids[last_ts] - sp.ts_start : -1;
+      s_row[j].ltv = (sp.ts_end > sp.ts_start && last_ts != -1 && last_ts > last_sos) ? ids[last_ts] - sp.ts_start : -1;
       float temp = sp.temperature;
       const int32_t* hist = sp.cond_per_row ? ids : p.run_in;       // (row 0 of the call = chunk 0, beam 0)
       for (int q = 0; q < sp.n_cond; ++q) {
         const int off = sp.cond_offset[q];
         if (T >= off && (sp.tok_flags[hist[T - off]] & (2 << q))) { temp = sp.cond_temp[q]; break; }
       }
-      s_temp[j] = temp;
+      s_row[j].temp = temp;
+      s_row[j].rs = p.rs_in[g * nb + j];
     }
   }
   __syncthreads();
 
-  // ---- log_softmax (+ guidance) + processors + running score -> val[] --------------------------------------------------------
-  // the prompt rows' logits are staged in LDS once (one round of independent loads); the per-beam maximum / sum then read LDS in the
-  // same thread -> column order as before, so the reductions keep their bits
-  for (int i = tid; i < n; i += kBeamThreads) {
-    const int j = i / V, v = i - j * V, r = g * nb + j;
-    val[i] = p.logits[(long)(p.cfg ? R + r : r) * V + v];                 // under guidance the prompt rows are the SECOND half
-  }
-  __syncthreads();
-  for (int j = 0; j < nb; ++j) {
-    const int r = g * nb + j;
-    float* lg_pos = val + j * V;
-    const float* lg_neg = p.logits + (long)r * V;
-    float mp = -INFINITY, mn = -INFINITY;
-    for (int v = tid; v < V; v += kBeamThreads) { mp = fmaxf(mp, lg_pos[v]); if (p.cfg) mn = fmaxf(mn, lg_neg[v]); }
-    mp = block_max(mp, red);
-    if (p.cfg) mn = block_max(mn, red);
-    float sp_ = 0.f, sn_ = 0.f;
-    for (int v = tid; v < V; v += kBeamThreads) { sp_ += expf(lg_pos[v] - mp); if (p.cfg) sn_ += expf(lg_neg[v] - mn); }
-    sp_ = block_sum(sp_, red);
-    if (p.cfg) sn_ = block_sum(sn_, red);
-    const float lse_p = logf(sp_), lse_n = p.cfg ? logf(sn_) : 0.f;
-    const int ltv = s_ltv[j];
-    const float temp = s_temp[j], rs = p.rs_in[r];
-    for (int v = tid; v < V; v += kBeamThreads) {      // (each thread rewrites exactly the columns it read)
-      float x = (lg_pos[v] - mp) - lse_p;
-      if (p.cfg) {   // HF ClassifierFreeGuidanceLogitsProcessor, first in the list, on the reference's row order: second + (first - second) * scale
-        const float xn = (lg_neg[v] - mn) - lse_n;
-        x = __fadd_rn(x, __fmul_rn(__fsub_rn(xn, x), p.cfg_scale));
-      }
-      if (ltv >= 0 && v >= sp.ts_start && v < sp.ts_start + ltv) x = -INFINITY;
-      if (sp.timeshift_bias != 0.f && v >= sp.ts_start && v < sp.ts_end) x += sp.timeshift_bias;
-      x = x / temp;
-      if (sp.lookback_mask_end > sp.ts_start && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
-      lg_pos[v] = x + rs;
+  // ---- log_softmax state per beam (both kernels: thread tid reduces columns tid, tid + 512, ... in ascending order, then block_max /
+  // block_sum, so a row's maximum and log-sum-exp have the same bits in both) ------------------------------------------------------
+  if constexpr (kStream) {
+    // all beams in ONE sweep for the maxima and one for the sums: the loads of a column's 2 .. 16 rows are independent
+    float mp[kBeamMaxBeams], mn[kBeamMaxBeams], sp_[kBeamMaxBeams], sn_[kBeamMaxBeams];
+#pragma unroll
+    for (int j = 0; j < kBeamMaxBeams; ++j) { mp[j] = mn[j] = -INFINITY; sp_[j] = sn_[j] = 0.f; }
+    for (int v = tid; v < V; v += kBeamThreads) {
+#pragma unroll
+      for (int j = 0; j < kBeamMaxBeams; ++j)
+        if (j < nb) { mp[j] = fmaxf(mp[j], lg_pos_g[(long)j * V + v]); if (p.cfg) mn[j] = fmaxf(mn[j], lg_neg_g[(long)j * V + v]); }
     }
+#pragma unroll
+    for (int j = 0; j < kBeamMaxBeams; ++j)
+      if (j < nb) { mp[j] = block_max(mp[j], red); if (p.cfg) mn[j] = block_max(mn[j], red); }
+    for (int v = tid; v < V; v += kBeamThreads) {
+#pragma unroll
+      for (int j = 0; j < kBeamMaxBeams; ++j)
+        if (j < nb) { sp_[j] += expf(lg_pos_g[(long)j * V + v] - mp[j]); if (p.cfg) sn_[j] += expf(lg_neg_g[(long)j * V + v] - mn[j]); }
+    }
+#pragma unroll
+    for (int j = 0; j < kBeamMaxBeams; ++j)
+      if (j < nb) {
+        sp_[j] = block_sum(sp_[j], red);
+        if (p.cfg) sn_[j] = block_sum(sn_[j], red);
+        if (tid == 0) { s_row[j].mp = mp[j]; s_row[j].lse_p = logf(sp_[j]); s_row[j].mn = mn[j]; s_row[j].lse_n = p.cfg ? logf(sn_[j]) : 0.f; }
+      }
+    __syncthreads();
+  } else {
+    // ---- log_softmax (+ guidance) + processors + running score -> val[] ------------------------------------------------------
+    // the prompt rows' logits are staged in LDS once (one round of independent loads); the per-beam maximum / sum then read LDS in
+    // the same thread -> column order as before, so the reductions keep their bits
+    for (int i = tid; i < n; i += kBeamThreads) val[i] = lg_pos_g[i];
+    __syncthreads();
+    for (int j = 0; j < nb; ++j) {
+      float* lg_pos = val + j * V;
+      const float* lg_neg = lg_neg_g + (long)j * V;
+      float mp = -INFINITY, mn = -INFINITY;
+      for (int v = tid; v < V; v += kBeamThreads) { mp = fmaxf(mp, lg_pos[v]); if (p.cfg) mn = fmaxf(mn, lg_neg[v]); }
+      mp = block_max(mp, red);
+      if (p.cfg) mn = block_max(mn, red);
+      float sp_ = 0.f, sn_ = 0.f;
+      for (int v = tid; v < V; v += kBeamThreads) { sp_ += expf(lg_pos[v] - mp); if (p.cfg) sn_ += expf(lg_neg[v] - mn); }
+      sp_ = block_sum(sp_, red);
+      if (p.cfg) sn_ = block_sum(sn_, red);
+      const BeamRow b{mp, logf(sp_), mn, p.cfg ? logf(sn_) : 0.f, s_row[j].temp, s_row[j].rs, s_row[j].ltv};
+      for (int v = tid; v < V; v += kBeamThreads)       // (each thread rewrites exactly the columns it read)
+        lg_pos[v] = beam_score(p, b, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   // ---- the K best of the chunk's num_beams x V accumulated scores, best first, ties by ascending flat index ----------------------
   // (1) radix select of the K-th largest value on the order-preserving integer image of the floats, 8 bits per pass
@@ -174,10 +262,11 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
     __syncthreads();
     const unsigned prefix = s_prefix;
     const int rem = s_remaining;
-    for (int i = tid; i < n; i += kBeamThreads) {
-      const unsigned u = beam_okey(val[i]);
-      if ((u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & 255], 1);
-    }
+    for (int j = 0; j < nb; ++j)
+      beam_sweep(scores, j, wid * 64, kBeamThreads, V, [&](int, float x, bool ok) {
+        const unsigned u = beam_okey(x);
+        if (ok && (u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & 255], 1);
+      });
     __syncthreads();
     // thread t owns bin 255 - t: the bin where the count from the top first reaches `rem` holds the K-th value
     const int h = tid < 256 ? s_hist[255 - tid] : 0;
@@ -191,19 +280,50 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
   }
   const unsigned kth = s_prefix;                 // integer image of the K-th largest value; s_remaining of its ties are wanted
   const int want_ties = s_remaining;
-  // (2) compaction: everything above the K-th value, then the `want_ties` ties of SMALLEST flat index (threads own contiguous index
-  //     ranges, so a block-wide exclusive scan of their tie counts ranks the ties in index order)
-  const int chunk = (n + kBeamThreads - 1) / kBeamThreads, i_lo = tid * chunk, i_hi = (i_lo + chunk < n) ? i_lo + chunk : n;
-  int above = 0, ties = 0;
-  for (int i = i_lo; i < i_hi; ++i) { const unsigned u = beam_okey(val[i]); above += u > kth; ties += u == kth; }
-  int n_above, n_ties;
-  int wpos = beam_excl_scan(above, s_w, n_above);            // n_above = K - want_ties
-  int trank = beam_excl_scan(ties, s_w, n_ties);
-  for (int i = i_lo; i < i_hi; ++i) {
-    const float x = val[i];
-    const unsigned u = beam_okey(x);
-    if (u > kth) arr[wpos++] = BeamKV{x, i};
-    else if (u == kth) { if (trank < want_ties) arr[n_above + trank] = BeamKV{x, i}; ++trank; }
+  // (2) compaction: everything above the K-th value, then the `want_ties` ties of SMALLEST flat index.  Wave w owns the columns
+  //     [w Vw, (w + 1) Vw) of every beam and walks them 64 at a time, so (beam, wave) slices are in flat-index order: the slices'
+  //     counts are scanned by one wave, and inside a slice a wave-wide vote ranks the 64 columns of a round.  (Where the values above
+  //     the K-th land among themselves does not matter: the sort below orders them by (value, flat index), a total order.)
+  const int Vw = (((V + kBeamWaves - 1) / kBeamWaves) + 63) & ~63;
+  const int v_lo = min(wid * Vw, V), v_hi = min(v_lo + Vw, V);
+  for (int j = 0; j < nb; ++j) {
+    int above = 0, ties = 0;
+    beam_sweep(scores, j, v_lo, 64, v_hi, [&](int, float x, bool ok) {
+      const unsigned u = beam_okey(x);
+      above += ok && u > kth;
+      ties += ok && u == kth;
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { above += __shfl_xor(above, o, 64); ties += __shfl_xor(ties, o, 64); }
+    if (lane == 0) { s_seg_above[j * kBeamWaves + wid] = above; s_seg_ties[j * kBeamWaves + wid] = ties; }
+  }
+  __syncthreads();
+  if (wid == 0) {      // exclusive scan over the nb x 8 slices (<= 64: one per lane)
+    const bool in = lane < nb * kBeamWaves;
+    const int a = in ? s_seg_above[lane] : 0, t = in ? s_seg_ties[lane] : 0;
+    int ia = a, it = t;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int ya = __shfl_up(ia, o, 64), yt = __shfl_up(it, o, 64);
+      if (lane >= o) { ia += ya; it += yt; }
+    }
+    if (in) { s_seg_above[lane] = ia - a; s_seg_ties[lane] = it - t; }
+  }
+  __syncthreads();
+  const int n_above = K - want_ties;
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  for (int j = 0; j < nb; ++j) {
+    int wpos = s_seg_above[j * kBeamWaves + wid], trank = s_seg_ties[j * kBeamWaves + wid];
+    beam_sweep(scores, j, v_lo, 64, v_hi, [&](int i, float x, bool ok) {
+      const unsigned u = beam_okey(x);
+      const bool is_above = ok && u > kth, is_tie = ok && u == kth;
+      const unsigned long long m_above = __ballot(is_above), m_tie = __ballot(is_tie);
+      const int pa = wpos + __popcll(m_above & lanes_below), pt = trank + __popcll(m_tie & lanes_below);
+      if (is_above && pa < n_above) arr[pa] = BeamKV{x, i};
+      if (is_tie && pt < want_ties) arr[n_above + pt] = BeamKV{x, i};
+      wpos += __popcll(m_above);
+      trank += __popcll(m_tie);
+    });
   }
   for (int i = K + tid; i < k_pad; i += kBeamThreads) arr[i] = BeamKV{-INFINITY, 0x7fffffff};
   __syncthreads();
@@ -359,27 +479,47 @@ extern "C" int64_t mh_beam_step_lds_bytes(int num_beams, int V) {      // the sc
   return (((int64_t)num_beams * V * 4 + 15) & ~(int64_t)15);
 }
 
+// which kernel a step of this shape runs under the option "beam_step_path" (0 = the LDS kernel wherever it fits, else the streaming
+// one; 1 = the LDS kernel or nothing; 2 = the streaming kernel): 0 = refused, 1 = LDS, 2 = streaming
+extern "C" int mh_beam_step_path(int num_beams, int V, int K) {
+  if (num_beams < 2 || num_beams > kBeamMaxBeams || V < 1 || K < num_beams || K > kBeamMaxK || K > (int64_t)num_beams * V) return 0;
+  const long want = option(OPT_BEAM_STEP_PATH);
+  if (want == 2) return 2;
+  int64_t k_pad = 1;
+  while (k_pad < K) k_pad <<= 1;
+  const bool fits = K <= kBeamLdsMaxK && mh_beam_step_lds_bytes(num_beams, V) + k_pad * 8 <= kBeamLdsBytes;
+  return fits ? 1 : want == 1 ? 0 : 2;
+}
+
 extern "C" int mh_beam_step(const MhBeamStep* bs, void* stream) {
   MH_REQUIRE(bs && bs->logits && bs->eos_table && bs->run_in && bs->run_out && bs->rs_in && bs->rs_out && bs->rb_in && bs->rb_out &&
              bs->seq_in && bs->seq_out && bs->bs_in && bs->bs_out && bs->bb_in && bs->bb_out && bs->fin_in && bs->fin_out &&
              bs->heuristic_open && bs->src && bs->last && bs->flags, "mh_beam_step: null argument");
-  MH_REQUIRE(bs->G >= 1 && bs->num_beams >= 2 && bs->num_beams <= 8, "mh_beam_step: %d chunks x %d beams (2 .. 8 beams)", bs->G, bs->num_beams);
-  MH_REQUIRE(bs->K >= bs->num_beams && bs->K <= kBeamMaxK && bs->K <= bs->num_beams * bs->V, "mh_beam_step: K = %d candidates not in [num_beams, %d]", bs->K, kBeamMaxK);
+  MH_REQUIRE(bs->G >= 1 && bs->V >= 1 && bs->num_beams >= 2 && bs->num_beams <= kBeamMaxBeams, "mh_beam_step: %d chunks x %d beams (2 .. %d beams)", bs->G, bs->num_beams, kBeamMaxBeams);
+  MH_REQUIRE(bs->K >= bs->num_beams && bs->K <= kBeamMaxK && bs->K <= (int64_t)bs->num_beams * bs->V, "mh_beam_step: K = %d candidates not in [num_beams, %d]", bs->K, kBeamMaxK);
   MH_REQUIRE(bs->P >= 1 && bs->cur_len >= bs->P && bs->cur_len < bs->max_length, "mh_beam_step: cur_len %d not in [P, max_length)", bs->cur_len);
   MH_REQUIRE(bs->sp.do_sample == 0, "mh_beam_step: greedy beams only (beam-sample draws on the host side)");
   MH_REQUIRE(!(bs->sp.lookback_types_first && bs->sp.lookback_mask_end > bs->sp.ts_start), "mh_beam_step: the types_first lookback renormalisation is not built for beams");
   MH_REQUIRE(bs->sp.tok_flags || bs->sp.n_cond == 0, "mh_beam_step: conditional temperature needs tok_flags");
   MH_REQUIRE(bs->sp.temperature > 0.f && bs->sp.n_sos >= 0 && bs->sp.n_sos <= 16 && bs->sp.n_cond >= 0 && bs->sp.n_cond <= 3, "mh_beam_step: bad sampling parameters");
+  MH_REQUIRE((int64_t)bs->num_beams * bs->V <= 0x7fffffff, "mh_beam_step: num_beams x V = %d x %d exceeds the 31-bit flat index", bs->num_beams, bs->V);
+  const int path = mh_beam_step_path(bs->num_beams, bs->V, bs->K);
+  MH_REQUIRE(path != 0, "mh_beam_step: num_beams x V = %d x %d (+ %d candidates) does not fit the LDS kernel (120 KB of LDS, K <= %d) and beam_step_path = 1 rules the streaming kernel out",
+             bs->num_beams, bs->V, bs->K, kBeamLdsMaxK);
   int64_t k_pad = 1;
   while (k_pad < bs->K) k_pad <<= 1;
-  const int64_t lds = mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8;
-  MH_REQUIRE(lds > 0 && lds <= 120 * 1024, "mh_beam_step: num_beams x V = %d x %d (+ %d candidates) does not fit 120 KB of LDS", bs->num_beams, bs->V, bs->K);
   static PerDeviceOnce attr_set;
   const int arc = attr_set.run([] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) == hipSuccess
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kBeamLdsBytes) == hipSuccess &&
+                   hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kBeamMaxK * 8) == hipSuccess
                ? MH_OK : check_launch("mh_beam_step: LDS attribute");
   });
   if (arc != MH_OK) return arc;
-  hipLaunchKernelGGL(beam_step_kernel, dim3(bs->G), dim3(kBeamThreads), (size_t)lds, (hipStream_t)stream, *bs);
-  return check_launch("beam_step_kernel");
+  if (path == 1) {
+    const int64_t lds = mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8;
+    hipLaunchKernelGGL(beam_step_kernel<false>, dim3(bs->G), dim3(kBeamThreads), (size_t)lds, (hipStream_t)stream, *bs);
+    return check_launch("beam_step_kernel<lds>");
+  }
+  hipLaunchKernelGGL(beam_step_kernel<true>, dim3(bs->G), dim3(kBeamThreads), (size_t)(k_pad * 8), (hipStream_t)stream, *bs);
+  return check_launch("beam_step_kernel<streaming>");
 }
