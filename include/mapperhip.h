@@ -31,6 +31,7 @@ typedef enum MhStatus {
   MH_ERR_ARG = -1,     /* bad argument (shape / alignment / null) */
   MH_ERR_LAUNCH = -2,  /* HIP launch or runtime error */
   MH_ERR_STATE = -3,   /* object used in the wrong state */
+  MH_ERR_DECODE_TAIL_TIMEOUT = -4,   /* a bounded in-kernel wait of the decode step's fused layer tail gave up (decode_fused_tail) */
 } MhStatus;
 
 /* MH_MX8 (ABI 7): OCP MX-fp8 -- e4m3 elements (one byte each) + one E8M0 scale byte per (row, 32 consecutive k); an OPERAND
@@ -83,6 +84,9 @@ int mh_abi_version(void);
  *                                                   (0 = never; bit-identical)
  *   "beam_step_path"     MH_BEAM_STEP_PATH     0    mh_beam_step: 0 = LDS kernel where it fits, else the streaming kernel; 1 = LDS
  *                                                   kernel or an error; 2 = streaming kernel everywhere (bit-identical)
+ *   "decode_fused_tail"  MH_DECODE_FUSED_TAIL  0    decode step: the three GEMVs that close a layer (cross O + residual, norm + wi +
+ *                                                   activation, wo + residual) as one persistent launch with two bounded in-kernel
+ *                                                   hand-offs (bit-identical; 0 = three launches; uncovered shapes run three anyway)
  * (gemm_tile128_min and dit_split3_min_rows are documented next to their definitions in csrc/api.hip: 11 options in all.
  * Round 5 removed the measured-slower variants decode_overlap, decode_fold_oproj, decode_cu_split, decode_self_rows,
  * mx8_waves = 4, dit_s3_fused_ln, the debugging aid gemm_lds_pad, the variant switches attn_flash2, dit_s3_presplit and
@@ -575,6 +579,12 @@ int mh_t5_cross_attn_probe(const MhT5Config* cfg, const MhT5Weights* w, const vo
  * timed one.  buf == NULL (ring 0) switches it off.  mh_t5_decode_chains(B) = row chains mh_t5_generate uses for B. */
 int mh_t5_decode_timing(void* buf, int ring);
 int mh_t5_decode_chains(int B);
+/* The status mh_t5_generate returns for the error word the decode step leaves in its workspace: 0 -> MH_OK, anything else ->
+ * MH_ERR_DECODE_TAIL_TIMEOUT with mh_last_error() set (a hand-off of the fused layer tail waited more than 2 ms and gave up). */
+int mh_t5_decode_tail_status(int err_word);
+/* Fused layer-tail launches enqueued by this process so far (a node of a captured step graph counts once, when it is captured):
+ * a shape that option "decode_fused_tail" = 1 does not cover runs the three launches and leaves this count unchanged. */
+long mh_t5_decode_tail_launches(void);
 int mh_t5_decode_chains_cfg(const MhT5Config* cfg, int B);   /* ABI 8: ... under cfg->options */
 /* ABI 8: instantiated step graphs are kept across mh_t5_generate calls (option "decode_graph_cache", default 1: LRU of 16, a
  * call replays an earlier call's graph iff every address, size, sampling field other than seed / rng_row0, option value and the

@@ -172,6 +172,8 @@ SYMBOLS = {
     "mh_t5_cross_attn_probe": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, I, C.POINTER(C.c_float), VP, I64, VP]),
     "mh_t5_decode_timing": (I, [VP, I]),
     "mh_t5_decode_chains": (I, [I]),
+    "mh_t5_decode_tail_status": (I, [I]),
+    "mh_t5_decode_tail_launches": (C.c_long, []),
     "mh_t5_decode_chains_cfg": (I, [C.POINTER(MhT5Config), I]),
     "mh_t5_step_graph_cache_stats": (I, [C.POINTER(C.c_long), C.POINTER(C.c_long), I]),
     "mh_wall_clock_khz": (I, []),

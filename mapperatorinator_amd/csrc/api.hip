@@ -49,6 +49,7 @@ static OptionSlot g_options[OPT_COUNT] = {
     {"dit_skinny_max_rows", "MH_DIT_SKINNY_MAX_ROWS", 512, false},   // fp32-semantics DiT with at most this many rows (N T: one chunk = 256): the four block GEMMs as one-round-trip 16 x 16 latency kernels with the LayerNorm taken from registers (dit.hip dit_skinny_kernel); 0 = the LDS-tiled GEMMs (different fp32 summation order)
     {"score_block_rows", "MH_SCORE_BLOCK_ROWS", 1024, false},   // mh_t5_score: scored positions per LM-head block (the fp32 logits scratch holds this many rows, whatever B and T); results do not depend on it.  The block's GEMM runs with the tile of the whole [B T, V] problem, so a small block leaves most CUs idle: whole pass at base dims bf16, B 32, T 2560, V 3837: 256 rows 53.9 ms, 512 48.1, 1024 44.7, 2048 43.6, 4096 43.4 (T 512, V 1849: 10.1 / 9.1 / 8.6 / 8.4 / 8.3); 1024 keeps the scratch at 16 MB for most of the gain
     {"beam_step_path", "MH_BEAM_STEP_PATH", 0, false},   // mh_beam_step: 0 = the LDS kernel wherever num_beams x V scores + K <= 4096 candidates fit 120 KB, else the streaming kernel (scores recomputed from the logits in every pass; any V, K <= 8192); 1 = the LDS kernel or an error; 2 = the streaming kernel everywhere (tests and measurements: the two are bit-identical)
+    {"decode_fused_tail", "MH_DECODE_FUSED_TAIL", 0, false},   // decode step: 1 = the three GEMVs that close a layer run as one persistent launch (dec_tail_kernel: two bounded in-kernel hand-offs, next phase's weights requested across them), 0 = three launches; bit-identical; shapes the fused kernel does not cover run the three launches either way
 };
 
 static thread_local const MhOptionSet* tl_option_set = nullptr;

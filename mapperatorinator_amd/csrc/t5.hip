@@ -417,9 +417,12 @@ namespace {
 struct DecState {       // device-resident control block
   int pos;              // index of the token being fed this step
   int n_running;        // rows not yet finished (written by the sampler)
+  int tail_err;         // != 0: a hand-off of dec_tail_kernel gave up (bounded wait); read by the host right after n_running
   int ticket;           // arrival counter of the sampler's workgroups (the last one advances `pos`)
   unsigned rng_row0;    // MhSampling.rng_row0 and .seed of the running call: written by dec_init_kernel and read from here by
   unsigned long long seed;   // the sampler, so that the replayed step graph does not carry them (they change call by call)
+  // dec_tail_kernel's hand-off counters, one 128-byte line per layer parity: zeroed by dec_init_kernel, then only ever added to
+  alignas(128) unsigned tail_cnt[2][32];
 };
 
 struct SampleP {
@@ -487,7 +490,7 @@ __global__ __launch_bounds__(256) void dec_init_kernel(SampleP p, int chain_rows
     p.last_ts_val[b] = v;
     p.finished[b] = 0;
     p.finish_col[b] = p.max_length - 1;
-    if (lb == 0) { p.st->pos = start_pos; p.st->n_running = chain_rows; p.st->ticket = 0; p.st->rng_row0 = p.sp.rng_row0; p.st->seed = p.sp.seed; }
+    if (lb == 0) { p.st->pos = start_pos; p.st->n_running = chain_rows; p.st->tail_err = 0; p.st->tail_cnt[0][0] = 0; p.st->tail_cnt[1][0] = 0; p.st->ticket = 0; p.st->rng_row0 = p.sp.rng_row0; p.st->seed = p.sp.seed; }
   }
   __shared__ int s_off;
   if (threadIdx.x == 0) {
@@ -973,6 +976,72 @@ int skinny_resid(const dec::SkinnyP& p, hipStream_t s) {
 
 constexpr int kMaxChains = 8;
 
+// ---- the three-GEMV tail of a layer as one launch (option decode_fused_tail; dec::dec_tail_kernel) ---------------------
+std::atomic<long> g_tail_launches{0};   // dec_tail_kernel nodes enqueued (captured or launched) by this process: mh_t5_decode_tail_launches
+template <typename T> int gemv_waves(int K) { return K / (4 * (16 / (int)sizeof(T))) > 4 * dec::kGemvCH ? 8 : 4; }   // launch_skinny's rule
+
+// The wave combination (O, wi, wo) the fused kernel is instantiated for at these dims: 1 = (4, 4, 4), 2 = (4, 4, 8), 3 = (8, 8, 8)
+// (fp32 only), 0 = none.  The ONE table tail_covers() and launch_tail_mf() both read.
+template <typename T>
+int tail_wave_combo(int inner, int d, int dff) {
+  const int a = gemv_waves<T>(inner), b = gemv_waves<T>(d), w = gemv_waves<T>(dff);
+  if (a == 4 && b == 4) return w == 4 ? 1 : 2;
+  if (sizeof(T) == 4 && a == 8 && b == 8 && w == 8) return 3;
+  return 0;
+}
+
+// The configurations the fused kernel covers; everything else runs the three launches:
+//   chains of <= 16 rows, in fp32 storage <= 32 rows (the bf16 kernel for two row fragments, MF = 2, needs more than 256
+//   VGPRs and would spill); a wave combination of the table above -- every T5 / Whisper preset in both storage types; the
+//   Whisper family with all of its tail biases present; operand shapes launch_skinny accepts.
+template <typename T>
+bool tail_covers(const MhT5Config* c, int B, bool wh, const float* b_o, const float* b_fc1, const float* b_fc2) {
+  const int kb = 4 * (16 / (int)sizeof(T)), d = c->d_model, inner = c->n_heads * 64, dff = c->d_ff;
+  if (B > (sizeof(T) == 2 ? 16 : 32)) return false;
+  if (inner % (2 * kb) || dff % (2 * kb) || d % kb || d % 4 || d / kb > 8 * dec::kGemvCH) return false;
+  if (wh ? !(b_o && b_fc1 && b_fc2) : (b_o || b_fc1 || b_fc2)) return false;
+  return tail_wave_combo<T>(inner, d, dff) != 0;
+}
+
+template <typename T, int MF, int PROWI, int EPIWI, bool BIAS>
+int launch_tail_mf(const dec::TailP& p, hipStream_t s) {
+  const int combo = tail_wave_combo<T>(p.o.K, p.wi.K, p.wo.K);
+  if constexpr (sizeof(T) == 2 && MF != 1) {
+    set_error("decode: the fused layer tail has no bf16 kernel for chains of more than 16 rows");
+    return MH_ERR_ARG;
+  } else {
+    if (combo == 1) hipLaunchKernelGGL((dec::dec_tail_kernel<T, MF, 4, 4, 4, PROWI, EPIWI, BIAS>), dim3(p.G), dim3(512), 0, s, p);
+    else if (combo == 2) hipLaunchKernelGGL((dec::dec_tail_kernel<T, MF, 4, 4, 8, PROWI, EPIWI, BIAS>), dim3(p.G), dim3(512), 0, s, p);
+    else if (combo == 3 && sizeof(T) == 4) {
+      if constexpr (sizeof(T) == 4) hipLaunchKernelGGL((dec::dec_tail_kernel<T, MF, 8, 8, 8, PROWI, EPIWI, BIAS>), dim3(p.G), dim3(512), 0, s, p);
+    } else {
+      set_error("decode: no fused layer tail for K = (%d, %d, %d) (tail_covers() should have said so)", p.o.K, p.wi.K, p.wo.K);
+      return MH_ERR_ARG;
+    }
+    g_tail_launches.fetch_add(1, std::memory_order_relaxed);
+    return check_launch("dec_tail_kernel");
+  }
+}
+
+// o / wi / wo: the SkinnyP descriptions of the three launches this one replaces; n_chains: chains that may run side by side
+template <typename T, int PROWI, int EPIWI, bool BIAS>
+int launch_tail(dec::TailP p, DecState* st, int layer, int n_chains, hipStream_t s) {
+  p.o.nv = gemv_cols(p.o.N); p.wo.nv = gemv_cols(p.wo.N);
+  p.wi.nv = EPIWI == dec::SK_GEGLU ? 8 : gemv_cols(p.wi.N);
+  const int go = 8 / gemv_waves<T>(p.o.K), gi = 8 / gemv_waves<T>(p.wi.K), gw = 8 / gemv_waves<T>(p.wo.K);
+  const int to = ceil_div(p.o.N, p.o.nv), tw = ceil_div(p.wo.N, p.wo.nv);
+  const int ti = EPIWI == dec::SK_GEGLU ? ceil_div(p.wi.N / 2, 8) : ceil_div(p.wi.N, p.wi.nv);
+  int G = std::max(std::max(ceil_div(to, go), ceil_div(ti, gi)), ceil_div(tw, gw));
+  const int cap = std::max(1, std::min(128, 256 / std::max(1, n_chains)));   // all chains' tails together: <= 256 workgroups
+  p.G = std::min(G, cap);
+  p.cnt = &st->tail_cnt[layer & 1][0];
+  p.err = &st->tail_err;
+  const int khz = mh_wall_clock_khz();
+  p.timeout_ticks = 2LL * (khz > 0 ? khz : 100000);   // 2 ms
+  if (p.o.B <= 16) return launch_tail_mf<T, 1, PROWI, EPIWI, BIAS>(p, s);
+  return launch_tail_mf<T, 2, PROWI, EPIWI, BIAS>(p, s);
+}
+
 struct DecBuffers {
   float* h; void* attn; void* ff; float* logits; int chain;
   void* self_k; void* self_v;  // [n_dec][B][H][tgt][64]
@@ -1131,6 +1200,24 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
     hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
     hp.ln_b = hf ? w->dec_ln2_b[l] : nullptr;
     MH_TRY(launch_cross_q_d<T>(ca, hp, s));
+    if (with_sampler && option(OPT_DECODE_FUSED_TAIL) != 0 &&
+        tail_covers<T>(c, B, wh, wh ? w->dec_co_b[l] : nullptr, wh ? w->dec_fc1_b[l] : nullptr, wh ? w->dec_fc2_b[l] : nullptr)) {
+      // cross O GEMV + residual, norm + wi + activation, wo + residual as ONE launch (the same device code per phase)
+      dec::TailP tp{};
+      tp.o.A = bf.attn; tp.o.lda = inner; tp.o.W = w->dec_co[l]; tp.o.ldw = inner; tp.o.B = B; tp.o.N = d; tp.o.K = inner; tp.o.h = bf.h; tp.o.ldh = d;
+      tp.wi.A = bf.h; tp.wi.lda = d; tp.wi.ln_w = w->dec_ln3[l]; tp.wi.eps = c->eps; tp.wi.W = w->dec_wi[l]; tp.wi.ldw = d; tp.wi.B = B;
+      tp.wi.K = d; tp.wi.out = bf.ff; tp.wi.ldo = dff; tp.wi.N = wh ? dff : 2 * dff;
+      tp.wo.A = bf.ff; tp.wo.lda = dff; tp.wo.W = w->dec_wo[l]; tp.wo.ldw = dff; tp.wo.B = B; tp.wo.N = d; tp.wo.K = dff; tp.wo.h = bf.h; tp.wo.ldh = d;
+      const int n_chains = ceil_div(Bfull, B);
+      if (!wh) {
+        MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GEGLU, false>(tp, bf.st, l, n_chains, s)));
+      } else {
+        tp.o.bias = w->dec_co_b[l]; tp.wi.bias = w->dec_fc1_b[l]; tp.wo.bias = w->dec_fc2_b[l];
+        if (hf) { tp.wi.ln_b = w->dec_ln3_b[l]; MH_TRY((launch_tail<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s))); }
+        else MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s)));
+      }
+      continue;
+    }
     sk = dec::SkinnyP{};
     sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_co[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
     sk.bias = wh ? w->dec_co_b[l] : nullptr;
@@ -1729,11 +1816,12 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
       }
       step += burst;
       if (step < total_steps && !forced) {
-        int running = 1;
-        if (hipMemcpyAsync(&running, &states[ci]->n_running, 4, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
+        int word[2] = {1, 0};   // DecState::n_running, ::tail_err
+        if (hipMemcpyAsync(word, &states[ci]->n_running, 8, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
             hipStreamSynchronize(chain_stream[ci]) != hipSuccess)
           return MH_ERR_LAUNCH;
-        if (running == 0) break;
+        if (word[1] != 0) return MH_ERR_DECODE_TAIL_TIMEOUT;
+        if (word[0] == 0) break;
       }
     }
     return MH_OK;
@@ -1758,10 +1846,11 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
         for (int ci = 0; ci < used; ++ci) {
           if (!alive[ci] || rcs[ci] != MH_OK) continue;
           if (step < total_steps && !forced) {
-            int running = 1;
-            if (hipMemcpyAsync(&running, &states[ci]->n_running, 4, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
+            int word[2] = {1, 0};   // DecState::n_running, ::tail_err
+            if (hipMemcpyAsync(word, &states[ci]->n_running, 8, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
                 hipStreamSynchronize(chain_stream[ci]) != hipSuccess) { rcs[ci] = MH_ERR_LAUNCH; continue; }
-            if (running == 0) alive[ci] = false;
+            if (word[1] != 0) { rcs[ci] = MH_ERR_DECODE_TAIL_TIMEOUT; continue; }
+            if (word[0] == 0) alive[ci] = false;
           }
           any = any || alive[ci];
         }
@@ -1775,7 +1864,8 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
       for (auto& t : th) t.join();
     }
     for (int ci = 0; ci < used; ++ci)
-      if (rcs[ci] != MH_OK) { set_error("mh_t5_generate: graph launch / poll failed on chain %d: %s", ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
+      if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
+      else if (rcs[ci] != MH_OK) { set_error("mh_t5_generate: graph launch / poll failed on chain %d: %s", ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
   }
   // join the chains back into the caller's stream
   for (int ci = 0; ci < used; ++ci) {
@@ -1787,6 +1877,13 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     rc = check_launch("dec_finalize_kernel");
   }
   (void)hipStreamSynchronize(s);   // the graph objects must outlive their launches
+  if (rc == MH_OK && option(OPT_DECODE_FUSED_TAIL) != 0) {   // the chains are idle: their last word on the bounded hand-offs
+    for (int ci = 0; ci < used && rc == MH_OK; ++ci) {
+      int err = 0;
+      if (hipMemcpy(&err, &states[ci]->tail_err, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = check_launch("tail status");
+      else rc = mh_t5_decode_tail_status(err);
+    }
+  }
   for (int ci = 0; ci < kMaxChains; ++ci) {
     if (cached[ci]) { step_graph_release(cached[ci]); continue; }
     if (execs[ci]) (void)hipGraphExecDestroy(execs[ci]);
@@ -1942,6 +2039,18 @@ extern "C" int mh_wall_clock_khz(void) {   // rate of the device wall clock the 
   }
   return khz;
 }
+
+// DecState::tail_err -> status: what mh_t5_generate returns (and mh_last_error() says) for the word the decode step leaves
+extern "C" int mh_t5_decode_tail_status(int err_word) {
+  if (err_word == 0) return MH_OK;
+  mh::set_error("decode: a hand-off of the fused layer tail (option decode_fused_tail) waited longer than 2 ms and gave up (error word %d); "
+                "the tokens of this call are not valid", err_word);
+  return MH_ERR_DECODE_TAIL_TIMEOUT;
+}
+
+// dec_tail_kernel launches enqueued so far (a captured graph node counts once, at capture): lets a caller -- the tests -- tell
+// that option decode_fused_tail = 1 really took the fused path for its shape instead of the silent three-launch fall-back
+extern "C" long mh_t5_decode_tail_launches(void) { return mh::g_tail_launches.load(); }
 
 extern "C" int mh_t5_decode_chains(int B) { return B > 0 ? mh::pick_chains(B) : 0; }
 extern "C" int mh_t5_decode_chains_cfg(const MhT5Config* c, int B) {   // ... under the engine's option set

@@ -28,6 +28,9 @@ LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # demangled-name fragments of the kernels whose loads are issued by inline asm and covered by counted waits
 ASM_LOAD_KERNELS = ("gemm_glds3_kernel", "gemm_s3g_kernel", "gemm_mx8_kernel", "gemm_glds4_kernel", "gemm_glds2s_kernel")
+# kernels whose workgroups wait for each other inside one launch: the residency argument written at the kernel holds
+# only within these per-workgroup limits, so they are checked at build time too
+RESIDENT_KERNELS = {"dec_tail_kernel": dict(lds=36 * 1024, vgpr=256)}
 
 
 def code_objects(lib_path: str):
@@ -120,6 +123,11 @@ def main(argv):
                   f"sgpr {r.get('.sgpr_count', '?'):>3} lds {r.get('.group_segment_fixed_size', '?'):>6} scratch {scratch:>5} spills {spills:>3}  {nm[:150]}")
         if watched and (scratch or spills):
             bad.append(nm)
+        for frag, lim in RESIDENT_KERNELS.items():
+            if frag in nm and (int(r.get(".group_segment_fixed_size", 0)) > lim["lds"] or
+                               int(r.get(".vgpr_count", 0)) + int(r.get(".agpr_count", 0)) > lim["vgpr"]):
+                print(f"!! over the residency limits {lim}: lds {r.get('.group_segment_fixed_size')} vgpr {r.get('.vgpr_count')} agpr {r.get('.agpr_count')}  {nm[:150]}")
+                bad.append(nm)
     print(f"{len(rows)} kernels, {n_checked} with asm-issued loads checked for scratch / spills: {'FAIL ' + str(len(bad)) if bad else 'ok'}"
           + (f" ({n_epi} with epilogue-only spills behind their last MFMA)" if n_epi else ""))
     return 1 if bad else 0

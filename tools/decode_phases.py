@@ -4,7 +4,7 @@ of the library (`make prof`: in-kernel phase stamps, thread 0 of workgroup 0) an
 shader-clock ticks from the kernel's first instruction to every stamp.  The cross-attention kernel is also timed in wall
 clock (mh_t5_decode_timing), which calibrates ticks per microsecond.
 
-  python tools/decode_phases.py [--batch 16] [--chains 1] [--tokens 192]
+  python tools/decode_phases.py [--batch 16] [--chains 1] [--tokens 192] [--fused-tail]
 """
 import argparse
 import ctypes as C
@@ -21,6 +21,12 @@ STAMPS = {
     "gemv": ["loads issued", "products done (this wave)", "all waves done", "stores issued"],
     "self": ["q/k/v projected", "cached keys attended", "partials merged"],
     "cross": ["row normalised", "query projected", "keys streamed", "partials merged"],
+    # dec_tail_kernel (option decode_fused_tail = 1; --fused-tail), in the order the stamps are taken (index = stamp id).  A wave's
+    # loads complete in order, so when the first poll of a hand-off has returned the weight fragments requested before the arrival
+    # are in registers: "first poll back" - "weights requested" is the part of the weight request that overlapped the wait.
+    "tail": [(0, "O phase: stores issued"), (1, "stores drained, wi weights requested"), (7, "hand-off 1: arrived, first poll back"),
+             (2, "hand-off 1 over (acquire + barrier)"), (3, "wi phase: stores issued"), (4, "stores drained, wo weights requested"),
+             (8, "hand-off 2: arrived, first poll back"), (5, "hand-off 2 over (acquire + barrier)"), (6, "wo phase: stores issued")],
 }
 EPI = {0: "STORE", 1: "QKV", 2: "GEGLU(wi)", 3: "RESID(o/co/wo)", 4: "LOGITS"}
 
@@ -30,6 +36,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--chains", type=int, default=1)
     ap.add_argument("--tokens", type=int, default=192)
+    ap.add_argument("--fused-tail", action="store_true", help="option decode_fused_tail = 1: one dec_tail_kernel per layer")
     args = ap.parse_args()
     from mapperatorinator_amd import Tokenizer, _lib
     from mapperatorinator_amd.modeling import MapperatorinatorHIP
@@ -40,6 +47,7 @@ def main():
     lib.mh_debug_phase_stamps.restype = C.c_int
     lib.mh_debug_phase_stamps.argtypes = [C.c_void_p, C.c_int]
     _lib.set_option("decode_chains", args.chains)
+    _lib.set_option("decode_fused_tail", 1 if args.fused_tail else 0)
     dev = torch.device("cuda", 0)
     tok = Tokenizer.benchmark_vocab(src_seq_len=1251)
     dims = T5_PRESETS["base"]
@@ -93,11 +101,13 @@ def main():
             name, labels = "self-attention + q/k/v projection", STAMPS["self"]
         elif kid == 11:
             name, labels = "cross-attention + q projection", STAMPS["cross"]
+        elif kid == 13:
+            name, labels = "fused layer tail (O -> wi -> wo, one launch)", STAMPS["tail"]
         else:
             name, labels = f"kernel {kid}", [f"stamp {i}" for i in range(16)]
         print(f"{name}:")
         prev = 0.0
-        for i, lab in enumerate(labels):
+        for i, lab in (labels if isinstance(labels[0], tuple) else enumerate(labels)):
             n = st[kid, i, 1].item()
             if n == 0:
                 continue
