@@ -721,6 +721,28 @@ int mh_ddpm_sample_loop(const MhDiTConfig* cfg, const MhDiTWeights* w, float* x_
                         const uint8_t* inpaint_mask, const float* inpaint_ref, const MhSliderSet* sliders,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One ddim_sample update (GaussianDiffusion.ddim_sample, gaussian_diffusion.py:563-610; epsilon prediction,
+ * clip_denoised -> clamp(-2,2)).  Arguments and the raw_pred / x0_override protocol as mh_ddpm_step; the learned-variance
+ * channels 2..3 of model_out are not read.
+ *   coef fp32[6] for this step: {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, sqrt(alpha_bar_prev), sigma,
+ *   sqrt(1 - alpha_bar_prev - sigma^2), nonzero_mask}, the last four computed on the host with the reference's own fp32
+ *   tensor operations (:593-605) from the fp32-extracted alphas_cumprod / alphas_cumprod_prev and eta.
+ *   x0 = sqrt_recip * x - sqrt_recipm1 * eps_model (:371-376) | in-paint, clamp | eps = (sqrt_recip * x - x0) / sqrt_recipm1
+ *   (:378-382, re-derived from the processed x0) | x_out = x0 * coef[2] + coef[4] * eps + coef[5] * coef[3] * noise. */
+int mh_ddim_step(const float* model_out, const float* x, const float* noise, const float* coef,
+                 const uint8_t* inpaint_mask, const float* inpaint_ref, const float* x0_override,
+                 int raw_pred, int N, int T, float* x_out, float* pred_xstart, void* stream);
+
+/* Whole ddim_sample_loop on device (gaussian_diffusion.py:653-735): mh_ddpm_sample_loop with mh_ddim_step as the update --
+ * the same arguments, the same captured graph (denoiser, step, counter; with sliders: eps -> x0, mh_slider_project, the
+ * update) replayed n_steps times on the caller's non-default stream, the same workspace (mh_ddpm_loop_workspace_bytes).
+ *   coefs fp32 [n_steps][6] as above; noise fp32 [n_steps][N,2,T] is read at every step, eta = 0 included (sigma = 0). */
+int mh_ddim_sample_loop(const MhDiTConfig* cfg, const MhDiTWeights* w, float* x_io, const float* c,
+                        const float* y, float cfg_scale, int band, int open_from, int N, int T, int n_steps,
+                        const int32_t* t_map, const float* coefs, const float* noise,
+                        const uint8_t* inpaint_mask, const float* inpaint_ref, const MhSliderSet* sliders,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,9 @@ SYMBOLS = {
     "mh_ddpm_sample_loop": (I, [C.POINTER(MhDiTConfig), C.POINTER(MhDiTWeights), VP, VP, VP, F, I, I, I, I, I,
                                 VP, VP, VP, VP, VP, C.POINTER(MhSliderSet), VP, I64, VP]),
     "mh_slider_project": (I, [VP, VP, VP, I, I, C.POINTER(MhSliderSet), VP]),
+    "mh_ddim_step": (I, [VP, VP, VP, VP, VP, VP, VP, I, I, I, VP, VP, VP]),
+    "mh_ddim_sample_loop": (I, [C.POINTER(MhDiTConfig), C.POINTER(MhDiTWeights), VP, VP, VP, F, I, I, I, I, I,
+                                VP, VP, VP, VP, VP, C.POINTER(MhSliderSet), VP, I64, VP]),
 }
 
 _lib = None

@@ -170,6 +170,37 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict_
   x_out[idx] = smp;
   if (pred) pred[idx] = x0;
 }
+
+// One DDIM update (GaussianDiffusion.ddim_sample, gaussian_diffusion.py:563-610), same conventions as ddpm_step_kernel.
+// coef row = (sqrt_recip, sqrt_recipm1, sqrt(abar_prev), sigma, sqrt(1 - abar_prev - sigma^2), nonzero).  The learned-variance
+// channels 2..3 of model_out are not read.  eps is re-derived from the processed x0 (in-paint, clamp), as the reference does.
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ model_out,
+                                                       const float* __restrict__ x, const float* __restrict__ noise,
+                                                       const float* __restrict__ coef, const int* __restrict__ sel,
+                                                       long noise_stride, const uint8_t* __restrict__ imask,
+                                                       const float* __restrict__ iref,
+                                                       const float* __restrict__ x0_override, int raw_pred, int N,
+                                                       int T, float* __restrict__ x_out, float* __restrict__ pred) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= N * 2 * T) return;
+  const int si = sel ? *sel : 0;
+  const float* cf = coef + (long)si * 6;
+  const float* nz = noise + (long)si * noise_stride;
+  const int n = idx / (2 * T), rem = idx - n * 2 * T, ch = rem / T, tp = rem - ch * T;
+  const float xt = x[idx];
+  const float srx = cf[0] * xt;
+  float x0 = x0_override ? x0_override[idx] : srx - cf[1] * model_out[((long)n * 4 + ch) * T + tp];
+  if (raw_pred) {  // only report the eps -> x0 prediction (caller applies its own denoised_fn)
+    if (pred) pred[idx] = x0;
+    return;
+  }
+  if (imask) x0 = imask[idx] ? x0 : iref[idx];
+  x0 = fminf(fmaxf(x0, -2.0f), 2.0f);
+  const float eps = (srx - x0) / cf[1];
+  const float mean = x0 * cf[2] + cf[4] * eps;
+  x_out[idx] = mean + (cf[5] * cf[3]) * nz[idx];
+  if (pred) pred[idx] = x0;
+}
 #pragma clang fp contract(fast)
 
 // y = silu(x), elementwise (input of every adaLN projection: nn.Sequential(SiLU, Linear), models.py:124-127)
@@ -804,6 +835,14 @@ int ddpm_step(const float* model_out, const float* x, const float* noise, const 
   return check_launch("ddpm_step_kernel");
 }
 
+int ddim_step(const float* model_out, const float* x, const float* noise, const float* coef, const int* sel,
+              long noise_stride, const uint8_t* imask, const float* iref, const float* x0_override, int raw_pred, int N,
+              int T, float* x_out, float* pred, hipStream_t s) {
+  hipLaunchKernelGGL(ddim_step_kernel, dim3(ceil_div(N * 2 * T, 256)), dim3(256), 0, s, model_out, x, noise, coef, sel,
+                     noise_stride, imask, iref, x0_override, raw_pred, N, T, x_out, pred);
+  return check_launch("ddim_step_kernel");
+}
+
 }  // namespace
 }  // namespace mh
 
@@ -850,20 +889,24 @@ extern "C" int mh_ddpm_step(const float* model_out, const float* x, const float*
                    pred_xstart, (hipStream_t)stream);
 }
 
-extern "C" int mh_ddpm_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, float* x_io, const float* cc,
-                                   const float* y, float cfg_scale, int band, int open_from, int N, int T, int n_steps,
-                                   const int32_t* t_map, const float* coefs, const float* noise,
-                                   const uint8_t* inpaint_mask, const float* inpaint_ref, const MhSliderSet* sliders,
-                                   void* workspace, int64_t workspace_bytes, void* stream) {
+namespace {
+// the two samplers' step launchers share one signature; the loop below differs between them in nothing else
+using StepFn = int (*)(const float*, const float*, const float*, const float*, const int*, long, const uint8_t*,
+                       const float*, const float*, int, int, int, float*, float*, hipStream_t);
+
+int sample_loop(const char* name, StepFn step, const MhDiTConfig* c, const MhDiTWeights* w, float* x_io, const float* cc,
+                const float* y, float cfg_scale, int band, int open_from, int N, int T, int n_steps, const int32_t* t_map,
+                const float* coefs, const float* noise, const uint8_t* inpaint_mask, const float* inpaint_ref,
+                const MhSliderSet* sliders, void* workspace, int64_t workspace_bytes, void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   MH_TRY(check_dit(c, N, T));
   MH_REQUIRE(w && x_io && cc && y && t_map && coefs && noise && workspace && n_steps > 0,
-             "mh_ddpm_sample_loop: null argument");
+             "%s: null argument", name);
   if (sliders) MH_TRY(check_slider_set(sliders, N));
-  MH_REQUIRE(open_from >= 0 && open_from <= T, "mh_ddpm_sample_loop: open_from outside [0, T]");
-  MH_REQUIRE(stream != nullptr, "mh_ddpm_sample_loop: needs a non-default stream (hipGraph capture)");
-  MH_REQUIRE(workspace_bytes >= mh_ddpm_loop_workspace_bytes(c, N, T, n_steps), "mh_ddpm_sample_loop: workspace too small");
-  MH_REQUIRE((inpaint_mask == nullptr) == (inpaint_ref == nullptr), "mh_ddpm_sample_loop: inpaint mask/ref mismatch");
+  MH_REQUIRE(open_from >= 0 && open_from <= T, "%s: open_from outside [0, T]", name);
+  MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", name);
+  MH_REQUIRE(workspace_bytes >= mh_ddpm_loop_workspace_bytes(c, N, T, n_steps), "%s: workspace too small", name);
+  MH_REQUIRE((inpaint_mask == nullptr) == (inpaint_ref == nullptr), "%s: inpaint mask/ref mismatch", name);
   hipStream_t s = (hipStream_t)stream;
   DiTBuf b;
   const int64_t used = dit_ws_layout(c, N, T, workspace, workspace_bytes, &b);
@@ -887,13 +930,13 @@ extern "C" int mh_ddpm_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, 
   int rc = check_launch("select_step_kernel");
   if (rc == MH_OK) rc = dit_body(c, w, x_io, cc, cfg_scale, band, open_from, N, T, mout, b, s);
   if (rc == MH_OK && !sliders)
-    rc = ddpm_step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, inpaint_mask, inpaint_ref, nullptr, 0, N, T, x_io,
+    rc = step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, inpaint_mask, inpaint_ref, nullptr, 0, N, T, x_io,
                    nullptr, s);
-  if (rc == MH_OK && sliders) {   // eps -> x0 | in-paint + slider ends | clamp, posterior mean, noise
-    rc = ddpm_step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, nullptr, nullptr, nullptr, 1, N, T, x_io, x0buf, s);
+  if (rc == MH_OK && sliders) {   // eps -> x0 | in-paint + slider ends | clamp, the sampler's mean, noise
+    rc = step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, nullptr, nullptr, nullptr, 1, N, T, x_io, x0buf, s);
     if (rc == MH_OK) rc = slider_project(x0buf, inpaint_mask, inpaint_ref, N, T, *sliders, s);
     if (rc == MH_OK)
-      rc = ddpm_step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, nullptr, nullptr, x0buf, 0, N, T, x_io, nullptr, s);
+      rc = step(mout, x_io, noise, coefs, b.sel, (long)N * 2 * T, nullptr, nullptr, x0buf, 0, N, T, x_io, nullptr, s);
   }
   if (rc == MH_OK) {
     hipLaunchKernelGGL(loop_dec_kernel, dim3(1), dim3(64), 0, s, b.sel);
@@ -901,7 +944,7 @@ extern "C" int mh_ddpm_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, 
   }
   hipError_t ce = hipStreamEndCapture(s, &graph);
   if (rc != MH_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  if (ce != hipSuccess || !graph) { set_error("mh_ddpm_sample_loop: capture failed: %s", hipGetErrorString(ce)); return MH_ERR_LAUNCH; }
+  if (ce != hipSuccess || !graph) { set_error("%s: capture failed: %s", name, hipGetErrorString(ce)); return MH_ERR_LAUNCH; }
   if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
     (void)hipGraphDestroy(graph);
     return check_launch("graph instantiate");
@@ -913,4 +956,33 @@ extern "C" int mh_ddpm_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, 
   (void)hipGraphExecDestroy(exec);
   (void)hipGraphDestroy(graph);
   return rc2;
+}
+}  // namespace
+
+extern "C" int mh_ddpm_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, float* x_io, const float* cc,
+                                   const float* y, float cfg_scale, int band, int open_from, int N, int T, int n_steps,
+                                   const int32_t* t_map, const float* coefs, const float* noise,
+                                   const uint8_t* inpaint_mask, const float* inpaint_ref, const MhSliderSet* sliders,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+  return sample_loop("mh_ddpm_sample_loop", ddpm_step, c, w, x_io, cc, y, cfg_scale, band, open_from, N, T, n_steps, t_map,
+                     coefs, noise, inpaint_mask, inpaint_ref, sliders, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mh_ddim_step(const float* model_out, const float* x, const float* noise, const float* coef,
+                            const uint8_t* inpaint_mask, const float* inpaint_ref, const float* x0_override,
+                            int raw_pred, int N, int T, float* x_out, float* pred_xstart, void* stream) {
+  MH_REQUIRE(model_out && x && noise && coef && x_out && N > 0 && T > 0, "mh_ddim_step: bad argument");
+  MH_REQUIRE((inpaint_mask == nullptr) == (inpaint_ref == nullptr), "mh_ddim_step: inpaint mask/ref must come together");
+  MH_REQUIRE(!raw_pred || pred_xstart, "mh_ddim_step: raw_pred needs pred_xstart");
+  return ddim_step(model_out, x, noise, coef, nullptr, 0, inpaint_mask, inpaint_ref, x0_override, raw_pred, N, T, x_out,
+                   pred_xstart, (hipStream_t)stream);
+}
+
+extern "C" int mh_ddim_sample_loop(const MhDiTConfig* c, const MhDiTWeights* w, float* x_io, const float* cc,
+                                   const float* y, float cfg_scale, int band, int open_from, int N, int T, int n_steps,
+                                   const int32_t* t_map, const float* coefs, const float* noise,
+                                   const uint8_t* inpaint_mask, const float* inpaint_ref, const MhSliderSet* sliders,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+  return sample_loop("mh_ddim_sample_loop", ddim_step, c, w, x_io, cc, y, cfg_scale, band, open_from, N, T, n_steps, t_map,
+                     coefs, noise, inpaint_mask, inpaint_ref, sliders, workspace, workspace_bytes, stream);
 }

@@ -429,7 +429,8 @@ class DiffusionPipelineHIP:
                  seq_len: int = 128, max_seq_len: int = 1024, overlap_buffer: int = 128, cfg_scale: float = 1.0,
                  refine_model: Optional[DiTHIP] = None, refine_iters: int = 10, random_init: bool = False,
                  pad_sequence: bool = False, start_time: Optional[float] = None, end_time: Optional[float] = None,
-                 tokenizer=None, types_first: bool = False, has_sv: bool = True):
+                 tokenizer=None, types_first: bool = False, has_sv: bool = True, sampler: str = "ddpm",
+                 ddim_eta: float = 0.0):
         # pad_sequence (reference diffusion_pipeline.py:186-193) pads every window to max_seq_len with zero positions and zero
         # context, pads the band mask with "allowed" and builds a key_padding_mask -- which DiTBlock.forward never hands to
         # its attention (models.py:133-150): every real query then attends all the pad tokens, so padding CHANGES the real
@@ -437,6 +438,13 @@ class DiffusionPipelineHIP:
         # BandMask(open_from=) / the attention kernels' `open_from`.
         if not 0 <= 2 * overlap_buffer < max_seq_len:
             raise ValueError("overlap_buffer must be less than half of max_seq_len")
+        # sampler: "ddpm" = the reference pipeline's ancestral loop; "ddim" = `ddim_sample_loop` over the same respacing
+        # (gaussian_diffusion.py:653-735; e.g. timesteps="ddim25"), ddim_eta its eta.  The refine iterations stay `p_sample`.
+        if sampler not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', got {sampler!r}")
+        if not ddim_eta >= 0:
+            raise ValueError(f"ddim_eta must be >= 0, got {ddim_eta}")
+        self.sampler, self.ddim_eta = sampler, float(ddim_eta)
         self.model, self.refine_model = model, refine_model
         self.device = model.device
         self.timesteps, self.diffusion_steps, self.noise_schedule = timesteps, diffusion_steps, noise_schedule
@@ -571,9 +579,15 @@ class DiffusionPipelineHIP:
             z_part = denoised_fn(z_part)
             model_kwargs = dict(c=c_part, y=y, cfg_scale=self.cfg_scale,
                                 attn_mask=BandMask(T, self.seq_len, open_from=real if pad > 0 else 0), key_padding_mask=None)
-            samples = diffusion.p_sample_loop(self.model.forward_with_cfg, z_part.shape, z_part, denoised_fn=denoised_fn,
-                                              clip_denoised=True, model_kwargs=model_kwargs, device=dev,
-                                              step_noise=noise_source(diffusion.num_timesteps, tuple(z_part.shape)))
+            step_noise = noise_source(diffusion.num_timesteps, tuple(z_part.shape))
+            if self.sampler == "ddim":
+                samples = diffusion.ddim_sample_loop(self.model.forward_with_cfg, z_part.shape, z_part, denoised_fn=denoised_fn,
+                                                     clip_denoised=True, model_kwargs=model_kwargs, device=dev,
+                                                     eta=self.ddim_eta, step_noise=step_noise)
+            else:
+                samples = diffusion.p_sample_loop(self.model.forward_with_cfg, z_part.shape, z_part, denoised_fn=denoised_fn,
+                                                  clip_denoised=True, model_kwargs=model_kwargs, device=dev,
+                                                  step_noise=step_noise)
             if self.refine_model is not None:
                 # the reference refines with `self.model.forward_with_cfg` (:261), not the refine model: kept as is
                 for _ in range(self.refine_iters):

@@ -421,6 +421,7 @@ class SpacedDiffusionHIP:
         self.num_timesteps = len(b)
         ac = np.cumprod(1.0 - b)
         ac_prev = np.append(1.0, ac[:-1])
+        self.alphas_cumprod, self.alphas_cumprod_prev = ac, ac_prev
         self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / ac)
         self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / ac - 1)
         pv = b * (1.0 - ac_prev) / (1.0 - ac)
@@ -436,6 +437,22 @@ class SpacedDiffusionHIP:
                         (np.arange(n) != 0).astype(np.float64)], axis=1)
         return torch.from_numpy(tab).float()  # float64 -> .float(), as _extract_into_tensor does
 
+    def ddim_coef_table(self, eta: float = 0.0) -> torch.Tensor:
+        """fp32 [n_steps, 6] rows = (sqrt_recip, sqrt_recipm1, sqrt(abar_prev), sigma, sqrt(1 - abar_prev - sigma^2), nonzero):
+        what `ddim_sample` multiplies by (gaussian_diffusion.py:593-609).  alphas_cumprod / alphas_cumprod_prev are extracted
+        float64 -> .float() as _extract_into_tensor does, then sigma and the two square roots are the reference's own fp32
+        tensor operations in its order.  Row 0: abar_prev = 1, so sigma = 0 and the direction term is 0 (the last step
+        returns x0)."""
+        if not eta >= 0:
+            raise ValueError(f"ddim: eta must be >= 0, got {eta}")
+        alpha_bar = torch.from_numpy(self.alphas_cumprod).float()
+        alpha_bar_prev = torch.from_numpy(self.alphas_cumprod_prev).float()
+        sigma = eta * torch.sqrt((1 - alpha_bar_prev) / (1 - alpha_bar)) * torch.sqrt(1 - alpha_bar / alpha_bar_prev)
+        nonzero = (torch.arange(self.num_timesteps) != 0).float()
+        return torch.stack([torch.from_numpy(self.sqrt_recip_alphas_cumprod).float(),
+                            torch.from_numpy(self.sqrt_recipm1_alphas_cumprod).float(),
+                            torch.sqrt(alpha_bar_prev), sigma, torch.sqrt(1 - alpha_bar_prev - sigma ** 2), nonzero], dim=1)
+
     @torch.no_grad()
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn: Optional[Callable] = None,
                       cond_fn=None, model_kwargs=None, device=None, progress=False, step_noise=None):
@@ -443,11 +460,26 @@ class SpacedDiffusionHIP:
         DiTHIP).  `step_noise` (optional, [n_steps, *shape], index = call order) injects the per-step
         gaussian noise for parity tests; otherwise `torch.randn_like` is called once per step on the
         device, consuming the global generator exactly as the reference loop does."""
+        return self._sample_loop("ddpm", "p_sample_loop", self.coef_table, model, shape, noise, clip_denoised, denoised_fn,
+                                 cond_fn, model_kwargs, step_noise)
+
+    @torch.no_grad()
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn: Optional[Callable] = None,
+                         cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None):
+        """Signature of GaussianDiffusion.ddim_sample_loop (gaussian_diffusion.py:653-735) plus `step_noise` as in
+        `p_sample_loop`.  The reference draws `randn_like(x)` on every step even at eta = 0 (:601), so does this."""
+        return self._sample_loop("ddim", "ddim_sample_loop", lambda: self.ddim_coef_table(eta), model, shape, noise,
+                                 clip_denoised, denoised_fn, cond_fn, model_kwargs, step_noise)
+
+    def _sample_loop(self, kind, who, coef_table, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+                     step_noise):
+        """the loop of either sampler: `kind` names the library's update (mh_<kind>_step / mh_<kind>_sample_loop)"""
         dit = getattr(model, "__self__", model)
         if not isinstance(dit, DiTHIP):
-            raise TypeError("p_sample_loop: model must be DiTHIP.forward_with_cfg")
+            raise TypeError(f"{who}: model must be DiTHIP.forward_with_cfg")
         if cond_fn is not None or not clip_denoised:
             raise NotImplementedError("cond_fn / clip_denoised=False are not used by the pipeline and not built")
+        coefs = coef_table()
         mk = dict(model_kwargs or {})
         dev = dit.device
         x = (noise if noise is not None else torch.randn(*shape, device=dev)).to(dev, torch.float32).contiguous().clone()
@@ -461,10 +493,11 @@ class SpacedDiffusionHIP:
             step_noise = torch.stack([torch.randn_like(x) for _ in range(n)])
         step_noise = step_noise.to(dev, torch.float32)
         noise_by_i = torch.flip(step_noise, dims=[0]).contiguous()  # call k handles loop index i = n-1-k
-        coefs = self.coef_table().to(dev).contiguous()
+        coefs = coefs.to(dev).contiguous()
         t_map = torch.tensor(self.timestep_map, dtype=torch.int32, device=dev)
         lib, s = dit.lib, None
         ws = dit.workspace(N, T, n)
+        loop, step = getattr(lib, f"mh_{kind}_sample_loop"), getattr(lib, f"mh_{kind}_step")
 
         if denoised_fn is None or isinstance(denoised_fn, InpaintSpec):
             imask = iref = sset = None
@@ -474,11 +507,11 @@ class SpacedDiffusionHIP:
             if isinstance(denoised_fn, SliderInpaintSpec):
                 sset = C.byref(denoised_fn.cset)
             with dit.on_own_stream() as own:
-                rc = lib.mh_ddpm_sample_loop(C.byref(dit.cfg), C.byref(dit.w), x.data_ptr(), c.data_ptr(),
-                                             y.data_ptr(), cfg_scale, band, open_from, N, T, n, t_map.data_ptr(),
-                                             coefs.data_ptr(), noise_by_i.data_ptr(), _lib.ptr(imask), _lib.ptr(iref),
-                                             sset, ws.data_ptr(), ws.numel(), own)
-            _lib.check(rc, "mh_ddpm_sample_loop")
+                rc = loop(C.byref(dit.cfg), C.byref(dit.w), x.data_ptr(), c.data_ptr(),
+                          y.data_ptr(), cfg_scale, band, open_from, N, T, n, t_map.data_ptr(),
+                          coefs.data_ptr(), noise_by_i.data_ptr(), _lib.ptr(imask), _lib.ptr(iref),
+                          sset, ws.data_ptr(), ws.numel(), own)
+            _lib.check(rc, f"mh_{kind}_sample_loop")
             return x
 
         # arbitrary host denoised_fn (slider re-projection): per-step launches, x0 round trip through python
@@ -490,13 +523,12 @@ class SpacedDiffusionHIP:
             _lib.check(lib.mh_dit_forward_cfg(C.byref(dit.cfg), C.byref(dit.w), x.data_ptr(), t32.data_ptr(),
                                               c.data_ptr(), y.data_ptr(), cfg_scale, band, open_from, N, T, mout.data_ptr(),
                                               ws.data_ptr(), ws.numel(), s), "mh_dit_forward_cfg")
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise_by_i[i].data_ptr(), coefs[i].data_ptr(),
-                                        None, None, None, 1, N, T, x.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise_by_i[i].data_ptr(), coefs[i].data_ptr(),
+                            None, None, None, 1, N, T, x.data_ptr(), x0.data_ptr(), s), f"mh_{kind}_step")
             x0n = denoised_fn(x0.clone()).to(dev, torch.float32).contiguous()
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise_by_i[i].data_ptr(), coefs[i].data_ptr(),
-                                        None, None, x0n.data_ptr(), 0, N, T, x.data_ptr(), None, s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise_by_i[i].data_ptr(), coefs[i].data_ptr(),
+                            None, None, x0n.data_ptr(), 0, N, T, x.data_ptr(), None, s), f"mh_{kind}_step")
         return x
-
 
     @torch.no_grad()
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn: Optional[Callable] = None, cond_fn=None,
@@ -505,52 +537,67 @@ class SpacedDiffusionHIP:
         SPACED loop index of every batch row (all equal), mapped through `timestep_map` like _WrappedModel does
         (respace.py:127-132).  `noise` injects the gaussian draw (default: torch.randn_like on the device -- drawn
         even when t == 0, where it is multiplied by 0, as in the reference).  Returns sample / pred_xstart."""
+        return self._sample_step("ddpm", "p_sample", self.coef_table, model, x, t, clip_denoised, denoised_fn, cond_fn,
+                                 model_kwargs, noise)
+
+    @torch.no_grad()
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn: Optional[Callable] = None, cond_fn=None,
+                    model_kwargs=None, eta=0.0, noise=None):
+        """One DDIM step, signature of GaussianDiffusion.ddim_sample (gaussian_diffusion.py:563-610) plus `noise` as in
+        `p_sample`; `t` as there.  The gaussian draw is made at eta = 0 too (:601).  Returns sample / pred_xstart."""
+        return self._sample_step("ddim", "ddim_sample", lambda: self.ddim_coef_table(eta), model, x, t, clip_denoised,
+                                 denoised_fn, cond_fn, model_kwargs, noise)
+
+    def _sample_step(self, kind, who, coef_table, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, noise):
+        """one step of either sampler (`kind` as in _sample_loop)"""
         dit = getattr(model, "__self__", model)
         if not isinstance(dit, DiTHIP):
-            raise TypeError("p_sample: model must be DiTHIP.forward_with_cfg")
+            raise TypeError(f"{who}: model must be DiTHIP.forward_with_cfg")
         if cond_fn is not None or not clip_denoised:
             raise NotImplementedError("cond_fn / clip_denoised=False are not used by the pipeline and not built")
+        coefs = coef_table()
         mk = dict(model_kwargs or {})
         dev = dit.device
         x = x.to(dev, torch.float32).contiguous()
         N, _, T = x.shape
         ti = t.to("cpu").tolist()
         if len(set(ti)) != 1:
-            raise NotImplementedError("p_sample: one loop index per call")
+            raise NotImplementedError(f"{who}: one loop index per call")
         i = int(ti[0])
         c = mk["c"].to(dev, torch.float32).contiguous()
         y = mk["y"].to(dev, torch.float32).contiguous()
         band, open_from = dit.band_from_mask(mk.get("attn_mask"), T)
         noise = (torch.randn_like(x) if noise is None else noise.to(dev, torch.float32)).contiguous()
-        coef = self.coef_table()[i].to(dev).contiguous()
+        coef = coefs[i].to(dev).contiguous()
         t32 = torch.full((N,), self.timestep_map[i], dtype=torch.int32, device=dev)
         mout = torch.empty((N, 4, T), dtype=torch.float32, device=dev)
         out, x0 = torch.empty_like(x), torch.empty_like(x)
         ws = dit.workspace(N, T)
         s = dit.caller_stream()
         lib = dit.lib
+        step, name = getattr(lib, f"mh_{kind}_step"), f"mh_{kind}_step"
         _lib.check(lib.mh_dit_forward_cfg(C.byref(dit.cfg), C.byref(dit.w), x.data_ptr(), t32.data_ptr(), c.data_ptr(),
                                           y.data_ptr(), float(mk.get("cfg_scale", 1.0)), band, open_from, N, T, mout.data_ptr(),
                                           ws.data_ptr(), ws.numel(), s), "mh_dit_forward_cfg")
-        if isinstance(denoised_fn, SliderInpaintSpec):     # eps -> x0 | in-paint + slider ends | posterior, all on the device
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
-                                        None, 1, N, T, out.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+        if isinstance(denoised_fn, SliderInpaintSpec):     # eps -> x0 | in-paint + slider ends | the update, all on the device
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
+                            None, 1, N, T, out.data_ptr(), x0.data_ptr(), s), name)
             denoised_fn.project_(x0, s)
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
-                                        x0.data_ptr(), 0, N, T, out.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
+                            x0.data_ptr(), 0, N, T, out.data_ptr(), x0.data_ptr(), s), name)
         elif denoised_fn is None or isinstance(denoised_fn, InpaintSpec):
             imask = iref = None
             if denoised_fn is not None:
                 imask = denoised_fn.mask.to(dev).to(torch.uint8).contiguous()
                 iref = denoised_fn.ref.to(dev, torch.float32).contiguous()
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), _lib.ptr(imask),
-                                        _lib.ptr(iref), None, 0, N, T, out.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), _lib.ptr(imask),
+                            _lib.ptr(iref), None, 0, N, T, out.data_ptr(), x0.data_ptr(), s), name)
         else:
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
-                                        None, 1, N, T, out.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
+                            None, 1, N, T, out.data_ptr(), x0.data_ptr(), s), name)
             x0n = denoised_fn(x0.clone()).to(dev, torch.float32).contiguous()
-            _lib.check(lib.mh_ddpm_step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
-                                        x0n.data_ptr(), 0, N, T, out.data_ptr(), x0.data_ptr(), s), "mh_ddpm_step")
+            _lib.check(step(mout.data_ptr(), x.data_ptr(), noise.data_ptr(), coef.data_ptr(), None, None,
+                            x0n.data_ptr(), 0, N, T, out.data_ptr(), x0.data_ptr(), s), name)
         return {"sample": out, "pred_xstart": x0}
 
 
