@@ -520,6 +520,15 @@ int mh_beam_step_path(int num_beams, int V, int K);
 int mh_t5_step(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B, int kv_group, const int32_t* ids,
                int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace, int64_t workspace_bytes,
                void* stream);
+/* mh_t5_step over the e4m3 copy of the cross K/V (additive at ABI 11: one symbol, no struct changes layout).  `cross_kv_fp8` = the
+ * packed copy mh_t5_quantize_cross_kv made of `cross_kv` (mh_t5_cross_kv_fp8_bytes(cfg, B / kv_group) bytes: it holds the same
+ * B / kv_group rows); every cross-attention of the step streams it instead of `cross_kv`, row b with the scales of K/V row
+ * b / kv_group.  Every other argument, the workspace and the logits are mh_t5_step's; the two entries may be mixed over one workspace
+ * (the self-attention caches do not depend on the copy).  bf16 storage only (fp32: MH_ERR_ARG), every arch.  Not a parity mode: the
+ * logits are those of K/V rounded to e4m3 with one fp32 scale per (layer, k|v, row, head). */
+int mh_t5_step_fp8(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B, int kv_group,
+                   const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
+                   int64_t workspace_bytes, void* stream);
 int64_t mh_t5_reorder_cache_scratch_bytes(const MhT5Config* cfg, int B, int n_pos);
 int mh_t5_reorder_cache(const MhT5Config* cfg, int B, const int32_t* src, int n_pos, void* workspace, int64_t workspace_bytes,
                         void* scratch, int64_t scratch_bytes, void* stream);

@@ -14,7 +14,7 @@ vectorised `GenerationMixin._beam_search` -- transformers >= 4.50; line referenc
     stop when no running beam can still beat the worst finished one (early_stopping = False heuristic)
 
 The device side is the step-wise entry of the library (`mh_t5_step`: one decoder position for all (chunk, beam) rows, raw
-logits out; `mh_t5_reorder_cache`).  Round 6: for greedy beams the WHOLE bookkeeping above is one kernel per token, `mh_beam_step`
+logits out -- `mh_t5_step_fp8` when the search is handed the e4m3 copy of the cross K/V, `kv_fp8`; `mh_t5_reorder_cache`).  Round 6: for greedy beams the WHOLE bookkeeping above is one kernel per token, `mh_beam_step`
 (csrc/beam.hip: log_softmax, guidance, processors, top-K over beams x V by a radix select + a sort of the K, EOS split, next-beam
 selection, finished-set merge, the early-stopping heuristic; 2 .. 8 beams, K <= 8192, any vocabulary: the scores live in LDS where
 they fit 120 KB, else a streaming kernel recomputes them from the logits, same bits) -- `_beam_search_kernel` below; the host reads three flags per chunk and step.  The torch-op
@@ -50,6 +50,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .t5_engine import require_bf16_for_cross_kv_fp8
 
 
 def _gather(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -125,8 +126,36 @@ def kernel_path_available(sp, num_beams: int, vocab_out: int, n_eos: int) -> boo
     return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), int(K)) != 0
 
 
+def _step_kv_fp8(engine, cross_kv: torch.Tensor, kv_fp8):
+    """The packed e4m3 copy the steps stream, or None.  `cross_kv` is the tensor the steps are handed -- under guidance the rows
+    already doubled: a copy of the undoubled rows is made again, so that the packed layout stays [data | scales] of ONE tensor."""
+    if kv_fp8 is None or kv_fp8 is False:
+        return None
+    require_bf16_for_cross_kv_fp8(engine.dtype)
+    want = int(engine.lib.mh_t5_cross_kv_fp8_bytes(C.byref(engine.packed.cfg), cross_kv.shape[2]))
+    if kv_fp8 is True or kv_fp8.numel() != want:
+        engine._enter()                                  # (the engine's stream waits for the concatenation above)
+        with torch.cuda.stream(engine.stream):
+            kv_fp8 = engine.cross_kv_fp8(cross_kv.contiguous())
+        engine._leave()
+    return kv_fp8
+
+
+def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P, logits, ws, stream):
+    """One decoder position for all (chunk, beam) rows: mh_t5_step, or mh_t5_step_fp8 over the e4m3 copy when there is one."""
+    if kv_fp8 is None:
+        rc = lib.mh_t5_step(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), rows, kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P,
+                            logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        _lib.check(rc, "mh_t5_step")
+    else:
+        rc = lib.mh_t5_step_fp8(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), kv_fp8.data_ptr(), rows, kv_group, tokens.data_ptr(),
+                                pos, _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        _lib.check(rc, "mh_t5_step_fp8")
+
+
 @torch.no_grad()
-def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping) -> torch.Tensor:
+def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
+                        kv_fp8=None) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
     D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs."""
     dev, lib, p = engine.device, engine.lib, engine.packed
@@ -140,6 +169,7 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
         neg_mask = None if prompt_mask is None else prompt_mask[:half]
         prompt_mask = None if prompt_mask is None else prompt_mask[half:]
         cross_kv = torch.cat([cross_kv, cross_kv], dim=2)
+    kv_fp8 = _step_kv_fp8(engine, cross_kv, kv_fp8)
     G, P = prompt.shape
     nb = int(num_beams)
     R = G * nb
@@ -203,9 +233,7 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     bs.heuristic_open, bs.src, bs.last, bs.flags = heuristic_open.data_ptr(), src.data_ptr(), feed.data_ptr(), flags.data_ptr()
 
     def step(tokens: torch.Tensor, pos: int):
-        rc = lib.mh_t5_step(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), RE, nb, tokens.data_ptr(), pos, _lib.ptr(mask), P,
-                            logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(rc, "mh_t5_step")
+        _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
 
     engine._enter()
     with torch.cuda.stream(engine.stream):
@@ -247,20 +275,23 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
 @torch.no_grad()
 def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids, sp,
                 num_beams: int, length_penalty: float = 1.0, early_stopping=False, sample_fn=None,
-                use_kernel: Optional[bool] = None) -> torch.Tensor:
+                use_kernel: Optional[bool] = None, kv_fp8=None) -> torch.Tensor:
     """cross_kv: the G chunks' cross K/V (engine.cross_kv); prompt int (G, P) left-padded, prompt_mask (G, P) or None.
     Under guidance (sp.cfg_scale > 1) `prompt` / `prompt_mask` carry 2G rows, [negative-prompt rows | prompt rows] (what
     T5Engine.generate and the scheduler build), and cross_kv still has G rows.
     Returns int64 (G, P + new) on the engine's device: the best hypothesis per chunk, shorter ones filled the way HF does
     (`pad_token_id or eos_token_id[0]`: with pad id 0 that is the FIRST EOS id).
     `use_kernel`: None = mh_beam_step whenever it covers the call (greedy beams, 2 .. 8 of them, K <= 8192: kernel_path_available), False = the torch-op
-    bookkeeping below, True = the kernel or an error."""
+    bookkeeping below, True = the kernel or an error.
+    `kv_fp8`: the packed e4m3 copy of `cross_kv` (engine.cross_kv_fp8(cross_kv)), or True to have it made here: every step streams
+    the copy (mh_t5_step_fp8) instead of `cross_kv`.  bf16 storage only."""
     can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(list(eos_ids))) and sample_fn is None
     if use_kernel is True and not can:
         raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
                                   "K = max(2, 1 + #eos) x beams > 8192)")
     if can and use_kernel is not False:
-        return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping)
+        return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
+                                   kv_fp8=kv_fp8)
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = None
@@ -272,6 +303,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
         neg_mask = None if prompt_mask is None else prompt_mask[:half]
         prompt_mask = None if prompt_mask is None else prompt_mask[half:]
         cross_kv = torch.cat([cross_kv, cross_kv], dim=2)          # [layer][k|v][chunk][H][L][64]: the negative rows read their chunk's K / V
+    kv_fp8 = _step_kv_fp8(engine, cross_kv, kv_fp8)
     G, P = prompt.shape
     nb = int(num_beams)
     R = G * nb                                                     # rows the beam bookkeeping ranks
@@ -321,10 +353,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     scale = float(sp.cfg_scale)
 
     def step(tokens: torch.Tensor, pos: int):
-        t32 = tokens.to(torch.int32).contiguous()
-        rc = lib.mh_t5_step(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), RE, nb, t32.data_ptr(), pos, _lib.ptr(mask), P,
-                            logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(rc, "mh_t5_step")
+        _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens.to(torch.int32).contiguous(), pos, mask, P, logits, ws, stream)
 
     engine._enter()
     with torch.cuda.stream(engine.stream):

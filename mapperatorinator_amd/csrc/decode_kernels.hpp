@@ -142,8 +142,7 @@ __device__ inline void store_piece_wt(TO* dst, const float* v, int n, int nvalid
 // One wave holds the 64 values of a head row (lane = feature): through a wave-private 64-float LDS patch (one wave's LDS
 // operations execute in order: no barrier) to 16-byte pieces, written by the first 8 (bf16) / 16 (fp32) lanes.
 template <typename T>
-__device__ inline void store_head_row_wt(T* dst, float val, float* patch) {
-  const int lane = threadIdx.x & 63;
+__device__ inline void store_head_row_wt(T* dst, float val, float* patch, int lane) {
   constexpr int N = 16 / (int)sizeof(T);
   patch[lane] = val;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -156,6 +155,8 @@ __device__ inline void store_head_row_wt(T* dst, float val, float* patch) {
     store_piece_wt<T>(dst + lane * N, v, N, N);
   }
 }
+template <typename T>
+__device__ inline void store_head_row_wt(T* dst, float val, float* patch) { store_head_row_wt<T>(dst, val, patch, threadIdx.x & 63); }
 // the same from 64 floats that already sit in LDS (visible to the calling wave): lanes `lane0 .. lane0 + 64 / N` of the block
 template <typename T>
 __device__ inline void store_head_row_from_lds_wt(T* dst, const float* src, int t) {   // t = thread index relative to the first storing thread
@@ -1194,8 +1195,12 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
   float m, l, a;
   block_merge<T, NW>(st, sm, m, l, a);
   MH_STAMP(KID_CROSS, 3);   // partials merged
-  if (threadIdx.x < 64)
-    store_head_row_wt<T>(reinterpret_cast<T*>(p.out) + (long)b * p.ldo + h * 64, l > 0.f ? a / l * vs : 0.f, &sm[0][0]);
+  if (threadIdx.x < 64) {
+    // (threadIdx.x < 64: the thread index IS the lane.  The e4m3 Whisper instantiations say so: the d = 768 one sits at the 64-register
+    // limit and would otherwise keep threadIdx.x & 63 of the prologue alive in scratch for this one use)
+    const int lane_st = (F8 && WH) ? (int)threadIdx.x : (int)(threadIdx.x & 63);
+    store_head_row_wt<T>(reinterpret_cast<T*>(p.out) + (long)b * p.ldo + h * 64, l > 0.f ? a / l * vs : 0.f, &sm[0][0], lane_st);
+  }
   if (p.tstamp && threadIdx.x == 0 && *p.pos < p.ts_ring) {      // the first ts_ring positions of the call, one slot each
     unsigned long long* slot = p.tstamp + 2 * ((long)(*p.pos) * p.ts_layers + p.ts_layer);
     atomicMin(slot, t_start);

@@ -1110,8 +1110,12 @@ int launch_cross_q(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStrea
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d, "decode: dense residual rows / projection weights expected");
   // one key in flight per 8-lane group: 64 VGPRs without spills (two 16-wave workgroups per CU); U = 2 measured the
   // same bandwidth
-  if (ca.scale != 0.f) {   // the Whisper family: biased Wq, scaled scores
-    MH_REQUIRE(ca.kscale == nullptr, "decode: the fp8 cross K/V copy is not wired for the Whisper family");
+  if (ca.scale != 0.f && ca.kscale != nullptr) {   // the Whisper family over the e4m3 copy (the scale folds into the key scale)
+    if constexpr (sizeof(T) == 2) {
+      if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+      else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    } else { set_error("decode: the fp8 cross K/V copy needs bf16 storage"); return MH_ERR_ARG; }
+  } else if (ca.scale != 0.f) {   // the Whisper family: biased Wq, scaled scores
     if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
     else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
   } else if (ca.kscale != nullptr) {
@@ -1187,7 +1191,6 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
     ca.out = bf.attn; ca.ldo = inner; ca.B = B; ca.H = H; ca.L = L; ca.kv_B = kv_group > 1 ? -kv_group : (kvB < Bfull ? kvB : 0);
     if (wh) { ca.q_bias = w->dec_cq_b[l]; ca.scale = c->attn_scale; }
     if (kv8) {
-      MH_REQUIRE(!wh, "decode: the fp8 cross K/V copy is not wired for the Whisper family");
       const long slab = (long)kvB * H * L * 64;
       ca.k = (const char*)kv8 + (long)(l * 2 + 0) * slab; ca.v = (const char*)kv8 + (long)(l * 2 + 1) * slab;
       ca.kscale = kv8_scales + (long)(l * 2 + 0) * kvB * H; ca.vscale = kv8_scales + (long)(l * 2 + 1) * kvB * H;
@@ -2135,6 +2138,35 @@ extern "C" int mh_t5_step(const MhT5Config* c, const MhT5Weights* w, const void*
   const int kvB = B / kv_group;
   return c->dtype == MH_BF16 ? enqueue_step<bf16_t>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, smp, s, nullptr, nullptr, false, kv_group)
                              : enqueue_step<float>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, smp, s, nullptr, nullptr, false, kv_group);
+}
+
+// mh_t5_step with the packed e4m3 copy of cross_kv (mh_t5_quantize_cross_kv over its B / kv_group rows) as one more argument: every
+// cross-attention of the step streams the copy, its scales indexed by the K/V row a decode row reads.  bf16 storage only.
+extern "C" int mh_t5_step_fp8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
+                              int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_step_fp8"));
+  MH_TRY(check_decode_shape(c, "mh_t5_step_fp8"));
+  MH_REQUIRE(w && cross_kv && cross_kv_fp8 && ids && logits && workspace, "mh_t5_step_fp8: null argument");
+  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_step_fp8: the fp8 cross K/V copy needs bf16 storage");
+  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step_fp8: batch %d not in [1, 64]", B);
+  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_step_fp8: %d rows are not whole groups of %d", B, kv_group);
+  MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "mh_t5_step_fp8: position %d outside the cache (tgt_len %d)", pos, c->tgt_len);
+  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step_fp8: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  DecBuffers bf = decode_layout(c, B, workspace).bf;
+  bf.logits = logits;
+  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "mh_t5_step_fp8: arch 2 needs decoder.embed_positions and the LayerNorm biases");
+  const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
+  const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
+  hipLaunchKernelGGL(step_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, s, ids, (const bf16_t*)w->dec_embed, c->d_model, bf.h, bf.st, pos, dpos, pmask, P);
+  MH_TRY(check_launch("step_embed_kernel"));
+  const int kvB = B / kv_group;
+  // packed copy: data, then (256-byte aligned) the scales [layer][k|v][kvB][H]
+  const int64_t data_bytes = (int64_t)c->n_dec_layers * 2 * kvB * c->n_heads * c->src_len * 64;
+  const float* scales = reinterpret_cast<const float*>((const char*)cross_kv_fp8 + align256(data_bytes));
+  return enqueue_step<bf16_t>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, SampleP{}, s, cross_kv_fp8, scales, false, kv_group);
 }
 
 // self-attention cache rows of every layer: row b <- row src[b] for positions 0 .. n_pos-1 (`cache.reorder_cache(beam_idx)`).

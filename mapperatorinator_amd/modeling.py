@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .conditioning import ConditioningEmbedders
-from .t5_engine import T5Dims, T5Engine, T5_PRESETS
+from .t5_engine import T5Dims, T5Engine, T5_PRESETS, require_bf16_for_cross_kv_fp8
 from .whisper_engine import VARWHISPER_PRESETS, VarWhisperDims, VarWhisperEngine
 
 
@@ -407,17 +407,18 @@ class MapperatorinatorHIP:
         if sp.cfg_scale > 1.0 and negative_prompt is None:
             raise ValueError("guidance needs negative_prompt (modeling_mapperatorinator.py:243-254)")
         row_bias = None if enc_states is not None else self._row_bias(decoder_input_ids.shape[0], unused)   # (the conditioning acts in the encoder)
+        kv_fp8 = bool(unused.get("cross_kv_fp8", False))
+        if kv_fp8:
+            require_bf16_for_cross_kv_fp8(self.dtype)
         if num_beams != 1:
-            if unused.get("cross_kv_fp8"):
-                raise NotImplementedError("cross_kv_fp8 with beam search: the step-wise beam entry streams the bf16 cross K / V")
             out = self.engine.generate_beam(audio, decoder_input_ids, decoder_attention_mask, eos, sp, int(num_beams),
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
-                                            sample_fn=unused.get("beam_sample_fn"),
+                                            sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=kv_fp8,
                                             **({} if row_bias is None else dict(row_bias=row_bias)))
             return out["tokens"].to(self.device)
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,
                                    negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
-                                   negative_mask=negative_prompt_attention_mask, cross_kv_fp8=bool(unused.get("cross_kv_fp8", False)),
+                                   negative_mask=negative_prompt_attention_mask, cross_kv_fp8=kv_fp8,
                                    encoder_states=enc_states,
                                    **({} if row_bias is None else dict(row_bias=row_bias)))
         return out["tokens"].to(self.device)

@@ -200,10 +200,9 @@ class SequentialWindowScheduler:
             kv = torch.stack([kvs[i][:, :, w] for i, _, _ in group], 2).contiguous()   # rows of this wave, gathered
             p_all = torch.cat([neg, prompts], 0) if cfg else prompts
             m_all = None if masks is None else (torch.cat([masks, masks], 0) if cfg else masks)
-            # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V
-            if gk.get("cross_kv_fp8") and nb > 1:
-                raise NotImplementedError("cross_kv_fp8 with beam search: the step-wise beam entry streams the bf16 cross K / V")
-            kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") else None
+            # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search
+            # makes it itself: with guidance it is a copy of the doubled rows)
+            kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") and nb == 1 else None
             if nb == 1:
                 tokens, n_out, _ = eng.decode(kv, p_all.to(dev, torch.int32).contiguous(),
                                               None if m_all is None else m_all.to(dev).contiguous(),
@@ -214,7 +213,8 @@ class SequentialWindowScheduler:
             # hypotheses are ranked among themselves only, so a window decodes as in the reference's batch-1 call; rows that
             # end early carry HF's fill (the first EOS id) and are cut at their first EOS-set id below like any other row
             from .beam import beam_search
-            result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn")).to(torch.int64).cpu()
+            result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn"),
+                                 kv_fp8=True if gk.get("cross_kv_fp8") else None).to(torch.int64).cpu()
         else:
             eng.synchronize()
             n_cols = int(n_out.item())

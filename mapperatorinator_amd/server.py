@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .event import ContextType
+from .t5_engine import require_bf16_for_cross_kv_fp8
 
 MILISECONDS_PER_SECOND = 1000
 MILISECONDS_PER_STEP = 10
@@ -332,18 +333,19 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
         # then fails on the shape mismatch; its own caller only passes one when cfg_scale > 1 (processor.py:1171)
         neg = neg_mask = None
 
+    kv_fp8 = bool(generate_kwargs.get("cross_kv_fp8", False))
+    if kv_fp8:
+        require_bf16_for_cross_kv_fp8(model.dtype)
     start = time.perf_counter()
     extra = {} if row_bias is None else dict(row_bias=row_bias)
     if getattr(sp, "num_beams", 1) > 1:
         # HF beam search (processor.py:159 `num_beams`; the timing generator uses two beams): mapperatorinator_amd/beam.py
-        if generate_kwargs.get("cross_kv_fp8"):
-            raise NotImplementedError("cross_kv_fp8 with beam search: the step-wise beam entry streams the bf16 cross K / V")
         out = model.engine.generate_beam(audio, prompt, mask, eos, sp, sp.num_beams, negative_prompt=neg,
                                          sample_fn=generate_kwargs.get("beam_sample_fn"),
-                                         use_kernel=generate_kwargs.get("beam_use_kernel"), **extra)
+                                         use_kernel=generate_kwargs.get("beam_use_kernel"), cross_kv_fp8=kv_fp8, **extra)
     else:
         out = model.engine.generate(audio, prompt, mask, eos, sp, negative_prompt=neg, negative_mask=neg_mask,
-                                    cross_kv_fp8=bool(generate_kwargs.get("cross_kv_fp8", False)), **extra)
+                                    cross_kv_fp8=kv_fp8, **extra)
     elapsed = time.perf_counter() - start
     result = out["tokens"]
     stats = _build_generation_stats(result, model_kwargs, pad_token_id, elapsed)

@@ -194,6 +194,14 @@ class PackedT5:
         return sum(t.numel() * t.element_size() for t in self._keep)
 
 
+def require_bf16_for_cross_kv_fp8(dtype) -> None:
+    """`cross_kv_fp8` on a model that does not store bf16: refused on the host, before anything is encoded (the copy is made of
+    bf16 rows, and the fp32 cross-attention kernel has no e4m3 form)."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"cross_kv_fp8 needs bf16 storage (this model stores {dtype}): the e4m3 copy of the cross-attention K / V "
+                         "is made of bf16 rows")
+
+
 def next_token_targets(ids: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Targets of next-token scoring: targets[b, t] = ids[b, t + 1]; the last column and every position whose TARGET column
     is masked out (left padding) are -1 = not scored.  int32, on the device of `ids`."""
@@ -338,10 +346,10 @@ class T5Engine:
 
     def cross_kv_fp8(self, kv: torch.Tensor) -> torch.Tensor:
         """The packed OCP e4m3 copy of `cross_kv(enc)` (one byte per element + one fp32 scale per (layer, k|v, row,
-        head)) that the token steps stream when `MhSampling.cross_kv_fp8` points at it: half the HBM bytes of the
-        dominant decode kernel (BASELINE configs[4]).  bf16 storage only; not a parity mode."""
-        if self.dtype != torch.bfloat16:
-            raise ValueError("the fp8 cross K/V copy needs bf16 storage")
+        head)) that the token steps stream when `MhSampling.cross_kv_fp8` points at it (greedy / sampled decode) or when it is
+        handed to `mh_t5_step_fp8` (beam search): half the HBM bytes of the dominant decode kernel (BASELINE configs[4]).
+        Every backbone (T5 and the Whisper families); bf16 storage only; not a parity mode."""
+        require_bf16_for_cross_kv_fp8(self.dtype)
         p = self.packed
         B = kv.shape[2]
         out = torch.empty(self.lib.mh_t5_cross_kv_fp8_bytes(C.byref(p.cfg), B), dtype=torch.uint8, device=self.device)
@@ -438,12 +446,16 @@ class T5Engine:
     def generate_beam(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids,
                       sampling: _lib.MhSampling, num_beams: int, row_bias: Optional[torch.Tensor] = None,
                       length_penalty: float = 1.0, early_stopping=False, negative_prompt: Optional[torch.Tensor] = None,
-                      sample_fn=None, use_kernel: Optional[bool] = None):
+                      sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False):
         """mel -> encoder -> cross K/V, then HF-style beam search over the step-wise decode entry (beam.py).  Returns
         dict(tokens=int64 CPU (B, n_cols), n_cols, logits=None) like `generate`.  `negative_prompt` with sampling.cfg_scale > 1:
         classifier-free guidance under beams (the doubled batch of modeling_mapperatorinator.py:243-254; beam.py).  With
-        `sampling.do_sample` the continuations are drawn (beam-sample): `sample_fn(probs, k)` or torch.multinomial on the device."""
+        `sampling.do_sample` the continuations are drawn (beam-sample): `sample_fn(probs, k)` or torch.multinomial on the device.
+        `cross_kv_fp8`: every step streams the e4m3 copy of the cross-attention K / V (see `cross_kv_fp8()`; under guidance the copy
+        is made of the doubled rows)."""
         from .beam import beam_search
+        if cross_kv_fp8:
+            require_bf16_for_cross_kv_fp8(self.dtype)
         audio = audio.to(self.device, torch.float32)
         if (negative_prompt is not None) != (sampling.cfg_scale > 1.0):
             raise ValueError("negative_prompt and sampling.cfg_scale > 1 go together")
@@ -461,7 +473,7 @@ class T5Engine:
             kv = self.cross_kv(self.encode_mel(self.mel(audio), row_bias=row_bias))
         self._leave()
         out = beam_search(self, kv, prompt, prompt_mask, eos_ids, sampling, num_beams, length_penalty, early_stopping,
-                          sample_fn=sample_fn, use_kernel=use_kernel)
+                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None)
         return dict(tokens=out.cpu(), n_cols=int(out.shape[1]), logits=None)
 
     def generate(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
@@ -477,6 +489,8 @@ class T5Engine:
         prepare_inputs_for_generation does it (modeling_mapperatorinator.py:243-254): the first half carries the
         negative prompt over the first columns of the prompt; the returned rows are the prompt rows."""
         dev = self.device
+        if cross_kv_fp8:
+            require_bf16_for_cross_kv_fp8(self.dtype)
         if encoder_states is None:
             audio = audio.to(dev, torch.float32)
         else:
