@@ -467,6 +467,38 @@ int mh_t5_generate(const MhT5Config* cfg, const MhT5Weights* w, const void* cros
                    const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
                    void* stream);
 
+/* e4m3 self-attention K/V cache for the token steps ("self_kv_fp8"; additive at ABI 11: symbols only, no struct changes layout; a
+ * library without them is an older 11).  The other half of an fp8 K/V cache beside MhSampling.cross_kv_fp8; opt-in, not a parity mode.
+ * Contract:
+ *   - bf16 storage only (fp32: MH_ERR_ARG; the hosts refuse it before anything is encoded).
+ *   - every cached self-attention key row and value row (64 elements of one layer, row, head, position) is held as 64 OCP e4m3 bytes
+ *     plus one fp32 scale: scale = absmax / 448 (1 when the row is all zero), element = cvt_e4m3(x * (1 / scale)) -- the reciprocal-
+ *     multiply form of mh_t5_quantize_cross_kv.
+ *   - a token step at position `pos` attends the e4m3 rows of positions < pos (dequantised by their scales: the key scale multiplies
+ *     the score before bias and mask, the value scale the probability), attends its OWN new key / value at storage precision as
+ *     mh_t5_generate does, then appends that row in e4m3 with its scale.  The bf16 row is still written to the bf16 cache of the
+ *     workspace, which stays valid for everything that reads it.
+ *   - the batched prompt prefill is unchanged: positions 0 .. P-2 attend each other through the bf16 cache and are quantised in one
+ *     pass before the first token step.  Under option decode_prefill = 0 every prompt position is a token step and behaves as the
+ *     previous item says (so a prompt row attends its predecessors in e4m3 there).
+ *   - rows stay batch-invariant: a row's logits do not depend on which rows share its call or its chain.
+ * mh_t5_self_kv_fp8_bytes: bytes of the caller-owned shadow cache -- e4m3 [n_dec][2][B][H][tgt_len][64] followed, 256-byte aligned,
+ *   by fp32 scales [n_dec][2][B][H][tgt_len] (0.53 x the bf16 cache, on top of it); -1 for fp32 storage.
+ * mh_t5_generate_skv8: mh_t5_generate's arguments plus the shadow.  Composes with MhSampling.cross_kv_fp8, guidance (the doubled rows
+ *   own their cache rows), sampling, forced ids and logits_dump.  The shadow need not be initialised and is rewritten by every call.
+ * mh_quantize_kv_rows: the bulk quantiser on plain buffers -- x_bf16 [n_rows][64] bf16 -> q [n_rows][64] e4m3 bytes, scales [n_rows].
+ * mh_t5_decode_self_cache: the bf16 self-attention caches [n_dec][B][H][tgt_len][64] inside a decode workspace of B rows.
+ * Not built here: mh_t5_step / mh_t5_step_fp8 / mh_t5_reorder_cache (beam search) have no shadow-cache form -- they take no shadow
+ *   argument and always run over the bf16 cache; the hosts refuse self_kv_fp8 with num_beams > 1. */
+int64_t mh_t5_self_kv_fp8_bytes(const MhT5Config* cfg, int B);
+int mh_t5_generate_skv8(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B,
+                        const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                        const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                        const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                        void* stream, void* self_kv_fp8);
+int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, float* scales, void* stream);
+int mh_t5_decode_self_cache(const MhT5Config* cfg, int B, void* workspace, void** k, void** v);
+
 /* (ABI 10) One beam-search step between two decoder positions as ONE kernel (csrc/beam.hip).  Replaces the per-step body of HF
  * `GenerationMixin._beam_search` (third-party, transformers >= 4.50's vectorised form) as the reference reaches it with
  * `num_beams > 1` (osuT5/osuT5/inference/processor.py:147,159; server.py:137; super_timing_generator.py:28 decodes with two beams):

@@ -158,6 +158,11 @@ SYMBOLS = {
     "mh_t5_quantize_cross_kv": (I, [C.POINTER(MhT5Config), VP, I, VP, VP]),
     "mh_t5_generate": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP,
                            C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP]),
+    "mh_t5_self_kv_fp8_bytes": (I64, [C.POINTER(MhT5Config), I]),
+    "mh_t5_generate_skv8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP,
+                                C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP, VP]),
+    "mh_quantize_kv_rows": (I, [VP, I64, VP, VP, VP]),
+    "mh_t5_decode_self_cache": (I, [C.POINTER(MhT5Config), I, VP, C.POINTER(VP), C.POINTER(VP)]),
     "mh_t5_step": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, I, VP, I, VP, I, VP, VP, I64, VP]),
     "mh_beam_step_lds_bytes": (I64, [I, I]),
     "mh_beam_step": (I, [C.POINTER(MhBeamStep), VP]),

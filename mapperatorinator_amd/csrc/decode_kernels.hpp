@@ -874,10 +874,14 @@ __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key g
   s.m = mw;
 }
 
-template <typename T, int U, typename E = T>
+// SC (the e4m3 self-attention cache): every key row carries its own fp32 scale pair, kscale_row[j] / vscale_row[j], fetched the
+// way the bias is (one value per key per 8-lane group, clamped index, unconditional load); the key scale multiplies the score
+// before bias and mask, the value scale multiplies the probability before the accumulate
+template <typename T, int U, typename E = T, bool SC = false>
 __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kbase, const E* vbase, int j0,
                                    int jend, int jstride, const float* bias_row, int pos, const uint8_t* mask_row,
-                                   int P, float scale, int jmin = 0) {   // keys below jmin are masked (sliding window)
+                                   int P, float scale, int jmin = 0,   // keys below jmin are masked (sliding window)
+                                   const float* kscale_row = nullptr, const float* vscale_row = nullptr) {
   // processes keys j0, j0+jstride, ... < jend for this lane's key group, U at a time
   const int c8 = (threadIdx.x & 7) * 8;
   for (int j = j0; j < jend; j += jstride * U) {
@@ -901,6 +905,13 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
     int mv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) { bv[u] = 0.f; mv[u] = 1; }
+    float ksv[U], vsv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int jj = j + u * jstride;
+      ksv[u] = SC ? kscale_row[jj < jend ? jj : j] : 1.f;
+      vsv[u] = SC ? vscale_row[jj < jend ? jj : j] : 1.f;
+    }
     if (bias_row) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -924,7 +935,8 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
       float d = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) d += q[i] * kv[u][i];
-      d = group_sum<8>(d) * scale + bv[u];
+      if (SC) d = group_sum<8>(d) * ksv[u] * scale + bv[u];
+      else d = group_sum<8>(d) * scale + bv[u];
       const bool ok = (jj < jend) && (jj >= jmin) && (mv[u] != 0);
       d = ok ? d : -INFINITY;
       s[u] = d;
@@ -939,8 +951,9 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
     for (int u = 0; u < U; ++u) {
       const float pu = fexp<T>(s[u] - mn);
       st.l += pu;
+      const float pv = SC ? pu * vsv[u] : pu;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) st.acc[i] += pu * vv[u][i];
+      for (int i = 0; i < 8; ++i) st.acc[i] += pv * vv[u][i];
     }
     st.m = mn;
   }
@@ -960,6 +973,34 @@ struct SelfAttnP {
   // pos - window are not attended (local layers under the flash-attention path, :330)
   const float* qkv_bias; const float* rope; float scale; int window;
 };
+
+// ---- e4m3 shadow of the self-attention cache (mh_t5_generate_skv8) ---------------------------------------------------------
+// One cached key / value row (64 elements of one layer, row, head, position) = 64 OCP e4m3 bytes + one fp32 scale:
+// scale = absmax / 448 (1 for an all-zero row), element = cvt_e4m3(x * (1 / scale)) -- the reciprocal-multiply form of
+// kv_quant_fp8_kernel (t5.hip).  quant_row64 is the ONE statement of it: the token step's append and the bulk pass after the prompt
+// prefill both call it, so the two cannot round differently.  A whole wave: lane i holds element i; lanes 0..15 store four bytes each
+// and lane 0 the scale, with ordinary vector stores (the next launch reads them).
+__device__ inline void quant_row64(float x, uint8_t* q_row, float* scale_slot) {
+  const int lane = threadIdx.x & 63;
+  float mx = fabsf(x);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  const float scale = mx > 0.f ? mx / 448.0f : 1.0f;   // 448 = largest finite e4m3 value
+  const float inv = 1.0f / scale;
+  const float y = x * inv;
+  const int src = (lane & 15) * 4;
+  const float y0 = __shfl(y, src, 64), y1 = __shfl(y, src + 1, 64), y2 = __shfl(y, src + 2, 64), y3 = __shfl(y, src + 3, 64);
+  int o = __builtin_amdgcn_cvt_pk_fp8_f32(y0, y1, 0, false);
+  o = __builtin_amdgcn_cvt_pk_fp8_f32(y2, y3, o, true);
+  if (lane < 16) reinterpret_cast<uint32_t*>(q_row)[lane] = (uint32_t)o;
+  if (lane == 0) *scale_slot = scale;
+}
+// the self-attention kernel's trailing argument: this layer's shadow rows of the chain's first row (F8 instantiations), or nothing
+struct SelfKv8P {
+  uint8_t* k8; uint8_t* v8;      // e4m3 [B][H][tgt_len][64]
+  float* ks; float* vs;          // fp32 scales [B][H][tgt_len]
+};
+struct NoSelfKv8P {};
 
 // merge the NW waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
 template <typename T, int NW = 4>
@@ -1210,11 +1251,16 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
 
 // self-attention of one (b, h) with its own q / k / v projections: appends the new key / value row to the caches and
 // attends over keys 0 .. pos-1 from the cache plus the new key straight from LDS (merged last)
-template <typename T, int KC, bool WH = false, bool LN = false>
+// F8 (bf16 storage only; mh_t5_generate_skv8): keys 0 .. pos-1 come from the e4m3 shadow cache `f8` with their per-row scales (64-byte
+// rows, 8 bytes per lane); the new key / value are attended at storage precision from LDS as ever, written to the bf16 cache as ever
+// (256 bytes per workgroup: the bf16 cache stays valid for everything that reads it) and appended to the shadow by waves 1 / 2
+template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))   // 16 waves = 4 per SIMD: the whole 128-register budget
 void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_, const int* pos_,
                                                                  const void* kc_, const void* vc_, int H_, int d_, SelfAttnP p,
-                                                                 HeadProjP hp) {   // leading scalars: preloaded kernel arguments
+                                                                 HeadProjP hp,   // leading scalars: preloaded kernel arguments
+                                                                 typename std::conditional<F8, SelfKv8P, NoSelfKv8P>::type f8) {
+  static_assert(!F8 || sizeof(T) == 2, "the e4m3 shadow cache is made of bf16 rows");
   hp.h = h_; hp.ln_w = lnw_; hp.W = W_; hp.ldh = d_; hp.ldw = d_; hp.d = d_;
   p.pos = pos_; p.kc = kc_; p.vc = vc_; p.H = H_;
   const int inner = H_ * 64;
@@ -1233,7 +1279,9 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   NormRow<T, LN> nrow;
   nrow.issue(hp, b);
   const int pos = *p.pos;
-  constexpr bool kAllAtOnce = sizeof(T) == 2 && KC <= 7;
+  // (F8, the Whisper family at d = 896: the scale pairs of the key loop on top of the 21 weight vectors spill; one projection at a
+  // time, as d = 1024 -- the same sums in the same order)
+  constexpr bool kAllAtOnce = sizeof(T) == 2 && KC <= ((F8 && WH) ? 6 : 7);
   HeadProj<T, KC, kAllAtOnce ? 3 : 1> proj;
   const int row03[3] = {h * 64, inner + h * 64, 2 * inner + h * 64};
   const float* bias_row = WH ? nullptr : p.bias + (long)h * p.tgt_len;       // (the Whisper family has no additive bias)
@@ -1280,6 +1328,11 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   T* vcache = reinterpret_cast<T*>(const_cast<void*>(p.vc)) + ((long)b * p.H + h) * p.tgt_len * 64;
   store_head_row_from_lds_wt<T>(kcache + (long)pos * 64, qkv[1], (int)threadIdx.x - 64);     // waves 1 / 2: whole 16-byte pieces
   store_head_row_from_lds_wt<T>(vcache + (long)pos * 64, qkv[2], (int)threadIdx.x - 128);
+  if constexpr (F8) {   // waves 1 / 2 own the new k / v rows: append them to the shadow (wave-uniform branch)
+    const long bh = (long)b * p.H + h;
+    if (wid == 1) quant_row64(qkv[1][lane], f8.k8 + (bh * p.tgt_len + pos) * 64, f8.ks + bh * p.tgt_len + pos);
+    if (wid == 2) quant_row64(qkv[2][lane], f8.v8 + (bh * p.tgt_len + pos) * 64, f8.vs + bh * p.tgt_len + pos);
+  }
   float q[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) q[i] = qkv[0][c8 + i];
@@ -1288,8 +1341,16 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   const float sc = WH ? p.scale : 1.0f;
   int j_first = 0;
   if (WH && p.window > 0 && pos - p.window > 0) j_first = (pos - p.window) & ~(8 * NW - 1);   // whole key iterations below the window are skipped
-  attend_keys<T, 2>(st, q, kcache, vcache, j_first + wid * 8 + g, pos, 8 * NW, bias_row, pos, mask_row, p.P, sc,
-                    (WH && p.window > 0) ? pos - p.window : 0);
+  if constexpr (F8) {
+    const long bh = (long)b * p.H + h;
+    attend_keys<T, 2, fp8_t, true>(st, q, reinterpret_cast<const fp8_t*>(f8.k8) + bh * p.tgt_len * 64,
+                                   reinterpret_cast<const fp8_t*>(f8.v8) + bh * p.tgt_len * 64, j_first + wid * 8 + g, pos, 8 * NW,
+                                   bias_row, pos, mask_row, p.P, sc, (WH && p.window > 0) ? pos - p.window : 0,
+                                   f8.ks + bh * p.tgt_len, f8.vs + bh * p.tgt_len);
+  } else {
+    attend_keys<T, 2>(st, q, kcache, vcache, j_first + wid * 8 + g, pos, 8 * NW, bias_row, pos, mask_row, p.P, sc,
+                      (WH && p.window > 0) ? pos - p.window : 0);
+  }
   MH_STAMP(KID_SELF, 1);    // cached keys attended (this wave)
   partial_merge_groups<T>(st);
   float m, l, a;

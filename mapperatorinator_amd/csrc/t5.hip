@@ -1046,6 +1046,10 @@ struct DecBuffers {
   float* h; void* attn; void* ff; float* logits; int chain;
   void* self_k; void* self_v;  // [n_dec][B][H][tgt][64]
   uint8_t* finished; int32_t* finish_col; int32_t* last_ts; DecState* st;
+  // the caller's e4m3 shadow of the self-attention cache (mh_t5_generate_skv8), else NULL: e4m3 [n_dec][2][B][H][tgt][64] and its
+  // fp32 scales [n_dec][2][B][H][tgt].  Non-NULL selects the F8 self-attention kernel (and, being part of this struct, is part of
+  // the step graph's cache key)
+  uint8_t* self8; float* self8_scales;
 };
 
 // The decode workspace of B rows (mh_t5_decode_workspace_bytes): the one description of its slabs, read by mh_t5_generate,
@@ -1081,28 +1085,39 @@ DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
 // (check_decode_shape).
 #define MH_SELF_LEAD_ARGS hp.h, hp.ln_w, hp.W, sa.pos, sa.kc, sa.vc, sa.H, hp.d
 #define MH_CROSS_LEAD_ARGS hp.h, hp.ln_w, hp.W, ca.k, ca.v, ca.H, ca.L, hp.d, ca.kv_B
+// f8 != NULL: the F8 instantiation over this layer's rows of the e4m3 shadow cache (bf16 storage only)
 template <typename T, int KC>
-int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s) {
+int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d && inner == sa.H * 64, "decode: dense residual rows / projection weights expected");
-  if (sa.rope && hp.ln_b)   // HF Whisper (arch 2): the same behind an affine LayerNorm, identity rotary table
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp);
+  const dec::NoSelfKv8P no8{};
+  if (f8) {
+    if constexpr (sizeof(T) == 2) {
+      if (sa.rope && hp.ln_b)
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
+      else if (sa.rope)
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
+      else
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
+    } else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
+  } else if (sa.rope && hp.ln_b)   // HF Whisper (arch 2): the same behind an affine LayerNorm, identity rotary table
+    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
   else if (sa.rope)   // the Whisper family: biased fused Wqkv, RoPE, scaled scores, optional window
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp);
+    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
   else
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp);
+    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
   return check_launch("dec_self_attn_qkv_kernel");
 }
 template <typename T>
-int launch_self_qkv_d(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s) {
+int launch_self_qkv_d(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8 = nullptr) {
   switch (hp.d) {
-    case 128: return launch_self_qkv<T, 1>(sa, hp, inner, s);
-    case 256: return launch_self_qkv<T, 2>(sa, hp, inner, s);
-    case 384: return launch_self_qkv<T, 3>(sa, hp, inner, s);
-    case 512: return launch_self_qkv<T, 4>(sa, hp, inner, s);
-    case 640: return launch_self_qkv<T, 5>(sa, hp, inner, s);
-    case 768: return launch_self_qkv<T, 6>(sa, hp, inner, s);
-    case 896: return launch_self_qkv<T, 7>(sa, hp, inner, s);
-    default: return launch_self_qkv<T, 8>(sa, hp, inner, s);
+    case 128: return launch_self_qkv<T, 1>(sa, hp, inner, s, f8);
+    case 256: return launch_self_qkv<T, 2>(sa, hp, inner, s, f8);
+    case 384: return launch_self_qkv<T, 3>(sa, hp, inner, s, f8);
+    case 512: return launch_self_qkv<T, 4>(sa, hp, inner, s, f8);
+    case 640: return launch_self_qkv<T, 5>(sa, hp, inner, s, f8);
+    case 768: return launch_self_qkv<T, 6>(sa, hp, inner, s, f8);
+    case 896: return launch_self_qkv<T, 7>(sa, hp, inner, s, f8);
+    default: return launch_self_qkv<T, 8>(sa, hp, inner, s, f8);
   }
 }
 template <typename T, int KC>
@@ -1179,7 +1194,13 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
     dec::HeadProjP hp{};
     hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln1[l]; hp.eps = c->eps; hp.W = w->dec_qkv[l]; hp.ldw = d; hp.d = d;
     hp.ln_b = hf ? w->dec_ln1_b[l] : nullptr;
-    MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s));
+    dec::SelfKv8P f8{};
+    if (bf.self8) {   // this layer's k | v slabs of the shadow: the chain's first row, the strides those of the full batch
+      const long rows = (long)Bfull * H * tgt;
+      f8.k8 = bf.self8 + (long)(l * 2 + 0) * rows * 64; f8.v8 = bf.self8 + (long)(l * 2 + 1) * rows * 64;
+      f8.ks = bf.self8_scales + (long)(l * 2 + 0) * rows; f8.vs = bf.self8_scales + (long)(l * 2 + 1) * rows;
+    }
+    MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s, bf.self8 ? &f8 : nullptr));
     dec::SkinnyP sk{};
     sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_o[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
     sk.bias = wh ? w->dec_o_b[l] : nullptr;
@@ -1575,6 +1596,55 @@ extern "C" int mh_t5_quantize_cross_kv(const MhT5Config* c, const void* cross_kv
   return check_launch("kv_quant_fp8_kernel");
 }
 
+// ---- e4m3 shadow of the self-attention cache ----------------------------------------------------------------------------
+// One wave per 64-element bf16 row (dec::quant_row64: the token step's append is the same function).  Rows are addressed as
+// (plane y, slab, position): plane y = (layer, k|v) reads src_k / src_v at layer * n_slabs * stride rows and writes plane y of q /
+// scales; within a plane, row (slab, i) for i < n_pos sits at row slab * stride + i of both.  Plain buffers: one plane, one slab.
+__global__ __launch_bounds__(256) void self_kv_quant_rows_kernel(const bf16_t* src_k, const bf16_t* src_v, uint8_t* q, float* scales,
+                                                                long n_slabs, long n_pos, long stride) {
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);   // (wave-uniform)
+  if (r >= n_slabs * n_pos) return;
+  const long slab = r / n_pos, i = r - slab * n_pos;
+  const long plane_rows = n_slabs * stride, y = blockIdx.y;
+  const bf16_t* src = ((y & 1) ? src_v : src_k) + (y >> 1) * plane_rows * 64;
+  const long row = slab * stride + i;
+  const float x = mh::Elem<bf16_t>::to_f32(src[row * 64 + (threadIdx.x & 63)]);
+  mh::dec::quant_row64(x, q + (y * plane_rows + row) * 64, scales + y * plane_rows + row);
+}
+
+extern "C" int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, float* scales, void* stream) {
+  MH_REQUIRE(x_bf16 && q && scales, "mh_quantize_kv_rows: null argument");
+  MH_REQUIRE(n_rows > 0, "mh_quantize_kv_rows: n_rows %lld must be positive", (long long)n_rows);
+  // a launch holds fewer than 2^32 threads: 2^24 rows (2^22 workgroups of four waves) at a time
+  constexpr int64_t kChunk = 1LL << 24;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += kChunk) {
+    const int64_t n = n_rows - r0 < kChunk ? n_rows - r0 : kChunk;
+    const bf16_t* x = (const bf16_t*)x_bf16 + r0 * 64;
+    hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n + 3) / 4), 1), dim3(256), 0, (hipStream_t)stream, x, x,
+                       (uint8_t*)q + r0 * 64, scales + r0, 1L, (long)n, (long)n);
+    MH_TRY(check_launch("self_kv_quant_rows_kernel"));
+  }
+  return MH_OK;
+}
+
+extern "C" int64_t mh_t5_self_kv_fp8_bytes(const MhT5Config* c, int B) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  if (!c || B <= 0) return -1;
+  if (c->dtype != MH_BF16) { mh::set_error("mh_t5_self_kv_fp8_bytes: the e4m3 self-attention cache needs bf16 storage"); return -1; }
+  const int64_t rows = (int64_t)c->n_dec_layers * 2 * B * c->n_heads * c->tgt_len;
+  return align256(rows * 64) + align256(rows * 4);
+}
+
+extern "C" int mh_t5_decode_self_cache(const MhT5Config* c, int B, void* workspace, void** k, void** v) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_decode_self_cache"));
+  MH_REQUIRE(workspace && k && v && B > 0, "mh_t5_decode_self_cache: null argument");
+  const mh::DecodeLayout ly = mh::decode_layout(c, B, workspace);
+  *k = ly.bf.self_k;
+  *v = ly.bf.self_v;
+  return MH_OK;
+}
+
 namespace mh {
 // ------------------------------------------------------------------------------------------------
 // Instantiated step graphs kept ACROSS mh_t5_generate calls.  A chain's step graph bakes in nothing but addresses, sizes, the
@@ -1646,33 +1716,33 @@ extern "C" int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset)
   return MH_OK;
 }
 
-extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                              const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
-                              const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
-                              const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                              void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_generate"));
-  MH_TRY(check_decode_shape(c, "mh_t5_generate"));
+// mh_t5_generate (self_kv_fp8 == NULL) and mh_t5_generate_skv8 (the caller's e4m3 shadow of the self-attention cache)
+static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
+                         const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                         const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                         const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                         void* stream, void* self_kv_fp8, const char* who) {   // who: the entry the caller used (error messages)
+  MH_TRY(check_cfg(c, who));
+  MH_TRY(check_decode_shape(c, who));
   MH_REQUIRE(w && cross_kv && prompt && eos_table && sp && tokens && n_steps_out && workspace,
-             "mh_t5_generate: null argument");
-  MH_REQUIRE(stream != nullptr, "mh_t5_generate: needs a non-default stream (hipGraph capture)");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_generate: batch %d not in [1, 64] (shard larger batches on the host)", B);
-  MH_REQUIRE(P >= 1 && P < sp->max_length, "mh_t5_generate: prompt length %d must be in [1, max_length)", P);
-  MH_REQUIRE(sp->max_length <= c->tgt_len, "mh_t5_generate: max_length %d exceeds tgt_len %d", sp->max_length, c->tgt_len);
-  MH_REQUIRE(sp->temperature > 0.f, "mh_t5_generate: temperature must be > 0");
-  MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "mh_t5_generate: too many sos ids");
+             "%s: null argument", who);
+  MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
+  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, B);
+  MH_REQUIRE(P >= 1 && P < sp->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
+  MH_REQUIRE(sp->max_length <= c->tgt_len, "%s: max_length %d exceeds tgt_len %d", who, sp->max_length, c->tgt_len);
+  MH_REQUIRE(sp->temperature > 0.f, "%s: temperature must be > 0", who);
+  MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "%s: too many sos ids", who);
   const bool cfg = sp->cfg_scale > 1.0f;
-  MH_REQUIRE(!cfg || B % 2 == 0, "mh_t5_generate: classifier-free guidance needs an even batch (negative rows, then prompt rows)");
-  MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "mh_t5_generate: n_cond %d not in [0, 3]", sp->n_cond);
+  MH_REQUIRE(!cfg || B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
+  MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "%s: n_cond %d not in [0, 3]", who, sp->n_cond);
   for (int j = 0; j < sp->n_cond; ++j)
-    MH_REQUIRE(sp->cond_temp[j] > 0.f && sp->cond_offset[j] >= 1, "mh_t5_generate: bad conditional temperature rule %d", j);
+    MH_REQUIRE(sp->cond_temp[j] > 0.f && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
   MH_REQUIRE(sp->tok_flags || (sp->n_cond == 0 && !sp->lookback_types_first),
-             "mh_t5_generate: tok_flags is required by the conditional temperature / types_first lookback processors");
+             "%s: tok_flags is required by the conditional temperature / types_first lookback processors", who);
   const int kvB = cfg ? B / 2 : B;
-  MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "mh_t5_generate: cross_kv_fp8 needs bf16 storage");
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_generate: workspace too small");
-  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "mh_t5_generate: arch 2 needs decoder.embed_positions and the LayerNorm biases");
+  MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
+  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "%s: workspace too small", who);
+  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "%s: arch 2 needs decoder.embed_positions and the LayerNorm biases", who);
   hipStream_t s = (hipStream_t)stream;
   const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
 
@@ -1706,9 +1776,24 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
       PrefillBuf pb;
       prefill_layout(c, B, P - 1, (char*)workspace + ly.end, workspace_bytes - ly.end, &pb);
       MH_REQUIRE(ly.end + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= workspace_bytes,
-                 "mh_t5_generate: workspace too small for the prompt prefill");
+                 "%s: workspace too small for the prompt prefill", who);
       MH_TRY(prefill_prompt(c, w, cross_kv, B, kvB, prompt, prompt_mask, P, P - 1, all.self_k, all.self_v, pb, s));
       start_pos = P - 1;
+    }
+  }
+  // the shadow: e4m3 rows, then (256-byte aligned) their scales.  The prompt positions the batched prefill wrote (they attended each
+  // other through the bf16 cache) are quantised in one pass before the first token step; every token step appends its own row
+  uint8_t* self8 = (uint8_t*)self_kv_fp8;
+  float* self8_scales = nullptr;
+  if (self8) {
+    const int64_t rows = (int64_t)c->n_dec_layers * 2 * B * H * c->tgt_len;
+    self8_scales = reinterpret_cast<float*>(self8 + align256(rows * 64));
+    if (start_pos > 0) {
+      const long n_slabs = (long)B * H;
+      hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
+                         (const bf16_t*)all.self_k, (const bf16_t*)all.self_v, self8, self8_scales, n_slabs, (long)start_pos,
+                         (long)c->tgt_len);
+      MH_TRY(check_launch("self_kv_quant_rows_kernel"));
     }
   }
   if (hipEventRecord(g_pool.fork, s) != hipSuccess) return check_launch("fork record");
@@ -1733,6 +1818,10 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     bf.logits = all.logits + (long)b0 * V;
     bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
     bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
+    if (self8) {   // the chain's first row of the shadow and of its scales (the same b0 offsets as the bf16 caches)
+      bf.self8 = self8 + (long)b0 * inner * c->tgt_len;
+      bf.self8_scales = self8_scales + (long)b0 * H * c->tgt_len;
+    }
     bf.finished = all.finished + b0;
     bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
     states[ci] = bf.st;
@@ -1795,7 +1884,7 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     hipError_t ce = hipStreamEndCapture(cs, &graphs[ci]);
     ++used;
     if (rce != MH_OK) { rc = rce; break; }
-    if (ce != hipSuccess || !graphs[ci]) { set_error("mh_t5_generate: stream capture failed: %s", hipGetErrorString(ce)); rc = MH_ERR_LAUNCH; break; }
+    if (ce != hipSuccess || !graphs[ci]) { set_error("%s: stream capture failed: %s", who, hipGetErrorString(ce)); rc = MH_ERR_LAUNCH; break; }
     if (hipGraphInstantiate(&execs[ci], graphs[ci], nullptr, nullptr, 0) != hipSuccess) { rc = check_launch("graph instantiate"); break; }
     if (!key.empty()) {
       if (StepGraphEntry* e = step_graph_insert(std::move(key), graphs[ci], execs[ci])) {
@@ -1868,7 +1957,7 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     }
     for (int ci = 0; ci < used; ++ci)
       if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
-      else if (rcs[ci] != MH_OK) { set_error("mh_t5_generate: graph launch / poll failed on chain %d: %s", ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
+      else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
   }
   // join the chains back into the caller's stream
   for (int ci = 0; ci < used; ++ci) {
@@ -1893,6 +1982,29 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
     if (graphs[ci]) (void)hipGraphDestroy(graphs[ci]);
   }
   return rc;
+}
+
+extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
+                              const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                              const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                              const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                              void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                       workspace_bytes, poll_every, stream, nullptr, "mh_t5_generate");
+}
+
+extern "C" int mh_t5_generate_skv8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
+                                   const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                                   const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                                   const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                                   void* stream, void* self_kv_fp8) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_generate_skv8"));
+  MH_REQUIRE(self_kv_fp8, "mh_t5_generate_skv8: null argument (self_kv_fp8: mh_t5_self_kv_fp8_bytes(cfg, B) bytes owned by the caller)");
+  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_generate_skv8: the e4m3 self-attention cache needs bf16 storage");
+  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                       workspace_bytes, poll_every, stream, self_kv_fp8, "mh_t5_generate_skv8");
 }
 
 // ------------------------------------------------------------------------------------------------

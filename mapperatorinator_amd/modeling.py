@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .conditioning import ConditioningEmbedders
-from .t5_engine import T5Dims, T5Engine, T5_PRESETS, require_bf16_for_cross_kv_fp8
+from .t5_engine import T5Dims, T5Engine, T5_PRESETS, require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
 from .whisper_engine import VARWHISPER_PRESETS, VarWhisperDims, VarWhisperEngine
 
 
@@ -410,6 +410,10 @@ class MapperatorinatorHIP:
         kv_fp8 = bool(unused.get("cross_kv_fp8", False))
         if kv_fp8:
             require_bf16_for_cross_kv_fp8(self.dtype)
+        skv8 = {}
+        if unused.get("self_kv_fp8", False):     # e4m3 shadow of the self-attention cache (T5Engine.decode): bf16 storage, no beams
+            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams))
+            skv8 = dict(self_kv_fp8=True)
         if num_beams != 1:
             out = self.engine.generate_beam(audio, decoder_input_ids, decoder_attention_mask, eos, sp, int(num_beams),
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
@@ -419,6 +423,6 @@ class MapperatorinatorHIP:
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,
                                    negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
                                    negative_mask=negative_prompt_attention_mask, cross_kv_fp8=kv_fp8,
-                                   encoder_states=enc_states,
+                                   encoder_states=enc_states, **skv8,
                                    **({} if row_bias is None else dict(row_bias=row_bias)))
         return out["tokens"].to(self.device)

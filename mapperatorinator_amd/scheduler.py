@@ -27,7 +27,7 @@ from typing import Callable, Optional
 import torch
 
 from .server import _build_generation_stats, build_sampling
-from .t5_engine import HostStager
+from .t5_engine import HostStager, require_bf16_for_self_kv_fp8
 
 
 @dataclasses.dataclass
@@ -131,6 +131,9 @@ class SequentialWindowScheduler:
     @torch.no_grad()
     def run(self, jobs: list[SongJob]):
         eng, tok = self.engine, self.tokenizer
+        for j in jobs:   # self_kv_fp8 where it is not built (fp32 storage, beams): refused before anything is encoded
+            if j.generate_kwargs.get("self_kv_fp8"):
+                require_bf16_for_self_kv_fp8(eng.dtype, int(j.generate_kwargs.get("num_beams", 1) or 1))
         start = time.perf_counter()
         kvs = self.encode_all(jobs)
         n_waves = max(j.frames.shape[0] for j in jobs)
@@ -167,6 +170,8 @@ class SequentialWindowScheduler:
         sp, eos = build_sampling(tok, gk, self.model.config.max_target_positions)
         cfg = sp.cfg_scale > 1.0
         nb = int(getattr(sp, "num_beams", 1) or 1)
+        if gk.get("self_kv_fp8"):   # (a window's own generate_kwargs may switch the mode on: the same refusals)
+            require_bf16_for_self_kv_fp8(eng.dtype, nb)
         if len(group) * (2 if cfg else 1) * nb > 64:
             raise ValueError(f"{len(group)} windows{' x 2 (guidance)' if cfg else ''}{f' x {nb} beams' if nb > 1 else ''} exceed "
                              f"the engine's 64-row decode batch")
@@ -203,10 +208,12 @@ class SequentialWindowScheduler:
             # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search
             # makes it itself: with guidance it is a copy of the doubled rows)
             kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") and nb == 1 else None
+            # generate_kwargs["self_kv_fp8"]: the token steps attend the engine's e4m3 shadow of the self-attention cache (no beams)
+            skv8 = dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {}
             if nb == 1:
                 tokens, n_out, _ = eng.decode(kv, p_all.to(dev, torch.int32).contiguous(),
                                               None if m_all is None else m_all.to(dev).contiguous(),
-                                              eos_table.to(dev), sp, kv_fp8=kv8)
+                                              eos_table.to(dev), sp, kv_fp8=kv8, **skv8)
         eng._leave()
         if nb > 1:
             # HF beam search over the step-wise decode entry (beam.py), the windows of this wave as its batch: every window's

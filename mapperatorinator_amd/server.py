@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .event import ContextType
-from .t5_engine import require_bf16_for_cross_kv_fp8
+from .t5_engine import require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
 
 MILISECONDS_PER_SECOND = 1000
 MILISECONDS_PER_STEP = 10
@@ -338,6 +338,10 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
         require_bf16_for_cross_kv_fp8(model.dtype)
     start = time.perf_counter()
     extra = {} if row_bias is None else dict(row_bias=row_bias)
+    if generate_kwargs.get("self_kv_fp8", False):
+        # the token steps attend an e4m3 shadow of the self-attention cache (T5Engine.decode); bf16 storage, no beams
+        require_bf16_for_self_kv_fp8(model.dtype, int(getattr(sp, "num_beams", 1) or 1))
+        extra["self_kv_fp8"] = True
     if getattr(sp, "num_beams", 1) > 1:
         # HF beam search (processor.py:159 `num_beams`; the timing generator uses two beams): mapperatorinator_amd/beam.py
         out = model.engine.generate_beam(audio, prompt, mask, eos, sp, sp.num_beams, negative_prompt=neg,

@@ -202,6 +202,18 @@ def require_bf16_for_cross_kv_fp8(dtype) -> None:
                          "is made of bf16 rows")
 
 
+def require_bf16_for_self_kv_fp8(dtype, num_beams: int = 1) -> None:
+    """`self_kv_fp8` where it is not built: refused on the host, before anything is encoded.  The shadow cache is made of bf16 rows
+    (fp32 storage has no e4m3 self-attention kernel), and the step-wise entries of beam search (`mh_t5_step`, `mh_t5_step_fp8`,
+    `mh_t5_reorder_cache`) have no shadow-cache form."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"self_kv_fp8 needs bf16 storage (this model stores {dtype}): the e4m3 self-attention cache is made of "
+                         "bf16 rows")
+    if num_beams > 1:
+        raise ValueError(f"self_kv_fp8 is not built for beam search (num_beams={num_beams}): the step-wise decode entries and the "
+                         "cache reorder have no e4m3 shadow-cache form; use num_beams=1 or drop the flag")
+
+
 def next_token_targets(ids: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Targets of next-token scoring: targets[b, t] = ids[b, t + 1]; the last column and every position whose TARGET column
     is masked out (left padding) are -1 = not scored.  int32, on the device of `ids`."""
@@ -413,10 +425,16 @@ class T5Engine:
 
     def decode(self, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
                eos_table: torch.Tensor, sampling: _lib.MhSampling, forced: Optional[torch.Tensor] = None,
-               dump_logits: bool = False, poll_every: int = 16, kv_fp8: Optional[torch.Tensor] = None):
+               dump_logits: bool = False, poll_every: int = 16, kv_fp8: Optional[torch.Tensor] = None,
+               self_kv_fp8: bool = False):
         """prompt int32 (B, P) on device.  Returns (tokens int32 (B, max_length) device, n_cols int, logits|None).
         Under CFG (sampling.cfg_scale > 1) the B rows are [negative-prompt rows | prompt rows], `cross_kv` holds
-        B/2 rows and the logits dump has B/2 rows (the guided scores)."""
+        B/2 rows and the logits dump has B/2 rows (the guided scores).
+        `self_kv_fp8`: the token steps attend an e4m3 shadow of the self-attention cache (`mh_t5_generate_skv8`, contract in
+        include/mapperhip.h: one fp32 scale per cached row, the step's own key / value at storage precision, the prompt prefill
+        unchanged and quantised in one pass).  The shadow is this engine's, kept like the workspaces.  bf16 storage only."""
+        if self_kv_fp8:
+            require_bf16_for_self_kv_fp8(self.dtype)
         p = self.packed
         B, P = prompt.shape
         cfg = sampling.cfg_scale > 1.0
@@ -436,12 +454,47 @@ class T5Engine:
         n_out = torch.zeros(1, dtype=torch.int32, device=self.device)
         logits = (torch.zeros((maxlen, B // 2 if cfg else B, p.vocab_out), dtype=torch.float32, device=self.device)
                   if dump_logits else None)
-        rc = self.lib.mh_t5_generate(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), B, prompt.data_ptr(),
-                                     _lib.ptr(prompt_mask), P, eos_table.data_ptr(), C.byref(sampling),
-                                     tokens.data_ptr(), n_out.data_ptr(), _lib.ptr(logits), _lib.ptr(forced),
-                                     ws.data_ptr(), ws.numel(), poll_every, self._s())
-        _lib.check(rc, "mh_t5_generate")
+        args = (C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), B, prompt.data_ptr(),
+                _lib.ptr(prompt_mask), P, eos_table.data_ptr(), C.byref(sampling),
+                tokens.data_ptr(), n_out.data_ptr(), _lib.ptr(logits), _lib.ptr(forced),
+                ws.data_ptr(), ws.numel(), poll_every, self._s())
+        if self_kv_fp8:
+            skv8 = self._workspace("skv8", self.lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), B))
+            _lib.check(self.lib.mh_t5_generate_skv8(*args, skv8.data_ptr()), "mh_t5_generate_skv8")
+        else:
+            _lib.check(self.lib.mh_t5_generate(*args), "mh_t5_generate")
         return tokens, n_out, logits
+
+    def quantize_kv_rows(self, rows: torch.Tensor):
+        """`mh_quantize_kv_rows`: bf16 (..., 64) on the device -> (e4m3 bytes uint8 (..., 64), fp32 scales (...)), the row form of the
+        e4m3 self-attention cache (scale = absmax / 448, element = cvt_e4m3(x * (1 / scale)))."""
+        rows = rows.contiguous()
+        if rows.dtype != torch.bfloat16 or rows.shape[-1] != 64:
+            raise ValueError(f"rows must be bf16 (..., 64), got {rows.dtype} {tuple(rows.shape)}")
+        q = torch.empty(rows.shape, dtype=torch.uint8, device=rows.device)
+        sc = torch.empty(rows.shape[:-1], dtype=torch.float32, device=rows.device)
+        _lib.check(self.lib.mh_quantize_kv_rows(rows.data_ptr(), rows.numel() // 64, q.data_ptr(), sc.data_ptr(), self._s()),
+                   "mh_quantize_kv_rows")
+        return q, sc
+
+    def self_kv_caches(self, B: int, shadow: bool = False):
+        """Views of what the last `decode` of B rows left behind (no copy): the bf16 self-attention caches (k, v), each
+        (n_dec, B, H, tgt_len, 64), read through `mh_t5_decode_self_cache`; with `shadow` also the e4m3 shadow of a `self_kv_fp8`
+        decode: bytes uint8 (n_dec, 2, B, H, tgt_len, 64) and fp32 scales (n_dec, 2, B, H, tgt_len)."""
+        p = self.packed
+        ws = self._ws["dec"]
+        k, v = C.c_void_p(), C.c_void_p()
+        _lib.check(self.lib.mh_t5_decode_self_cache(C.byref(p.cfg), B, ws.data_ptr(), C.byref(k), C.byref(v)), "mh_t5_decode_self_cache")
+        shape = (self.dims.n_dec_layers, B, self.dims.n_heads, p.tgt_len, 64)
+        n = shape[0] * shape[1] * shape[2] * shape[3] * 64 * ws.new_empty(0, dtype=self.dtype).element_size()
+        out = [ws[ptr - ws.data_ptr(): ptr - ws.data_ptr() + n].view(self.dtype).view(shape) for ptr in (k.value, v.value)]
+        if shadow:
+            sh = self._ws["skv8"]
+            rows = shape[0] * 2 * B * shape[2] * shape[3]
+            off = (rows * 64 + 255) // 256 * 256
+            out.append(sh[: rows * 64].view(shape[0], 2, B, shape[2], shape[3], 64))
+            out.append(sh[off: off + rows * 4].view(torch.float32).view(shape[0], 2, B, shape[2], shape[3]))
+        return tuple(out)
 
     def generate_beam(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids,
                       sampling: _lib.MhSampling, num_beams: int, row_bias: Optional[torch.Tensor] = None,
@@ -480,10 +533,12 @@ class T5Engine:
                  eos_ids, sampling: _lib.MhSampling, forced: Optional[torch.Tensor] = None,
                  dump_logits: bool = False, poll_every: int = 16, negative_prompt: Optional[torch.Tensor] = None,
                  negative_mask: Optional[torch.Tensor] = None, cross_kv_fp8: bool = False,
-                 row_bias: Optional[torch.Tensor] = None, encoder_states: Optional[torch.Tensor] = None):
+                 row_bias: Optional[torch.Tensor] = None, encoder_states: Optional[torch.Tensor] = None,
+                 self_kv_fp8: bool = False):
         """Full hot path for one batch of chunks.  `encoder_states` (B, src_len, d_model): the encoder's last_hidden_state given by
         the caller (`generate(encoder_outputs=...)` of the reference's signature) -- mel and encoder are skipped, `audio` may be None.  `cross_kv_fp8`: the token steps stream the e4m3 copy of the
-        cross-attention K / V (see `cross_kv_fp8()`).  Inputs may be CPU tensors (copied like
+        cross-attention K / V (see `cross_kv_fp8()`); `self_kv_fp8`: they attend the e4m3 shadow of the self-attention cache (see `decode`; the two
+        compose to a whole fp8 K/V cache).  Inputs may be CPU tensors (copied like
         server.py:86-87 does).  Returns dict(tokens=int64 CPU (B, n_cols), logits=..., n_cols=int).
         With `negative_prompt` (classifier-free guidance) the decode batch is doubled the way the reference's
         prepare_inputs_for_generation does it (modeling_mapperatorinator.py:243-254): the first half carries the
@@ -491,6 +546,8 @@ class T5Engine:
         dev = self.device
         if cross_kv_fp8:
             require_bf16_for_cross_kv_fp8(self.dtype)
+        if self_kv_fp8:
+            require_bf16_for_self_kv_fp8(self.dtype)
         if encoder_states is None:
             audio = audio.to(dev, torch.float32)
         else:
@@ -528,7 +585,7 @@ class T5Engine:
             kv = self.cross_kv(enc)
             kv8 = self.cross_kv_fp8(kv) if cross_kv_fp8 else None
             tokens, n_out, logits = self.decode(kv, prompt_d, mask_d, eos_table, sampling, forced_d, dump_logits,
-                                                poll_every, kv_fp8=kv8)
+                                                poll_every, kv_fp8=kv8, self_kv_fp8=self_kv_fp8)
         self._leave()
         torch.cuda.current_stream(dev).synchronize()
         n_cols = int(n_out.item()) if forced is None else sampling.max_length
