@@ -111,7 +111,7 @@ int mh_options_clear(MhOptionSet* set, const char* name);      /* drop one overr
 long mh_options_get(const MhOptionSet* set, const char* name);
 /* sizeof() of the ABI structs as this library was compiled, so that a binding can verify its own layout:
  * which = 0 MhGemm, 1 MhT5Config, 2 MhT5Weights, 3 MhSampling, 4 MhDiTConfig, 5 MhDiTWeights,
- * 6 MhSliderSet; -1 otherwise. */
+ * 6 MhSliderSet, 7 MhBeamStep, 8 MhRowSampling; -1 otherwise. */
 int mh_struct_size(int which);
 
 /* ------------------------------------------------------------------------------------------------
@@ -498,6 +498,54 @@ int mh_t5_generate_skv8(const MhT5Config* cfg, const MhT5Weights* w, const void*
                         void* stream, void* self_kv_fp8);
 int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, float* scales, void* stream);
 int mh_t5_decode_self_cache(const MhT5Config* cfg, int B, void* workspace, void** k, void** v);
+
+/* Row settings: the greedy / sampled decode with one MhRowSampling per RETURNED row, so that requests with different settings share
+ * one call (additive at ABI 11: one struct, one symbol, mh_struct_size(8); MhSampling keeps its layout).  No reference counterpart:
+ * the reference decodes one kwargs set per call; every row here computes what it computes in a uniform call (mh_t5_generate /
+ * mh_t5_generate_skv8) made with its own settings, bit for bit -- token ids up to the row's end and its rows of logits_dump.
+ * Contract:
+ *   - per ROW, from rows[r] (r = index among the returned rows: the batch row, or the pair index under guidance):
+ *       temperature; cond_temp[3] with cond_mask (bit j set: rule j of sp applies to this row.  A rule the reference drops for this
+ *       row because its temperature equals the row's base one (logit_processors.py:62-67) has its bit CLEAR and is skipped -- first
+ *       match wins, so it must not match with the base temperature); top_k; top_p; timeshift_bias; lookback_mask_end; max_length (the
+ *       row finishes at its own cap and receives pad_id afterwards; `tokens` keeps the stride sp->max_length, the largest cap);
+ *       eos_set (row of eos_tables); seed and rng_row (the draw stays uniform01(seed, rng_row, column): rng_row = rng_row0 + the
+ *       row's index in the uniform call it is compared with); cfg_scale (the pair's scale under guidance).
+ *   - per CALL, from sp as in mh_t5_generate: do_sample, guidance on / off (sp->cfg_scale > 1), ts_start / ts_end, sos_ids, n_cond,
+ *     cond_offset, tok_flags (the token set of rule j is bit 2 << j for every row), lookback_types_first, pad_id, cond_per_row,
+ *     cross_kv_fp8; max_length is the stride of `tokens` and the cap of the loop.  sp's per-row fields (temperature, cond_temp,
+ *     top_k, top_p, timeshift_bias, lookback_mask_end, seed, rng_row0) and the `eos_table` argument are ignored.
+ *   - rows       device, B entries (B / 2 under guidance); read by every token step: the CONTENTS may change between calls without
+ *                a new step graph, the pointer is part of the graph's cache key (as eos_tables and n_eos_sets are: a caller who
+ *                wants one graph for any mix keeps both buffers and passes the count of sets the buffer holds; the key holds
+ *                sp->cfg_scale as on / off only, the scale being each pair's own)
+ *     eos_tables device uint8 [n_eos_sets][vocab_out]
+ *   - the library cannot read `rows` before the launch; the sampler clamps eos_set into [0, n_eos_sets) and max_length into
+ *     [1, sp->max_length], so no entry can make it read or write out of bounds.  temperature and cond_temp must be > 0.
+ *   - self_kv_fp8 may be NULL (mh_t5_generate) or the shadow of mh_t5_generate_skv8 (bf16 storage only, as there).
+ *   - refused with MH_ERR_ARG and a message before any launch: NULL rows / eos_tables, n_eos_sets < 1, what mh_t5_generate(_skv8) refuse.
+ * Not built: beams -- mh_t5_step / mh_beam_step have no row form; guided and unguided rows, or greedy and sampled rows, in one call. */
+typedef struct MhRowSampling {
+  float temperature;
+  float cond_temp[3];
+  int cond_mask;            /* 3 bits */
+  int top_k;
+  float top_p;
+  float timeshift_bias;
+  int lookback_mask_end;
+  int max_length;
+  int eos_set;
+  unsigned rng_row;
+  uint64_t seed;
+  float cfg_scale;
+  int reserved;             /* 0 (the entry is 64 bytes) */
+} MhRowSampling;
+
+int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B,
+                        const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                        const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                        const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                        void* stream, void* self_kv_fp8, const MhRowSampling* rows, const uint8_t* eos_tables, int n_eos_sets);
 
 /* (ABI 10) One beam-search step between two decoder positions as ONE kernel (csrc/beam.hip).  Replaces the per-step body of HF
  * `GenerationMixin._beam_search` (third-party, transformers >= 4.50's vectorised form) as the reference reaches it with

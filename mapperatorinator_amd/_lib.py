@@ -83,6 +83,14 @@ class MhSampling(C.Structure):
                 ("cross_kv_fp8", C.c_void_p)]
 
 
+class MhRowSampling(C.Structure):
+    """One returned row's settings of mh_t5_generate_rows (64 bytes; the lists of per-row and per-call settings: mapperhip.h)."""
+    _fields_ = [("temperature", C.c_float), ("cond_temp", C.c_float * 3), ("cond_mask", C.c_int), ("top_k", C.c_int),
+                ("top_p", C.c_float), ("timeshift_bias", C.c_float), ("lookback_mask_end", C.c_int), ("max_length", C.c_int),
+                ("eos_set", C.c_int), ("rng_row", C.c_uint), ("seed", C.c_uint64), ("cfg_scale", C.c_float),
+                ("reserved", C.c_int)]
+
+
 class MhBeamStep(C.Structure):
     _fields_ = [("logits", VP), ("eos_table", VP),
                 ("G", C.c_int), ("num_beams", C.c_int), ("V", C.c_int), ("P", C.c_int), ("max_length", C.c_int), ("K", C.c_int),
@@ -161,6 +169,8 @@ SYMBOLS = {
     "mh_t5_self_kv_fp8_bytes": (I64, [C.POINTER(MhT5Config), I]),
     "mh_t5_generate_skv8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP,
                                 C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP, VP]),
+    "mh_t5_generate_rows": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP,
+                                C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP, VP, VP, VP, I]),
     "mh_quantize_kv_rows": (I, [VP, I64, VP, VP, VP]),
     "mh_t5_decode_self_cache": (I, [C.POINTER(MhT5Config), I, VP, C.POINTER(VP), C.POINTER(VP)]),
     "mh_t5_step": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, I, VP, I, VP, I, VP, VP, I64, VP]),
@@ -222,7 +232,8 @@ def load():
         fn.argtypes = args
     if lib.mh_abi_version() != ABI_VERSION:
         raise RuntimeError("libmapperhip.so ABI version mismatch")
-    for which, st in enumerate((MhGemm, MhT5Config, MhT5Weights, MhSampling, MhDiTConfig, MhDiTWeights, MhSliderSet, MhBeamStep)):
+    for which, st in enumerate((MhGemm, MhT5Config, MhT5Weights, MhSampling, MhDiTConfig, MhDiTWeights, MhSliderSet, MhBeamStep,
+                                MhRowSampling)):
         if lib.mh_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"libmapperhip.so: layout of {st.__name__} differs from the binding "
                                f"({lib.mh_struct_size(which)} vs {C.sizeof(st)} bytes)")

@@ -144,6 +144,7 @@ extern "C" int mh_struct_size(int which) {
     case 5: return (int)sizeof(MhDiTWeights);
     case 6: return (int)sizeof(MhSliderSet);
     case 7: return (int)sizeof(MhBeamStep);
+    case 8: return (int)sizeof(MhRowSampling);
   }
   return -1;
 }

@@ -449,6 +449,15 @@ struct SampleP {
   int chain_rows;                     // rows of this chain (both halves under CFG)
 };
 
+// dec_sample_kernel's trailing argument: the row settings of mh_t5_generate_rows (the ROWS instantiations), or nothing
+struct RowSetP { const MhRowSampling* rows; const uint8_t* eos_tables; int n_eos_sets; };
+struct NoRowSetP {};
+struct RowVals {   // one entry as the sampler holds it (scalars: no indexed member, nothing that would live in scratch)
+  float temperature, cond_temp0, cond_temp1, cond_temp2, top_p, timeshift_bias, cfg_scale;
+  int cond_mask, top_k, lookback_mask_end, max_length, eos_set;
+  unsigned rng_row; uint64_t seed;
+};
+
 __device__ inline int32_t next_ts_state(const MhSampling& sp, int tok, int32_t cur) {
   // incremental form of MonotonicTimeShiftLogitsProcessor's "last TIME_SHIFT after the last SOS-type
   // token" scan (osuT5/osuT5/inference/logit_processors.py:150-172): the state after `tok`
@@ -514,8 +523,10 @@ constexpr int kSampleRegs = 16;   // the register sampling path holds up to 16 i
 // One workgroup per returned row (per CFG pair): processors -> selection -> bookkeeping -> next-token embedding.
 // Processor order = server.py:106-134: CFG -> MonotonicTimeShift -> TimeshiftBias -> (Conditional)Temperature ->
 // LookbackBias, then HF's own top-k / top-p warpers and the multinomial draw.
-template <typename T>
-__global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
+// ROWS (mh_t5_generate_rows): temperature, the conditional temperatures and their mask, top-k / top-p, the time-shift bias, the
+// lookback end, the length cap, the EOS set, the RNG key and the guidance scale come from rs.rows[returned row] instead of p.sp
+template <typename T, bool ROWS = false>
+__global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std::conditional<ROWS, RowSetP, NoRowSetP>::type rs) {
   __shared__ float sf[8];
   __shared__ int si[8];
   __shared__ float s3[12];
@@ -549,11 +560,24 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
       rawn[i] = cfg ? lgn[v] : 0.f;
     }
   }
+  // (ROWS: the row's entry, 64 bytes at a workgroup-uniform address, leaves with the same round trip)
+  RowVals row{};
+  if constexpr (ROWS) {
+    const MhRowSampling& r = rs.rows[gr];
+    row.temperature = r.temperature; row.cond_temp0 = r.cond_temp[0]; row.cond_temp1 = r.cond_temp[1]; row.cond_temp2 = r.cond_temp[2];
+    row.cond_mask = r.cond_mask; row.top_k = r.top_k; row.top_p = r.top_p; row.timeshift_bias = r.timeshift_bias;
+    row.lookback_mask_end = r.lookback_mask_end; row.eos_set = r.eos_set; row.rng_row = r.rng_row; row.seed = r.seed;
+    row.cfg_scale = r.cfg_scale;
+    // the row's own cap, never beyond the stride of `tokens`
+    row.max_length = r.max_length < 1 ? 1 : (r.max_length < p.max_length ? r.max_length : p.max_length);
+  }
   const bool was_finished = p.finished[b] != 0;
   const int ltv = p.last_ts_val[b];
   const int pos = p.st->pos;
   const int col = pos + 1;  // column being produced
   const MhSampling& sp = p.sp;
+  // a per-row setting where it is used: the row's value, or the very expression the uniform form always had
+#define MH_ROWV(f) (ROWS ? row.f : sp.f)
   if (col >= p.max_length) return;
   int nxt[2] = {0, 0};      // the ids the next step is fed (row b, and under guidance its negative-prompt row)
 
@@ -567,11 +591,14 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
       // ConditionalTemperatureLogitsWarper: the lookback is ROW 0's history for the whole batch
       // (logit_processors.py:75-80 `input_ids[0, -max_offset:]`), first matching rule wins; cond_per_row: the row's
       // own history (= the reference called with batch 1 per row: sequential songs, shards)
-      float temp = sp.temperature;
+      float temp = MH_ROWV(temperature);
       const int row0 = sp.cond_per_row ? b : (cfg ? p.pair : 0);
       for (int j = 0; j < sp.n_cond; ++j) {
+        if constexpr (ROWS) {   // a rule this row does not have (its temperature equals the row's base one) must not match
+          if (!((row.cond_mask >> j) & 1)) continue;
+        }
         const int off = sp.cond_offset[j];
-        if (col >= off && (sp.tok_flags[history_id(p, row0, col - off)] & (2 << j))) { temp = sp.cond_temp[j]; break; }
+        if (col >= off && (sp.tok_flags[history_id(p, row0, col - off)] & (2 << j))) { temp = ROWS ? (j == 0 ? row.cond_temp0 : (j == 1 ? row.cond_temp1 : row.cond_temp2)) : sp.cond_temp[j]; break; }
       }
       s_temp = temp;
       // LookbackBiasLogitsWarper types_first: "the scores are for a timeshift event" when the last id is a timed event
@@ -579,16 +606,16 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
     }
     __syncthreads();
     const float temp = s_temp;
-    const bool lb_range_on = sp.lookback_mask_end > sp.ts_start;
+    const bool lb_range_on = MH_ROWV(lookback_mask_end) > sp.ts_start;
     // CFG -> monotonic -> bias -> temperature
     auto warped_of = [&](int v, float x, float xn) -> float {
       // HF ClassifierFreeGuidanceLogitsProcessor on the reference's row order (first half = negative prompt):
       // uncond + (cond - uncond) * scale with cond = first half, no fused multiply-add
-      if (cfg) x = __fadd_rn(x, __fmul_rn(__fsub_rn(xn, x), sp.cfg_scale));
+      if (cfg) x = __fadd_rn(x, __fmul_rn(__fsub_rn(xn, x), MH_ROWV(cfg_scale)));
       // MonotonicTimeShiftLogitsProcessor: ids [ts_start, ts_start + value) -> -inf
       if (ltv >= 0 && v >= sp.ts_start && v < sp.ts_start + ltv) x = -INFINITY;
       // TimeshiftBias
-      if (sp.timeshift_bias != 0.f && v >= sp.ts_start && v < sp.ts_end) x += sp.timeshift_bias;
+      if (MH_ROWV(timeshift_bias) != 0.f && v >= sp.ts_start && v < sp.ts_end) x += MH_ROWV(timeshift_bias);
       // TemperatureLogitsWarper / ConditionalTemperatureLogitsWarper (scores / temperature)
       return x / temp;
     };
@@ -625,7 +652,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
         for (int v = tid; v < p.V; v += 256) {
           const float ec = expf(cur[v] - mc), el = expf(last[v] - ml);
           s_cur += ec;
-          if (!(v >= sp.ts_start && v < sp.lookback_mask_end)) o_cur += ec;
+          if (!(v >= sp.ts_start && v < MH_ROWV(lookback_mask_end))) o_cur += ec;
           s_last += el;
           if (sp.tok_flags[v] & 16) e_last += el;
         }
@@ -639,7 +666,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
         const float log_norm = logf(s_cur) - logf(sc);
         for (int v = tid; v < p.V; v += 256) {
           float x;
-          if (v >= sp.ts_start && v < sp.lookback_mask_end) x = (v == sp.ts_start) ? logf(extra) : -INFINITY;
+          if (v >= sp.ts_start && v < MH_ROWV(lookback_mask_end)) x = (v == sp.ts_start) ? logf(extra) : -INFINITY;
           else x = (cur[v] - mc) - log_norm;   // log(softmax(cur)[v] * sc), kept in the log domain (no underflow)
           consider(v, x);
         }
@@ -651,14 +678,14 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
         if (v < p.V) {
           float x = warped_of(v, raw[i], rawn[i]);
           // LookbackBiasLogitsWarper, types_first == False branch
-          if (lb_range_on && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
+          if (lb_range_on && v >= sp.ts_start && v < MH_ROWV(lookback_mask_end)) x = -INFINITY;
           consider(v, x);
         }
       }
     } else {
       for (int v = tid; v < p.V; v += 256) {
         float x = warped(v);
-        if (lb_range_on && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
+        if (lb_range_on && v >= sp.ts_start && v < MH_ROWV(lookback_mask_end)) x = -INFINITY;
         consider(v, x);
       }
     }
@@ -702,7 +729,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
         out[2] = s3[2] + s3[5] + s3[8] + s3[11];
       };
       float thr = -INFINITY;
-      if (sp.top_k > 0 && sp.top_k < p.V) {   // largest threshold (to 80 / 4^14) that still keeps >= top_k ids
+      if (MH_ROWV(top_k) > 0 && MH_ROWV(top_k) < p.V) {   // largest threshold (to 80 / 4^14) that still keeps >= top_k ids
         float lo = -80.f, hi = 0.f;
         for (int it = 0; it < 14; ++it) {
           const float q = 0.25f * (hi - lo), t1 = lo + q, t2 = lo + 2.f * q, t3 = lo + 3.f * q;
@@ -711,7 +738,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
           for (int i = 0; i < kSampleRegs; ++i) { c1 += xr[i] >= t1 ? 1.f : 0.f; c2 += xr[i] >= t2 ? 1.f : 0.f; c3 += xr[i] >= t3 ? 1.f : 0.f; }
           float r[3];
           reduce3(c1, c2, c3, r);
-          const float k = (float)sp.top_k;
+          const float k = (float)MH_ROWV(top_k);
           if (r[2] >= k) lo = t3; else if (r[1] >= k) { lo = t2; hi = t3; } else if (r[0] >= k) { lo = t1; hi = t2; } else hi = t1;
         }
         thr = lo;
@@ -721,7 +748,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
 #pragma unroll
       for (int i = 0; i < kSampleRegs; ++i) { er[i] = xr[i] >= thr ? __expf(xr[i]) : 0.f; part += er[i]; }
       const float total = block_sum(part, sf);
-      if (sp.top_p < 1.0f) {   // largest probability threshold whose kept mass still reaches top_p
+      if (MH_ROWV(top_p) < 1.0f) {   // largest probability threshold whose kept mass still reaches top_p
         float lo = 0.f, hi = 1.f;
         const float inv = 1.0f / total;
         for (int it = 0; it < 12; ++it) {
@@ -734,7 +761,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
           }
           float r[3];
           reduce3(m1, m2, m3, r);
-          if (r[2] >= sp.top_p) lo = t3; else if (r[1] >= sp.top_p) { lo = t2; hi = t3; } else if (r[0] >= sp.top_p) { lo = t1; hi = t2; } else hi = t1;
+          if (r[2] >= MH_ROWV(top_p)) lo = t3; else if (r[1] >= MH_ROWV(top_p)) { lo = t2; hi = t3; } else if (r[0] >= MH_ROWV(top_p)) { lo = t1; hi = t2; } else hi = t1;
         }
 #pragma unroll
         for (int i = 0; i < kSampleRegs; ++i) er[i] = (er[i] * inv >= lo) ? er[i] : 0.f;
@@ -769,7 +796,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
       float base = incl - run;
       for (int w2 = 0; w2 < wid; ++w2) base += sf[w2];
       const float mass = sf[0] + sf[1] + sf[2] + sf[3];
-      const float u = uniform01(p.st->seed, (uint32_t)gr + p.st->rng_row0, (uint32_t)col) * mass;
+      const float u = uniform01(ROWS ? row.seed : p.st->seed, ROWS ? row.rng_row : (uint32_t)gr + p.st->rng_row0, (uint32_t)col) * mass;
       int first = 0x7fffffff, last = -1;
       float prev = 0.f;
 #pragma unroll
@@ -788,14 +815,14 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
       const float mx = sf[4];
       __syncthreads();   // sf[4] is reused as reduction scratch below
       float thr = -INFINITY;
-      if (sp.top_k > 0 && sp.top_k < p.V) {
+      if (MH_ROWV(top_k) > 0 && MH_ROWV(top_k) < p.V) {
         float lo = -80.f, hi = 0.f;  // on x - mx
         for (int it = 0; it < 40; ++it) {
           const float mid = 0.5f * (lo + hi);
           int cnt = 0;
           for (int v = tid; v < p.V; v += 256) cnt += (fin[v] - mx >= mid) ? 1 : 0;
           cnt = (int)block_sum((float)cnt, sf);
-          if (cnt >= sp.top_k) lo = mid; else hi = mid;
+          if (cnt >= MH_ROWV(top_k)) lo = mid; else hi = mid;
         }
         thr = lo;
       }
@@ -807,7 +834,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
       }
       float total = block_sum(part, sf);
       float pthr = 0.f;
-      if (sp.top_p < 1.0f) {
+      if (MH_ROWV(top_p) < 1.0f) {
         // keep the smallest set of most-probable ids whose mass reaches top_p
         float lo = 0.f, hi = 1.f;
         for (int it = 0; it < 30; ++it) {
@@ -821,7 +848,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
             }
           }
           mass = block_sum(mass, sf);
-          if (mass >= sp.top_p) lo = mid; else hi = mid;
+          if (mass >= MH_ROWV(top_p)) lo = mid; else hi = mid;
         }
         pthr = lo;
         float part2 = 0.f;
@@ -837,14 +864,14 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
         __syncthreads();
       }
       if (tid == 0) {
-        const float u = uniform01(p.st->seed, (uint32_t)gr + p.st->rng_row0, (uint32_t)col) * s_sum;
+        const float u = uniform01(ROWS ? row.seed : p.st->seed, ROWS ? row.rng_row : (uint32_t)gr + p.st->rng_row0, (uint32_t)col) * s_sum;
         float cum = 0.f;
         int pick = tok;
         for (int v = 0; v < p.V; ++v) {
           const float x = fin[v];
           if (x - mx >= thr) {
             const float e = __expf(x - mx);
-            if (sp.top_p < 1.0f && e / total < pthr) continue;
+            if (MH_ROWV(top_p) < 1.0f && e / total < pthr) continue;
             cum += e;
             pick = v;
             if (cum >= u) break;
@@ -862,13 +889,18 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
     nxt[0] = forced ? p.forced[(long)b * p.max_length + col] : emit;
     if (cfg) nxt[1] = forced ? p.forced[(long)bneg * p.max_length + col] : emit;
     if (tid == 0) {
-      const bool done = !forced && !was_finished && (p.eos_table[emit] || col + 1 >= sp.max_length);
+      const uint8_t* eos = p.eos_table;
+      if constexpr (ROWS) {   // the row's set, clamped into the tables the call was given
+        const int set = row.eos_set < 0 ? 0 : (row.eos_set < rs.n_eos_sets ? row.eos_set : rs.n_eos_sets - 1);
+        eos = rs.eos_tables + (long)set * p.V;
+      }
+      const bool done = !forced && !was_finished && (eos[emit] || col + 1 >= MH_ROWV(max_length));
       for (int j = 0; j < nrow; ++j) {   // the rows of a CFG pair receive the same id (decoder_input_ids.repeat)
-        const int row = j == 0 ? b : bneg;
-        dec::store_wt(p.tokens + (long)row * p.max_length + col, (int32_t)emit);
+        const int brow = j == 0 ? b : bneg;   // (not `row`: that is the row's settings, which MH_ROWV reads)
+        dec::store_wt(p.tokens + (long)brow * p.max_length + col, (int32_t)emit);
         if (done) {
-          __hip_atomic_store(&p.finished[row], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the last-arriving workgroup below
-          dec::store_wt(p.finish_col + row, (int32_t)col);
+          __hip_atomic_store(&p.finished[brow], (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the last-arriving workgroup below
+          dec::store_wt(p.finish_col + brow, (int32_t)col);
         }
       }
       dec::store_wt(&p.last_ts_val[b], next_ts_state(sp, nxt[0], ltv));
@@ -912,6 +944,8 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p) {
     }
   }
 }
+
+#undef MH_ROWV
 
 __global__ void dec_finalize_kernel(const int32_t* finish_col, int B, int32_t* n_steps_out) {
   if (threadIdx.x == 0) {
@@ -1163,7 +1197,9 @@ DecodeTiming g_timing;
 template <typename T>
 int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int Bfull, int kvB,
                  const uint8_t* prompt_mask, int P, const DecBuffers& bf, const SampleP& smp, hipStream_t s,
-                 const void* kv8 = nullptr, const float* kv8_scales = nullptr, bool with_sampler = true, int kv_group = 0) {
+                 const void* kv8 = nullptr, const float* kv8_scales = nullptr, bool with_sampler = true, int kv_group = 0,
+                 const RowSetP* rows = nullptr) {
+  // rows != NULL: the sampler reads its settings per returned row (mh_t5_generate_rows)
   // with_sampler = false: the step ends with the logits (mh_t5_step: the host selects); kv_group > 1: rows are (chunk, beam)
   // pairs and row b reads cross K/V row b / kv_group
   // kv8 / kv8_scales: the chain's first row of the e4m3 copy of cross_kv and of its scales (mh_t5_quantize_cross_kv)
@@ -1269,7 +1305,8 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
   if (hf) { sk.ln_b = w->dec_final_ln_b; MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_LOGITS>(sk, s))); }
   else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_LOGITS>(sk, s)));
   if (!with_sampler) return MH_OK;
-  hipLaunchKernelGGL(dec_sample_kernel<T>, dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp);
+  if (rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, *rows);
+  else hipLaunchKernelGGL((dec_sample_kernel<T, false>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, NoRowSetP{});
   return check_launch("dec_sample_kernel");
 }
 
@@ -1716,27 +1753,29 @@ extern "C" int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset)
   return MH_OK;
 }
 
-// mh_t5_generate (self_kv_fp8 == NULL) and mh_t5_generate_skv8 (the caller's e4m3 shadow of the self-attention cache)
+// mh_t5_generate (self_kv_fp8 == NULL), mh_t5_generate_skv8 (the caller's e4m3 shadow of the self-attention cache) and
+// mh_t5_generate_rows (rowset != NULL: the sampler's settings per returned row)
 static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
                          const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
                          const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
                          const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                         void* stream, void* self_kv_fp8, const char* who) {   // who: the entry the caller used (error messages)
+                         void* stream, void* self_kv_fp8, const char* who,   // who: the entry the caller used (error messages)
+                         const mh::RowSetP* rowset = nullptr) {
   MH_TRY(check_cfg(c, who));
   MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && cross_kv && prompt && eos_table && sp && tokens && n_steps_out && workspace,
+  MH_REQUIRE(w && cross_kv && prompt && (eos_table || rowset) && sp && tokens && n_steps_out && workspace,
              "%s: null argument", who);
   MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
   MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, B);
   MH_REQUIRE(P >= 1 && P < sp->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
   MH_REQUIRE(sp->max_length <= c->tgt_len, "%s: max_length %d exceeds tgt_len %d", who, sp->max_length, c->tgt_len);
-  MH_REQUIRE(sp->temperature > 0.f, "%s: temperature must be > 0", who);
+  MH_REQUIRE(rowset || sp->temperature > 0.f, "%s: temperature must be > 0", who);
   MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "%s: too many sos ids", who);
   const bool cfg = sp->cfg_scale > 1.0f;
   MH_REQUIRE(!cfg || B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
   MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "%s: n_cond %d not in [0, 3]", who, sp->n_cond);
   for (int j = 0; j < sp->n_cond; ++j)
-    MH_REQUIRE(sp->cond_temp[j] > 0.f && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
+    MH_REQUIRE((rowset || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
   MH_REQUIRE(sp->tok_flags || (sp->n_cond == 0 && !sp->lookback_types_first),
              "%s: tok_flags is required by the conditional temperature / types_first lookback processors", who);
   const int kvB = cfg ? B / 2 : B;
@@ -1862,12 +1901,21 @@ static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* 
       for (int o = 0; o < OPT_COUNT; ++o) opts[o] = option(o);
       int dev_id = 0;
       (void)hipGetDevice(&dev_id);
-      const void* ptrs[] = {ckv, pm, kv8, kv8_scales, (const void*)g_timing.buf};
-      const int ints[] = {Bc, B, kvB, P, g_timing.ring, dev_id, bf16 ? 1 : 0};
+      // (the row form is another sampler with two more pointers in its arguments: keyed apart from the uniform form)
+      const void* ptrs[] = {ckv, pm, kv8, kv8_scales, (const void*)g_timing.buf, rowset ? (const void*)rowset->rows : nullptr,
+                            rowset ? (const void*)rowset->eos_tables : nullptr};
+      const int ints[] = {Bc, B, kvB, P, g_timing.ring, dev_id, bf16 ? 1 : 0, rowset ? 1 : 0, rowset ? rowset->n_eos_sets : 0};
       put(&cc, sizeof(cc)); put(opts, sizeof(opts)); put(w, sizeof(*w)); put(ptrs, sizeof(ptrs)); put(ints, sizeof(ints));
       SampleP smp_key = smp;          // (seed and rng_row0 reach the sampler through DecState, not through the graph)
       smp_key.sp.seed = 0;
       smp_key.sp.rng_row0 = 0;
+      if (rowset) {                   // the row form ignores these: calls that differ in them alone replay one graph
+        smp_key.eos_table = nullptr;
+        smp_key.sp.cfg_scale = cfg ? 2.f : 1.f;   // (guidance on / off is the call's, the scale each pair's own)
+        smp_key.sp.temperature = smp_key.sp.top_p = smp_key.sp.timeshift_bias = 0.f;
+        smp_key.sp.top_k = smp_key.sp.lookback_mask_end = 0;
+        for (int j = 0; j < 3; ++j) smp_key.sp.cond_temp[j] = 0.f;
+      }
       put(&bf, sizeof(bf)); put(&smp_key, sizeof(smp_key));
       if (StepGraphEntry* e = step_graph_acquire(key)) {
         cached[ci] = e;
@@ -1879,8 +1927,8 @@ static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* 
       g_step_graph_misses.fetch_add(1);
     }
     if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) { rc = check_launch("begin capture"); break; }
-    int rce = bf16 ? enqueue_step<bf16_t>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales)
-                   : enqueue_step<float>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales);
+    int rce = bf16 ? enqueue_step<bf16_t>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales, true, 0, rowset)
+                   : enqueue_step<float>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales, true, 0, rowset);
     hipError_t ce = hipStreamEndCapture(cs, &graphs[ci]);
     ++used;
     if (rce != MH_OK) { rc = rce; break; }
@@ -2005,6 +2053,23 @@ extern "C" int mh_t5_generate_skv8(const MhT5Config* c, const MhT5Weights* w, co
   MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_generate_skv8: the e4m3 self-attention cache needs bf16 storage");
   return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
                        workspace_bytes, poll_every, stream, self_kv_fp8, "mh_t5_generate_skv8");
+}
+
+extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
+                                   const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
+                                   const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
+                                   const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
+                                   void* stream, void* self_kv_fp8, const MhRowSampling* rows, const uint8_t* eos_tables,
+                                   int n_eos_sets) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  (void)eos_table;   // ignored: every row names its set of eos_tables
+  MH_TRY(check_cfg(c, "mh_t5_generate_rows"));
+  MH_REQUIRE(rows && eos_tables, "mh_t5_generate_rows: null argument (rows: one MhRowSampling per returned row; eos_tables: [n_eos_sets][vocab_out])");
+  MH_REQUIRE(n_eos_sets >= 1, "mh_t5_generate_rows: n_eos_sets %d must be >= 1", n_eos_sets);
+  MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "mh_t5_generate_rows: the e4m3 self-attention cache needs bf16 storage");
+  const mh::RowSetP rowset{rows, eos_tables, n_eos_sets};
+  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                       workspace_bytes, poll_every, stream, self_kv_fp8, "mh_t5_generate_rows", &rowset);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@ from typing import Callable, Optional
 
 import torch
 
-from .server import _build_generation_stats, build_sampling
+from .server import _build_generation_stats, build_row_sampling, build_sampling, row_call_key
 from .t5_engine import HostStager, require_bf16_for_self_kv_fp8
 
 
@@ -54,7 +54,7 @@ def _left_pad(rows, pad_id: int, dtype):
 
 
 class SequentialWindowScheduler:
-    def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32):
+    def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32, merge_kwargs: bool = False):
         if decode_batch > 64 or decode_batch < 1:
             raise ValueError("decode_batch must be in [1, 64] (32 at most when windows run under classifier-free guidance)")
         self.model, self.tokenizer = model, tokenizer
@@ -62,6 +62,10 @@ class SequentialWindowScheduler:
         self.encode_batch, self.decode_batch = int(encode_batch), int(decode_batch)
         self.stats = dict(windows=0, decode_calls=0, encode_calls=0, generated_tokens=0, elapsed_seconds=0.0)
         self._seed_calls: dict = {}       # explicit seed -> decode calls made with it BY THIS scheduler
+        # merge_kwargs (off by default: the reference's grouping): the kwargs groups of a wave that agree in the per-call settings
+        # (server.row_call_key) decode as ONE call, every row under its own settings (T5Engine.decode(row_sampling=)); a wave
+        # whose first / last windows carry other EOS windows than the rest is then one decode call, not two or three
+        self.merge_kwargs = bool(merge_kwargs)
 
     # ---- stage 1: everything that depends on the audio only ------------------------------------------------
     @torch.no_grad()
@@ -146,6 +150,9 @@ class SequentialWindowScheduler:
                 gk = dict(jobs[i].generate_kwargs, **ask.pop("generate_kwargs", {}))
                 key = repr(sorted(gk.items(), key=lambda kv_: kv_[0]))
                 asks.setdefault(key, []).append((i, ask, gk))
+            if self.merge_kwargs:
+                self._run_wave_merged(jobs, kvs, w, asks, pad_id)
+                continue
             for group in asks.values():
                 # guidance doubles the decode batch (negative rows + prompt rows): half as many windows per call
                 step = max(1, self.decode_batch // 2) if float(group[0][2].get("cfg_scale", 1.0)) > 1.0 else self.decode_batch
@@ -156,18 +163,59 @@ class SequentialWindowScheduler:
         self.stats["elapsed_seconds"] += time.perf_counter() - start
         return self.stats
 
-    def _decode_group(self, jobs, kvs, w, group, pad_id):
-        eng, tok = self.engine, self.tokenizer
+    def _run_wave_merged(self, jobs, kvs, w, asks, pad_id):
+        """merge_kwargs: the groups of one wave, cut into the calls the default policy would make (so every window keeps the seed
+        and the RNG row of its own group's call), then joined per `row_call_key` into calls of up to decode_batch rows.  Groups
+        with beams have no row form and decode as they do by default; so does a group whose `max_length` cannot hold the widest
+        prompt of the call it would join (a cap counts COLUMNS, the left padding included: the group would fail a call it passes
+        among its own prompts)."""
+        keys = {k: row_call_key(dict(group[0][2], conditional_temperature_per_row=True)) for k, group in asks.items()}
+        width = {}                            # per call key: the widest prompt among the groups that could share a call
+        for k, group in asks.items():
+            width[keys[k]] = max([width.get(keys[k], 0)] + [ask["decoder_input_ids"].shape[-1] for _, ask, _ in group])
+        merged = {}
+        for k, group in asks.items():
+            gk0 = group[0][2]
+            guided = float(gk0.get("cfg_scale", 1.0)) > 1.0
+            step = max(1, self.decode_batch // 2) if guided else self.decode_batch
+            step = max(1, step // max(1, int(gk0.get("num_beams", 1) or 1)))
+            alone = keys[k] is None or (gk0.get("max_length") is not None and int(gk0["max_length"]) <= width[keys[k]])
+            for a in range(0, len(group), step):
+                if alone:
+                    self._decode_group(jobs, kvs, w, group[a:a + step], pad_id)
+                    continue
+                gk = self._call_kwargs(gk0)   # (one seed call index per call the default policy makes, in its order)
+                merged.setdefault(keys[k], []).extend((i, ask, gk, gk0) for i, ask, _ in group[a:a + step])
+        for rows in merged.values():
+            step = max(1, self.decode_batch // 2) if float(rows[0][2].get("cfg_scale", 1.0)) > 1.0 else self.decode_batch
+            for a in range(0, len(rows), step):
+                self._decode_group(jobs, kvs, w, rows[a:a + step], pad_id, merged=True)
+
+    def _call_kwargs(self, gk0: dict) -> dict:
+        """the kwargs of one decode call of a group"""
         # rows of different songs share this batch where the reference runs one batch-1 call per window: the conditional
         # temperature must look at each row's OWN history (the reference's processor reads row 0 of its batch)
-        gk = dict(group[0][2], conditional_temperature_per_row=True)
+        gk = dict(gk0, conditional_temperature_per_row=True)
         if gk.get("seed") is not None and gk.get("seed_call_index") is None:
             # explicit seed: the n-th decode call of THIS scheduler with that seed draws from stream (seed, n) -- the count is
             # the scheduler's own, so a run reproduces whatever else samples in the process (server.fresh_seed)
             n = self._seed_calls.get(gk["seed"], 0)
             self._seed_calls[gk["seed"]] = n + 1
             gk["seed_call_index"] = n
-        sp, eos = build_sampling(tok, gk, self.model.config.max_target_positions)
+        return gk
+
+    def _decode_group(self, jobs, kvs, w, group, pad_id, merged: bool = False):
+        """merged: every entry of `group` is (job, ask, the kwargs of ITS call, its group's kwargs) (`_run_wave_merged`), the rows
+        decode under their own"""
+        eng, tok = self.engine, self.tokenizer
+        row_sampling = None
+        if merged:
+            gk = group[0][2]               # (the per-call settings agree over the rows)
+            row_sampling = build_row_sampling(tok, [g[2] for g in group], self.model.config.max_target_positions)
+            sp, eos = row_sampling[0], []
+        else:
+            gk = self._call_kwargs(group[0][2])
+            sp, eos = build_sampling(tok, gk, self.model.config.max_target_positions)
         cfg = sp.cfg_scale > 1.0
         nb = int(getattr(sp, "num_beams", 1) or 1)
         if gk.get("self_kv_fp8"):   # (a window's own generate_kwargs may switch the mode on: the same refusals)
@@ -202,7 +250,7 @@ class SequentialWindowScheduler:
         t0 = time.perf_counter()
         eng._enter()
         with eng.on_stream():
-            kv = torch.stack([kvs[i][:, :, w] for i, _, _ in group], 2).contiguous()   # rows of this wave, gathered
+            kv = torch.stack([kvs[g[0]][:, :, w] for g in group], 2).contiguous()   # rows of this wave, gathered
             p_all = torch.cat([neg, prompts], 0) if cfg else prompts
             m_all = None if masks is None else (torch.cat([masks, masks], 0) if cfg else masks)
             # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search
@@ -210,6 +258,8 @@ class SequentialWindowScheduler:
             kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") and nb == 1 else None
             # generate_kwargs["self_kv_fp8"]: the token steps attend the engine's e4m3 shadow of the self-attention cache (no beams)
             skv8 = dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {}
+            if merged:   # every row under its own settings (mh_t5_generate_rows); eos_table is ignored there
+                skv8["row_sampling"] = row_sampling
             if nb == 1:
                 tokens, n_out, _ = eng.decode(kv, p_all.to(dev, torch.int32).contiguous(),
                                               None if m_all is None else m_all.to(dev).contiguous(),
@@ -232,16 +282,22 @@ class SequentialWindowScheduler:
         self.stats["decode_calls"] += 1
         P = prompts.shape[1]
         redo = {}
-        for r, (i, ask, _) in enumerate(group):
+        for r, (i, ask, *_) in enumerate(group):
             own = ask["decoder_input_ids"].shape[-1]
             row = result[r, P - own:]                      # strip the padding this batch added on the left
             # a row that finished early carries pad_id up to the batch's longest row: cut after its first EOS-set id,
             # which is where a batch-1 call for this window would have ended
             body = row[own:]
+            cap = sp.max_length
+            if merged:                                     # the row's own EOS set and cap
+                eos_ids = row_sampling[2][row_sampling[1][r].eos_set].nonzero().reshape(-1)
+                cap = row_sampling[1][r].max_length
+                if row.shape[0] > cap - (P - own):         # (columns past the row's cap hold pad_id)
+                    row, body = row[:cap - (P - own)], row[own:cap - (P - own)]
             hit = torch.isin(body, eos_ids).nonzero()
             if hit.numel():
                 row = row[:own + int(hit[0]) + 1]
-            elif own < P and row.shape[0] < sp.max_length:
+            elif own < P and row.shape[0] < cap:
                 # no EOS and the row stopped at max_length COLUMNS, `P - own` of which were this batch's left padding: the
                 # reference's batch-1 call (no padding) would have gone on to max_length tokens.  Rare (windows end by
                 # EOS); such rows are decoded again among rows of their own prompt length, i.e. without padding.
@@ -253,7 +309,16 @@ class SequentialWindowScheduler:
             self.stats["generated_tokens"] += st["generated_tokens"]
             jobs[i].on_result(w, row, st)
         for sub in redo.values():
-            self._decode_group(jobs, kvs, w, sub, pad_id)
+            if not merged:
+                self._decode_group(jobs, kvs, w, sub, pad_id)
+                continue
+            # a redo decodes as the default policy's does: the rows of one group and one prompt length by themselves, under the
+            # group's kwargs with the next seed call index and the RNG rows of that call
+            again = {}
+            for i, ask, _, gk0 in sub:
+                again.setdefault(repr(sorted(gk0.items(), key=lambda kv_: kv_[0])), []).append((i, ask, gk0))
+            for rows in again.values():
+                self._decode_group(jobs, kvs, w, rows, pad_id)
 
 
 # ---- the reference's own sequential loop on the scheduler -------------------------------------------------------------

@@ -154,6 +154,16 @@ def reset_seed_calls() -> None:
         _SEED_CALLS.clear()
 
 
+def _conditional_rules(tokenizer, temperature, timing_t, mania_t, taiko_t):
+    """ConditionalTemperatureLogitsWarper's rules as the reference keeps them (logit_processors.py:59-73): [(slot, temperature,
+    token ids, offset)] over the slots 0 timing, 1 mania column, 2 taiko hit, without those whose temperature equals the base
+    one or whose token set this tokenizer does not have."""
+    return [(slot, t, ids, off) for slot, (t, ids, off) in enumerate(((timing_t, get_beat_type_tokens(tokenizer), 1),
+                                                                      (mania_t, get_mania_type_tokens(tokenizer), 3),
+                                                                      (taiko_t, get_scroll_speed_tokens(tokenizer), 1)))
+            if t != temperature and len(ids) > 0]
+
+
 def build_sampling(tokenizer, generate_kwargs: dict, max_target_positions: int):
     """Translate the reference's generate kwargs (processor.py:156-170,358-360) into MhSampling + EOS ids."""
     gk = dict(generate_kwargs)
@@ -179,14 +189,9 @@ def build_sampling(tokenizer, generate_kwargs: dict, max_target_positions: int):
     need_flags = False
     if types_first:
         # ConditionalTemperatureLogitsWarper (logit_processors.py:59-73): (temperature, token set, offset) rules
-        rules = []
-        for t, ids, off in ((timing_t, get_beat_type_tokens(tokenizer), 1),
-                            (mania_t, get_mania_type_tokens(tokenizer), 3),
-                            (taiko_t, get_scroll_speed_tokens(tokenizer), 1)):
-            if t != temperature and len(ids) > 0:
-                rules.append((t, ids, off))
+        rules = _conditional_rules(tokenizer, temperature, timing_t, mania_t, taiko_t)
         sp.n_cond = len(rules)
-        for j, (t, ids, off) in enumerate(rules):
+        for j, (_, t, ids, off) in enumerate(rules):
             sp.cond_temp[j], sp.cond_offset[j] = float(t), int(off)
             flags[np.asarray(ids, dtype=np.int64)] |= FLAG_COND0 << j
             need_flags = True
@@ -233,6 +238,108 @@ def build_sampling(tokenizer, generate_kwargs: dict, max_target_positions: int):
     eos = get_eos_token_id(tokenizer, lookback_time=lookback_time, lookahead_time=lookahead_time,
                            context_type=context_type)
     return sp, eos
+
+
+# what one decode call has once for all its rows (include/mapperhip.h, mh_t5_generate_rows): name -> value of a kwargs dict
+_ROW_CALL_KEYS = {
+    "do_sample": lambda gk: bool(gk.get("do_sample", False)),
+    "cfg_scale": lambda gk: gk.get("cfg_scale", 1.0) > 1.0,                       # guided against unguided
+    "types_first": lambda gk: bool(gk.get("types_first", False)),
+    "num_beams": lambda gk: int(gk.get("num_beams", 1) or 1),
+    "pad_token_id": lambda gk: gk.get("pad_token_id"),
+    "cross_kv_fp8": lambda gk: bool(gk.get("cross_kv_fp8", False)),
+    "self_kv_fp8": lambda gk: bool(gk.get("self_kv_fp8", False)),
+    "precision": lambda gk: gk.get("precision"),
+    "conditional_temperature_per_row": lambda gk: bool(gk.get("conditional_temperature_per_row", False)),
+}
+
+
+def row_call_key(generate_kwargs: dict):
+    """The per-call part of one row's kwargs: rows whose keys are equal (and without beams) can share a row-settings decode call;
+    None for what never merges (num_beams != 1)."""
+    if _ROW_CALL_KEYS["num_beams"](generate_kwargs) != 1:
+        return None
+    return tuple(f(generate_kwargs) for f in _ROW_CALL_KEYS.values())
+
+
+def _kwargs_key(generate_kwargs: dict) -> str:
+    return repr(sorted(generate_kwargs.items(), key=lambda kv: kv[0]))
+
+
+def build_row_sampling(tokenizer, generate_kwargs_list, max_target_positions: int):
+    """One kwargs dict per RETURNED row -> `(sp, rows, eos_tables)` for `T5Engine.decode(..., row_sampling=)` / `mh_t5_generate_rows`:
+    `sp` the per-call settings (a `Sampling`; `max_length` the largest cap, the conditional rules and `tok_flags` those of all rows
+    together), `rows` a ctypes array of `MhRowSampling`, `eos_tables` uint8 (n_sets, vocab_out) with equal EOS sets stored once.
+    Built from `build_sampling` per distinct dict: rows with equal kwargs are one group -- one `build_sampling` call, hence one seed,
+    and `rng_row = rng_row_offset + index in the group`, which is what a uniform call of that group alone draws with.  For a
+    list of equal dicts the result describes exactly the call `build_sampling` describes.  Rows that differ in a per-call setting
+    (do_sample, guided against unguided, types_first, pad_token_id, the fp8 modes, precision, conditional_temperature_per_row), or
+    any row with beams, raise ValueError naming the key."""
+    entries = [dict(gk) for gk in generate_kwargs_list]
+    if not entries:
+        raise ValueError("build_row_sampling: no rows")
+    for gk in entries:
+        if _ROW_CALL_KEYS["num_beams"](gk) != 1:
+            raise ValueError(f"build_row_sampling: num_beams={gk.get('num_beams')}: beam search has no row-settings form")
+    for name, f in _ROW_CALL_KEYS.items():
+        for r, gk in enumerate(entries):
+            if f(gk) != f(entries[0]):
+                raise ValueError(f"build_row_sampling: row {r} differs from row 0 in the per-call setting {name!r} "
+                                 f"({gk.get(name)!r} vs {entries[0].get(name)!r}): such rows need calls of their own")
+    built, member = {}, []                                   # distinct kwargs -> [sp, eos ids, rule slots, rows so far]
+    for gk in entries:
+        k = _kwargs_key(gk)
+        if k not in built:
+            sp_e, eos_e = build_sampling(tokenizer, gk, max_target_positions)
+            t = gk.get("temperature", 1.0)
+            slots = {}
+            if gk.get("types_first", False):
+                slots = {slot: (rt, ids, off) for slot, rt, ids, off in _conditional_rules(
+                    tokenizer, t, gk.get("timing_temperature", t), gk.get("mania_column_temperature", t), gk.get("taiko_hit_temperature", t))}
+            built[k] = [sp_e, eos_e, slots, 0]
+        member.append((k, built[k][3]))
+        built[k][3] += 1
+    # the call's rules: every slot some row has, in the reference's order; rule j's token set is bit FLAG_COND0 << j for every row
+    call_slots = sorted({slot for b in built.values() for slot in b[2]})
+    vocab = int(tokenizer.vocab_size_out)
+    eos_index, tables = {}, []
+    rows = (_lib.MhRowSampling * len(entries))()
+    for r, (k, idx) in enumerate(member):
+        sp_e, eos_e, slots, _ = built[k]
+        ids = tuple(sorted(set(int(e) for e in eos_e if 0 <= int(e) < vocab)))
+        if ids not in eos_index:
+            eos_index[ids] = len(tables)
+            tables.append(ids)
+        row = rows[r]
+        row.temperature, row.top_k, row.top_p = sp_e.temperature, sp_e.top_k, sp_e.top_p
+        row.timeshift_bias, row.lookback_mask_end, row.max_length = sp_e.timeshift_bias, sp_e.lookback_mask_end, sp_e.max_length
+        row.eos_set, row.seed, row.rng_row, row.cfg_scale = eos_index[ids], sp_e.seed, (sp_e.rng_row0 + idx) & 0xFFFFFFFF, sp_e.cfg_scale
+        for j, slot in enumerate(call_slots):
+            row.cond_temp[j] = float(slots[slot][0]) if slot in slots else sp_e.temperature
+            if slot in slots:                              # a rule the reference drops for this row stays masked out
+                row.cond_mask |= 1 << j
+    eos_tables = torch.zeros((len(tables), vocab), dtype=torch.uint8)
+    for i, ids in enumerate(tables):
+        eos_tables[i, torch.as_tensor(ids, dtype=torch.long)] = 1
+    firsts = list(built.values())
+    sp = firsts[0][0]
+    flags = np.zeros(vocab, dtype=np.uint8)
+    need_flags = False
+    for sp_e, _, _, _ in firsts:
+        if sp_e.host_tok_flags is not None:
+            flags |= sp_e.host_tok_flags & np.uint8(FLAG_TIMED | FLAG_LOOKBACK_EOS)
+            need_flags = True
+    sp.n_cond = len(call_slots)
+    for j, slot in enumerate(call_slots):
+        _, ids, off = next(b[2][slot] for b in firsts if slot in b[2])
+        sp.cond_temp[j], sp.cond_offset[j] = rows[0].cond_temp[j], int(off)
+        flags[np.asarray(ids, dtype=np.int64)] |= FLAG_COND0 << j
+    for j in range(len(call_slots), 3):
+        sp.cond_temp[j], sp.cond_offset[j] = 0.0, 0
+    sp.host_tok_flags = flags if need_flags else None
+    sp.lookback_types_first = int(any(b[0].lookback_types_first for b in firsts))
+    sp.max_length = max(b[0].max_length for b in firsts)
+    return sp, rows, eos_tables
 
 
 def sampling_from_processors(processors, vocab_size_out: int, *, do_sample=False, top_k=0, top_p=1.0, max_length: int,
@@ -302,19 +409,58 @@ def sampling_from_processors(processors, vocab_size_out: int, *, do_sample=False
     return sp
 
 
+def _conditioning_bias(model, model_kwargs):
+    cond = getattr(model, "cond", None)
+    if cond is None or not cond.active:
+        return None
+    vec = cond.vectors(model_kwargs["inputs"].shape[0], beatmap_idx=model_kwargs.get("beatmap_idx"),
+                       difficulty=model_kwargs.get("difficulty"), mapper_idx=model_kwargs.get("mapper_idx"),
+                       song_position=model_kwargs.get("song_position"))
+    return cond.channels(vec, model.dtype) if cond.as_channels else cond.row_bias(vec, model.dtype)
+
+
+@torch.no_grad()
+def model_generate_rows(model, tokenizer, model_kwargs, generate_kwargs_list):
+    """`model_generate` for rows that do not share their generate kwargs: `generate_kwargs_list[r]` belongs to row r of the batch,
+    and the rows decode as ONE call under their own settings (`build_row_sampling`; no reference counterpart -- the reference and
+    `model_generate` take one kwargs set per call).  Each row's ids are those of a `model_generate` call made of the rows that
+    share its kwargs.  Same result and stats as `model_generate`; the rows must agree in the per-call settings."""
+    sp, rows, eos_tables = build_row_sampling(tokenizer, generate_kwargs_list, model.config.max_target_positions)
+    if sp.max_length > model.config.max_target_positions:
+        raise ValueError(f"max_length {sp.max_length} exceeds max_target_positions {model.config.max_target_positions}")
+    gk0 = generate_kwargs_list[0]
+    if len(generate_kwargs_list) != model_kwargs["decoder_input_ids"].shape[0]:
+        raise ValueError(f"{len(generate_kwargs_list)} generate kwargs for {model_kwargs['decoder_input_ids'].shape[0]} rows")
+    pad_token_id = gk0.get("pad_token_id", getattr(tokenizer, "pad_id", None))
+    neg = model_kwargs.get("negative_prompt")
+    if sp.cfg_scale > 1.0 and neg is None:
+        raise ValueError("cfg_scale > 1 needs model_kwargs['negative_prompt'] (modeling_mapperatorinator.py:243-254)")
+    if sp.cfg_scale <= 1.0:
+        neg = None
+    kv_fp8 = bool(gk0.get("cross_kv_fp8", False))
+    if kv_fp8:
+        require_bf16_for_cross_kv_fp8(model.dtype)
+    extra = {}
+    row_bias = _conditioning_bias(model, model_kwargs)
+    if row_bias is not None:
+        extra["row_bias"] = row_bias
+    if gk0.get("self_kv_fp8", False):
+        require_bf16_for_self_kv_fp8(model.dtype, 1)
+        extra["self_kv_fp8"] = True
+    start = time.perf_counter()
+    out = model.engine.generate(model_kwargs["inputs"], model_kwargs["decoder_input_ids"], model_kwargs.get("decoder_attention_mask"),
+                                None, sp, negative_prompt=neg, cross_kv_fp8=kv_fp8, row_sampling=(sp, rows, eos_tables), **extra)
+    result = out["tokens"]
+    return result, _build_generation_stats(result, model_kwargs, pad_token_id, time.perf_counter() - start)
+
+
 @torch.no_grad()
 def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     """See module docstring.  `model_kwargs['inputs']`: raw audio float32 (B, Ns)."""
     generate_kwargs = dict(generate_kwargs)
     # conditioning inputs (modeling_mapperatorinator.py:174-228): used when the model carries the embedders, ignored
     # otherwise -- exactly the reference's `if self.do_*_embed` switches
-    cond = getattr(model, "cond", None)
-    row_bias = None
-    if cond is not None and cond.active:
-        vec = cond.vectors(model_kwargs["inputs"].shape[0], beatmap_idx=model_kwargs.get("beatmap_idx"),
-                           difficulty=model_kwargs.get("difficulty"), mapper_idx=model_kwargs.get("mapper_idx"),
-                           song_position=model_kwargs.get("song_position"))
-        row_bias = cond.channels(vec, model.dtype) if cond.as_channels else cond.row_bias(vec, model.dtype)
+    row_bias = _conditioning_bias(model, model_kwargs)
     audio = model_kwargs["inputs"]
     prompt = model_kwargs["decoder_input_ids"]
     mask = model_kwargs.get("decoder_attention_mask")
@@ -416,9 +562,13 @@ class RequestBatcher:
     below 32 rows (decode), so smaller batches only lose throughput.  64 rows (the engine's maximum: two 32-row
     chains) decode 14 % more tokens per second at 1.75 x the per-token latency (profiles/r06_small_batch_decode.txt)."""
 
-    def __init__(self, model, tokenizer, max_batch_size: int = 32, generate_fn=None):
+    def __init__(self, model, tokenizer, max_batch_size: int = 32, generate_fn=None, merge_kwargs: bool = False):
         self.model, self.tokenizer, self.max_batch_size = model, tokenizer, int(max_batch_size)
-        self.generate_fn = generate_fn or model_generate
+        # merge_kwargs (not the reference's policy, off by default): a batch that has room left after the first group goes on
+        # through the groups that agree with it in the per-call settings (`row_call_key`); `generate_fn` then receives a LIST of
+        # kwargs, one per row (`model_generate_rows`: one decode call, every row under its own settings)
+        self.merge_kwargs = bool(merge_kwargs)
+        self.generate_fn = generate_fn or (model_generate_rows if self.merge_kwargs else model_generate)
         self.grouped_requests: dict = {}
         self.prefetch = True          # start the next batch's H2D before this batch decodes (HIP engine only)
         self._staged, self._stager = None, None
@@ -445,7 +595,6 @@ class RequestBatcher:
         if not self.grouped_requests:
             return None
         key = next(iter(self.grouped_requests))
-        requests = self.grouped_requests[key]
         generate_kwargs = dict(key)
         cfg_scale, num_beams = generate_kwargs.get("cfg_scale", 1.0), generate_kwargs.get("num_beams", 1)
         multiplier = 2 * num_beams if cfg_scale > 1 else num_beams
@@ -453,6 +602,35 @@ class RequestBatcher:
         if room <= 0:
             raise ValueError(f"max_batch_size {self.max_batch_size} holds no row at batch multiplier {multiplier}")
         batch = []
+        room = self._take_from(key, room, batch)
+        if self.merge_kwargs:
+            per_row = [generate_kwargs] * sum(b[2] for b in batch)
+            call_key = row_call_key(generate_kwargs)
+
+            def prompt_width(model_kwargs):
+                ids = model_kwargs.get("decoder_input_ids")
+                return int(ids.shape[-1]) if isinstance(ids, torch.Tensor) else 0
+            # a cap counts COLUMNS of the collated batch, the left padding included: a group joins only while every group's
+            # max_length still holds the widest prompt (one that does not would fail a batch it passes among its own requests)
+            width = max(prompt_width(b[0]) for b in batch)
+            cap = float(generate_kwargs.get("max_length") or "inf")
+            for other in list(self.grouped_requests) if call_key is not None else ():
+                gk = dict(other)
+                if room > 0 and row_call_key(gk) == call_key:
+                    w_o = max([width] + [prompt_width(r["model_kwargs"]) for r in self.grouped_requests[other]])
+                    c_o = min(cap, float(gk.get("max_length") or "inf"))
+                    if not w_o < c_o:
+                        continue
+                    width, cap = w_o, c_o
+                    n = len(batch)
+                    room = self._take_from(other, room, batch)
+                    per_row += [gk] * sum(b[2] for b in batch[n:])
+            return per_row, batch
+        return generate_kwargs, batch
+
+    def _take_from(self, key, room: int, batch: list) -> int:
+        """move whole or partial requests of group `key` into `batch` until `room` rows are filled; returns the room left"""
+        requests = self.grouped_requests[key]
         while room > 0 and requests:
             req = requests.pop(0)
             left = req["total_work"] - req["work_taken"]       # rows not yet handed to a batch (the batch before this one
@@ -464,7 +642,7 @@ class RequestBatcher:
                 requests.insert(0, req)            # the rest of it leads the next batch
         if not requests:
             del self.grouped_requests[key]
-        return generate_kwargs, batch
+        return room
 
     def _collate(self, batch):
         keys = [k for k, v in batch[0][0].items() if v is not None]
@@ -508,10 +686,23 @@ class RequestBatcher:
         self._staged = self._stage(self._take_batch())
         if ev is not None:
             torch.cuda.current_stream(collated["inputs"].device).wait_event(ev)
-        if generate_kwargs.get("seed") is not None and generate_kwargs.get("seed_call_index") is None:
-            n = self._seed_calls.get(generate_kwargs["seed"], 0)
-            self._seed_calls[generate_kwargs["seed"]] = n + 1
-            generate_kwargs = dict(generate_kwargs, seed_call_index=n)
+        if isinstance(generate_kwargs, list):      # merge_kwargs: one dict per row; each group counts its seed as a batch of its own
+            counted = {}
+            for gk in generate_kwargs:
+                if id(gk) not in counted:
+                    counted[id(gk)] = gk
+                    if gk.get("seed") is not None and gk.get("seed_call_index") is None:
+                        n = self._seed_calls.get(gk["seed"], 0)
+                        self._seed_calls[gk["seed"]] = n + 1
+                        counted[id(gk)] = dict(gk, seed_call_index=n)
+            generate_kwargs = [counted[id(gk)] for gk in generate_kwargs]
+            first_kwargs = generate_kwargs[0]
+        else:
+            if generate_kwargs.get("seed") is not None and generate_kwargs.get("seed_call_index") is None:
+                n = self._seed_calls.get(generate_kwargs["seed"], 0)
+                self._seed_calls[generate_kwargs["seed"]] = n + 1
+                generate_kwargs = dict(generate_kwargs, seed_call_index=n)
+            first_kwargs = generate_kwargs
         try:
             outputs, stats = self.generate_fn(self.model, self.tokenizer, collated, generate_kwargs)
         except BaseException as e:
@@ -533,7 +724,7 @@ class RequestBatcher:
                 # parts of one request decoded in different batches can stop at different lengths; the reference's
                 # torch.cat raises here (and its client retries): widen with the pad id finished rows already carry
                 width = max(req["result"].shape[1], out.shape[1])
-                fill = generate_kwargs.get("pad_token_id", getattr(self.tokenizer, "pad_id", 0))
+                fill = first_kwargs.get("pad_token_id", getattr(self.tokenizer, "pad_id", 0))
                 req["result"] = torch.nn.functional.pad(req["result"], (0, width - req["result"].shape[1]), value=fill)
                 out = torch.nn.functional.pad(out, (0, width - out.shape[1]), value=fill)
             req["result"] = out if req["result"] is None else torch.cat((req["result"], out), dim=0)

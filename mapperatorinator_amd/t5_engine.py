@@ -426,18 +426,47 @@ class T5Engine:
     def decode(self, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
                eos_table: torch.Tensor, sampling: _lib.MhSampling, forced: Optional[torch.Tensor] = None,
                dump_logits: bool = False, poll_every: int = 16, kv_fp8: Optional[torch.Tensor] = None,
-               self_kv_fp8: bool = False):
+               self_kv_fp8: bool = False, row_sampling=None):
         """prompt int32 (B, P) on device.  Returns (tokens int32 (B, max_length) device, n_cols int, logits|None).
         Under CFG (sampling.cfg_scale > 1) the B rows are [negative-prompt rows | prompt rows], `cross_kv` holds
         B/2 rows and the logits dump has B/2 rows (the guided scores).
         `self_kv_fp8`: the token steps attend an e4m3 shadow of the self-attention cache (`mh_t5_generate_skv8`, contract in
         include/mapperhip.h: one fp32 scale per cached row, the step's own key / value at storage precision, the prompt prefill
-        unchanged and quantised in one pass).  The shadow is this engine's, kept like the workspaces.  bf16 storage only."""
+        unchanged and quantised in one pass).  The shadow is this engine's, kept like the workspaces.  bf16 storage only.
+        `row_sampling`: what `server.build_row_sampling` returned -- `(sp, rows, eos_tables)`, or its `(rows, eos_tables)` -- decodes
+        through `mh_t5_generate_rows`: one `MhRowSampling` per returned row and one EOS table per distinct EOS set (the lists of
+        per-row and per-call settings: include/mapperhip.h); `sampling` carries the per-call settings and `eos_table` is ignored
+        (may be None).  The device copies live in this engine's buffers, so their pointers -- part of the step graph's key -- do not
+        move from call to call."""
         if self_kv_fp8:
             require_bf16_for_self_kv_fp8(self.dtype)
         p = self.packed
         B, P = prompt.shape
         cfg = sampling.cfg_scale > 1.0
+        row_args = None
+        if row_sampling is not None:
+            rows, eos_tables = row_sampling[-2], row_sampling[-1]
+            n_ret = B // 2 if cfg else B
+            if len(rows) != n_ret:
+                raise ValueError(f"row_sampling holds {len(rows)} rows for {n_ret} returned rows (batch {B}, cfg={cfg})")
+            eos_tables = torch.as_tensor(eos_tables, dtype=torch.uint8).reshape(-1, p.vocab_out).contiguous()
+            n_sets = int(eos_tables.shape[0])
+            bad = [r for r in range(n_ret) if not 0 <= rows[r].eos_set < n_sets or not P < rows[r].max_length <= sampling.max_length
+                   or not rows[r].temperature > 0]
+            if bad:
+                raise ValueError(f"row_sampling: row {bad[0]} is out of range (eos_set in [0, {n_sets}), prompt length {P} < max_length "
+                                 f"<= {sampling.max_length}, temperature > 0)")
+            if n_sets > 64:
+                raise ValueError(f"row_sampling: {n_sets} EOS sets (a decode batch has 64 rows at most, hence 64 distinct sets)")
+            # 64 entries and 64 tables (the largest decode batch), allocated once: neither pointer ever moves, and the library is
+            # told the buffer's 64 sets whatever the call uses (its clamp guards the buffer, the check above the call's own range),
+            # so neither the pointers nor the count -- all three in the step graph's key -- change with the mix
+            rows_d = self._workspace("row_sampling", 64 * C.sizeof(_lib.MhRowSampling))
+            eos_d = self._workspace("row_eos_tables", 64 * p.vocab_out)
+            host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
+            rows_d[:host.numel()].copy_(host)
+            eos_d[:eos_tables.numel()].copy_(eos_tables.reshape(-1))
+            row_args = (rows_d.data_ptr(), eos_d.data_ptr(), 64)
         if cross_kv.shape[2] != (B // 2 if cfg else B):
             raise ValueError(f"cross_kv holds {cross_kv.shape[2]} rows for a decode batch of {B} (cfg={cfg})")
         flags = getattr(sampling, "host_tok_flags", None)
@@ -455,10 +484,13 @@ class T5Engine:
         logits = (torch.zeros((maxlen, B // 2 if cfg else B, p.vocab_out), dtype=torch.float32, device=self.device)
                   if dump_logits else None)
         args = (C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), B, prompt.data_ptr(),
-                _lib.ptr(prompt_mask), P, eos_table.data_ptr(), C.byref(sampling),
+                _lib.ptr(prompt_mask), P, _lib.ptr(eos_table), C.byref(sampling),
                 tokens.data_ptr(), n_out.data_ptr(), _lib.ptr(logits), _lib.ptr(forced),
                 ws.data_ptr(), ws.numel(), poll_every, self._s())
-        if self_kv_fp8:
+        if row_args is not None:
+            skv8 = self._workspace("skv8", self.lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), B)) if self_kv_fp8 else None
+            _lib.check(self.lib.mh_t5_generate_rows(*args, _lib.ptr(skv8), *row_args), "mh_t5_generate_rows")
+        elif self_kv_fp8:
             skv8 = self._workspace("skv8", self.lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), B))
             _lib.check(self.lib.mh_t5_generate_skv8(*args, skv8.data_ptr()), "mh_t5_generate_skv8")
         else:
@@ -534,8 +566,9 @@ class T5Engine:
                  dump_logits: bool = False, poll_every: int = 16, negative_prompt: Optional[torch.Tensor] = None,
                  negative_mask: Optional[torch.Tensor] = None, cross_kv_fp8: bool = False,
                  row_bias: Optional[torch.Tensor] = None, encoder_states: Optional[torch.Tensor] = None,
-                 self_kv_fp8: bool = False):
-        """Full hot path for one batch of chunks.  `encoder_states` (B, src_len, d_model): the encoder's last_hidden_state given by
+                 self_kv_fp8: bool = False, row_sampling=None):
+        """Full hot path for one batch of chunks.  `row_sampling`: the result of `server.build_row_sampling` -- every row decodes under
+        its own settings (see `decode`); `sampling` is its first item and `eos_ids` is ignored.  `encoder_states` (B, src_len, d_model): the encoder's last_hidden_state given by
         the caller (`generate(encoder_outputs=...)` of the reference's signature) -- mel and encoder are skipped, `audio` may be None.  `cross_kv_fp8`: the token steps stream the e4m3 copy of the
         cross-attention K / V (see `cross_kv_fp8()`); `self_kv_fp8`: they attend the e4m3 shadow of the self-attention cache (see `decode`; the two
         compose to a whole fp8 K/V cache).  Inputs may be CPU tensors (copied like
@@ -576,7 +609,7 @@ class T5Engine:
         mask_d = prompt_mask.to(dev).to(torch.uint8).contiguous() if prompt_mask is not None else None
         forced_d = forced.to(dev, torch.int32).contiguous() if forced is not None else None
         eos_table = torch.zeros(self.packed.vocab_out, dtype=torch.uint8)
-        eos_table[torch.as_tensor(sorted(set(int(e) for e in eos_ids if 0 <= int(e) < self.packed.vocab_out)),
+        eos_table[torch.as_tensor(sorted(set(int(e) for e in (eos_ids or ()) if 0 <= int(e) < self.packed.vocab_out)),
                                   dtype=torch.long)] = 1
         eos_table = eos_table.to(dev)
         self._enter()
@@ -585,7 +618,7 @@ class T5Engine:
             kv = self.cross_kv(enc)
             kv8 = self.cross_kv_fp8(kv) if cross_kv_fp8 else None
             tokens, n_out, logits = self.decode(kv, prompt_d, mask_d, eos_table, sampling, forced_d, dump_logits,
-                                                poll_every, kv_fp8=kv8, self_kv_fp8=self_kv_fp8)
+                                                poll_every, kv_fp8=kv8, self_kv_fp8=self_kv_fp8, row_sampling=row_sampling)
         self._leave()
         torch.cuda.current_stream(dev).synchronize()
         n_cols = int(n_out.item()) if forced is None else sampling.max_length
