@@ -220,10 +220,62 @@ int mh_layernorm(const float* x, int ldx, const float* w, const float* b, void* 
  * out  [B*L, ld_out] element type `dtype`, head h at columns [h*64, h*64+64).
  * K7  also the DiT attention (osu_diffusion/utils/models.py:145-151): scale = 1/8, bias NULL and
  *     band > 0: query q attends key k iff -(band-1) <= k - q <= band, which is exactly the banded
- *     bool mask built at diffusion_pipeline.py:146-148 (band = seq_len = 128).  band <= 0: no mask. */
+ *     bool mask built at diffusion_pipeline.py:146-148 (band = seq_len = 128).  band = 0: no mask.
+ *     band < 0: the symmetric window |k - q| <= -band (the local layers of the Whisper family). */
 int mh_attention(const void* qk, int ld_qk, int k_col0, const void* vt, int Lpad, const float* bias,
                  void* out, int ld_out, int B, int L, int H, float scale, int band, int dtype,
                  void* stream);
+
+/* Test-facing entries of the attention kernels (additive at ABI 11: three symbols and one struct of their own; a library without
+ * them is an older 11).  They launch exactly what the models launch and add no kernel.
+ *
+ * mh_attention_packed: mh_attention with the two options the DiT blocks and the encoders pass internally:
+ *   open_from  > 0 with band != 0: positions >= open_from are padding -- key k is visible from query q iff it is in the band OR
+ *              k >= open_from OR q >= open_from (the DiT pipeline's pad_sequence); 0 = none;
+ *   out_split3 != 0 (fp32 only, ld_out % 32 == 0): every 32 output values are stored as [32 x bf16 hi | 32 x bf16 lo], the
+ *              pre-split A operand of MhGemm.w_split3 & 2 (a row still occupies ld_out * 4 bytes).
+ *
+ * mh_attention_strided: one problem in the strided form the decoder's prompt prefill and its cross-attention use.  All strides in
+ * BYTES and multiples of 16; head_dim = 64.  Key `key` is visible from query row `row` (qpos = q_pos0 + row) iff
+ *   key < Lk, and (key >= mask_len or key_mask[b * mask_ld + key] != 0; key_mask NULL: no mask), and
+ *   (band == 0, or the key is in the band -- band > 0: -(band-1) <= key - qpos <= band; band < 0: |key - qpos| <= -band -- or, with
+ *   open_from > 0, key >= open_from or qpos >= open_from), and (causal == 0 or key <= qpos).
+ * A visible key's score is scale * q.k + bias[h * bias_hs + bias_center + clamp(bias_sign * (key - qpos), bias_min, bias_max)]
+ * (bias NULL: none); a row without a visible key is written as zeros.  vt is V^T [B][H][64][Lkpad] with Lkpad % 64 == 0 and the
+ * pad columns zero.  Refused (MH_ERR_ARG): struct_bytes != sizeof(MhAttnProblem); a null q / k / vt / out; q_pos0 < 0; q_pos0 != 0
+ * together with band != 0 (the kernels pick their key tiles from the query index: no model combines the two); key_mask with
+ * mask_len <= 0 or mask_ld < mask_len; out_split3 with bf16.  A bf16 problem whose out / out_rs / out_bs is not 16-byte aligned
+ * runs the 64-query kernel with 2-byte stores instead of the 128-query one. */
+typedef struct MhAttnProblem {
+  int64_t struct_bytes;                        /* sizeof(MhAttnProblem) of the caller                                      */
+  const void* q; int64_t q_rs, q_bs;           /* + b*q_bs + row*q_rs + h*64*sizeof(T)                                     */
+  const void* k; int64_t k_rs, k_bs, k_hs;     /* + b*k_bs + h*k_hs + key*k_rs                                             */
+  const void* vt; int64_t vt_bs, vt_hs;        /* + b*vt_bs + h*vt_hs + d*Lkpad*sizeof(T)                                  */
+  const float* bias; int64_t bias_hs;
+  const uint8_t* key_mask;                     /* [B][mask_ld] bytes                                                       */
+  void* out; int64_t out_rs, out_bs;           /* + b*out_bs + row*out_rs + h*64*sizeof(T)                                 */
+  int Lkpad, bias_center, bias_sign, bias_min, bias_max, mask_ld, mask_len;
+  int Lq, Lk;
+  float scale;
+  int open_from, out_split3, band, causal, q_pos0;
+  int B, H, dtype;
+} MhAttnProblem;
+int mh_attention_packed(const void* qk, int ld_qk, int k_col0, const void* vt, int Lpad, const float* bias,
+                        void* out, int ld_out, int B, int L, int H, float scale, int band, int dtype,
+                        int open_from, int out_split3, void* stream);
+int mh_attention_strided(const MhAttnProblem* p, void* stream);
+/* The kernel the calling thread's last attention launch ran (host-only bookkeeping; MH_ATTN_NONE before the first one):
+ * MH_ATTN_FLASH2 carries two more bits, MH_ATTN_FLASH2_BIAS and MH_ATTN_FLASH2_SIMPLE, for its four compiled forms. */
+typedef enum MhAttnKernel {
+  MH_ATTN_NONE = 0,
+  MH_ATTN_FLASH_F32 = 1,   /* 64-query flash kernel, fp32                                         */
+  MH_ATTN_FLASH_BF16 = 2,  /* 64-query flash kernel, bf16 (outputs that are not 16-byte aligned)  */
+  MH_ATTN_SMALL_K2 = 3,    /* key-split fp32 kernel, L <= 128                                     */
+  MH_ATTN_SMALL_K4 = 4,    /* key-split fp32 kernel, L <= 256                                     */
+  MH_ATTN_FLASH2 = 8,      /* 128-query transposed-S bf16 kernel                                  */
+  MH_ATTN_FLASH2_BIAS = 1, MH_ATTN_FLASH2_SIMPLE = 2
+} MhAttnKernel;
+int mh_attention_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------------
  * K2  Whisper-style audio front-end (HF WhisperEncoder.forward prologue; reference forks

@@ -129,6 +129,25 @@ class MhSliderSet(C.Structure):
                 ("end_idx", VP), ("length", VP)]
 
 
+class MhAttnProblem(C.Structure):
+    """One strided attention problem of mh_attention_strided (byte strides; `struct_bytes` = C.sizeof(MhAttnProblem))."""
+    _fields_ = [("struct_bytes", C.c_int64),
+                ("q", VP), ("q_rs", C.c_int64), ("q_bs", C.c_int64),
+                ("k", VP), ("k_rs", C.c_int64), ("k_bs", C.c_int64), ("k_hs", C.c_int64),
+                ("vt", VP), ("vt_bs", C.c_int64), ("vt_hs", C.c_int64),
+                ("bias", VP), ("bias_hs", C.c_int64), ("key_mask", VP),
+                ("out", VP), ("out_rs", C.c_int64), ("out_bs", C.c_int64),
+                ("Lkpad", C.c_int), ("bias_center", C.c_int), ("bias_sign", C.c_int), ("bias_min", C.c_int),
+                ("bias_max", C.c_int), ("mask_ld", C.c_int), ("mask_len", C.c_int),
+                ("Lq", C.c_int), ("Lk", C.c_int), ("scale", C.c_float),
+                ("open_from", C.c_int), ("out_split3", C.c_int), ("band", C.c_int), ("causal", C.c_int), ("q_pos0", C.c_int),
+                ("B", C.c_int), ("H", C.c_int), ("dtype", C.c_int)]
+
+
+# mh_attention_last_kernel (MhAttnKernel)
+(ATTN_NONE, ATTN_FLASH_F32, ATTN_FLASH_BF16, ATTN_SMALL_K2, ATTN_SMALL_K4) = range(5)
+ATTN_FLASH2, ATTN_FLASH2_BIAS, ATTN_FLASH2_SIMPLE = 8, 1, 2
+
 ABI_VERSION = 11  # MH_ABI_VERSION of include/mapperhip.h
 
 # every symbol include/mapperhip.h declares: (name, restype, argtypes)
@@ -152,6 +171,9 @@ SYMBOLS = {
     "mh_quantize_mx8": (I, [VP, I, I, I, I, VP, I, VP, VP]),
     "mh_rmsnorm_mx8": (I, [VP, I, VP, I, I, F, I, VP, I, VP, VP]),
     "mh_attention": (I, [VP, I, I, VP, I, VP, VP, I, I, I, I, F, I, I, VP]),
+    "mh_attention_packed": (I, [VP, I, I, VP, I, VP, VP, I, I, I, I, F, I, I, I, I, VP]),
+    "mh_attention_strided": (I, [C.POINTER(MhAttnProblem), VP]),
+    "mh_attention_last_kernel": (I, []),
     "mh_whisper_frontend_workspace_bytes": (I64, [I, I, I, I, I]),
     "mh_whisper_frontend": (I, [VP, I, I, I, VP, VP, VP, VP, VP, I, VP, VP, I64, I, VP]),
     "mh_cond_channels": (I, [VP, I, I, I, I, VP, I, I, VP]),

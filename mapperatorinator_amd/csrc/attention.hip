@@ -744,6 +744,9 @@ __global__ __launch_bounds__(256) void transpose_v_kernel(const T* __restrict__ 
   }
 }
 
+// which kernel the calling thread's last attention launch ran (mh_attention_last_kernel: host-only, for tests)
+thread_local int tl_last_kernel = MH_ATTN_NONE;
+
 }  // namespace
 
 int attention_general(const AttnArgs& a, int B, int H, int dtype, hipStream_t s) {
@@ -762,6 +765,7 @@ int attention_general(const AttnArgs& a, int B, int H, int dtype, hipStream_t s)
     MH_REQUIRE(total < (1L << 30), "attention: too many workgroups");
     const int per_xcd = (int)((total + 7) / 8);
     const size_t smem = (size_t)4 * 64 * (64 * 2 + 16);        // two buffers of (K tile | V^T tile)
+    tl_last_kernel = MH_ATTN_FLASH2 | (a.bias ? MH_ATTN_FLASH2_BIAS : 0) | (simple ? MH_ATTN_FLASH2_SIMPLE : 0);
     if (a.bias && simple)
       hipLaunchKernelGGL((flash2_bf16_kernel<2, true, true>), dim3(8 * per_xcd), dim3(256), smem, s, a, nqt, H, (int)total);
     else if (a.bias)
@@ -774,6 +778,7 @@ int attention_general(const AttnArgs& a, int B, int H, int dtype, hipStream_t s)
   }
   dim3 grid(ceil_div(a.Lq, 64), H, B), block(256);
   const size_t smem = (size_t)(128 + 64) * (64 * es + 16);
+  tl_last_kernel = dtype == MH_BF16 ? MH_ATTN_FLASH_BF16 : MH_ATTN_FLASH_F32;
   if (dtype == MH_BF16)
     hipLaunchKernelGGL(flash_attn_kernel<bf16_t>, grid, block, smem, s, a);
   else
@@ -951,6 +956,7 @@ int attention(const void* qk, int ld_qk, int k_col0, const void* vt, int Lpad, c
     sp.ld_qk = ld_qk; sp.vt_hs = 64L * Lpad; sp.vt_bs = (long)H * 64 * Lpad; sp.ld_out = ld_out;
     sp.L = L; sp.Lpad = Lpad; sp.H = H; sp.band = band; sp.open_from = open_from; sp.out_split3 = out_split3; sp.scale = scale;
     dim3 grid(ceil_div(L, 16), H, B), block(256);
+    tl_last_kernel = L <= 128 ? MH_ATTN_SMALL_K2 : MH_ATTN_SMALL_K4;
     if (L <= 128) hipLaunchKernelGGL(attn_small_f32_kernel<2>, grid, block, 0, s, sp);
     else hipLaunchKernelGGL(attn_small_f32_kernel<4>, grid, block, 0, s, sp);
     return check_launch("attn_small_f32_kernel");
@@ -983,3 +989,36 @@ extern "C" int mh_attention(const void* qk, int ld_qk, int k_col0, const void* v
   return mh::attention(qk, ld_qk, k_col0, vt, Lpad, bias, out, ld_out, B, L, H, scale, band, dtype,
                        (hipStream_t)stream);
 }
+
+extern "C" int mh_attention_packed(const void* qk, int ld_qk, int k_col0, const void* vt, int Lpad, const float* bias,
+                                   void* out, int ld_out, int B, int L, int H, float scale, int band, int dtype,
+                                   int open_from, int out_split3, void* stream) {
+  MH_REQUIRE(dtype == MH_F32 || dtype == MH_BF16, "mh_attention_packed: dtype must be MH_F32 or MH_BF16");
+  return mh::attention(qk, ld_qk, k_col0, vt, Lpad, bias, out, ld_out, B, L, H, scale, band, dtype,
+                       (hipStream_t)stream, open_from, out_split3);
+}
+
+extern "C" int mh_attention_strided(const MhAttnProblem* p, void* stream) {
+  MH_REQUIRE(p, "mh_attention_strided: null problem");
+  MH_REQUIRE(p->struct_bytes == (int64_t)sizeof(MhAttnProblem), "mh_attention_strided: struct_bytes = %lld, this library's MhAttnProblem has %zu",
+             (long long)p->struct_bytes, sizeof(MhAttnProblem));
+  MH_REQUIRE(p->dtype == MH_F32 || p->dtype == MH_BF16, "mh_attention_strided: dtype must be MH_F32 or MH_BF16");
+  // the kernels choose their key tiles from the query INDEX: a band (and open_from with it) is only right at q_pos0 = 0
+  MH_REQUIRE(p->q_pos0 >= 0 && (p->q_pos0 == 0 || p->band == 0), "mh_attention_strided: q_pos0 = %d with band = %d: a band needs q_pos0 = 0",
+             p->q_pos0, p->band);
+  MH_REQUIRE(!p->key_mask || (p->mask_len > 0 && p->mask_ld >= p->mask_len), "mh_attention_strided: key_mask needs 0 < mask_len <= mask_ld");
+  MH_REQUIRE(!p->out_split3 || p->dtype == MH_F32, "mh_attention_strided: out_split3 is an fp32 path");
+  mh::AttnArgs a{};
+  a.q = p->q; a.q_rs = p->q_rs; a.q_bs = p->q_bs;
+  a.k = p->k; a.k_rs = p->k_rs; a.k_bs = p->k_bs; a.k_hs = p->k_hs;
+  a.vt = p->vt; a.vt_bs = p->vt_bs; a.vt_hs = p->vt_hs; a.Lkpad = p->Lkpad;
+  a.bias = p->bias; a.bias_hs = p->bias_hs; a.bias_center = p->bias_center; a.bias_sign = p->bias_sign;
+  a.bias_min = p->bias_min; a.bias_max = p->bias_max;
+  a.key_mask = p->key_mask; a.mask_ld = p->mask_ld; a.mask_len = p->mask_len;
+  a.out = p->out; a.out_rs = p->out_rs; a.out_bs = p->out_bs;
+  a.Lq = p->Lq; a.Lk = p->Lk; a.scale = p->scale; a.open_from = p->open_from; a.out_split3 = p->out_split3;
+  a.band = p->band; a.causal = p->causal; a.q_pos0 = p->q_pos0;
+  return mh::attention_general(a, p->B, p->H, p->dtype, (hipStream_t)stream);
+}
+
+extern "C" int mh_attention_last_kernel(void) { return mh::tl_last_kernel; }

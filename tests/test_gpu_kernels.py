@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from mh_testing.attention import split3_unpack
+
 pytestmark = pytest.mark.gpu
 
 
@@ -29,13 +31,6 @@ def split3_pack(W):
     hi = W.to(torch.bfloat16)
     lo = (W - hi.float()).to(torch.bfloat16)
     return torch.stack([hi.reshape(n, k // 32, 32), lo.reshape(n, k // 32, 32)], dim=2).reshape(n, 2 * k).contiguous()
-
-
-def split3_unpack(P):
-    """inverse of split3_pack (rows of [hi 32 | lo 32] bf16 blocks, viewed from an fp32-sized buffer) -> fp32 values hi + lo"""
-    n = P.shape[0]
-    b = P.contiguous().view(torch.bfloat16).reshape(n, -1, 2, 32).float()
-    return (b[:, :, 0] + b[:, :, 1]).reshape(n, -1)
 
 
 def run_gemm(A, W, epi, dtype, bias=None, C0=None, gate=None, rows_per_batch=0, kv=None, n_split=0, Lpad=0, out_cols=None,
