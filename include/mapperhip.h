@@ -614,7 +614,8 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
  * nb] = the row each new running beam continues (the argument of mh_t5_reorder_cache: MapperatorinatorCache.reorder_cache,
  * inference/cache_utils.py:16-20), `last` [G nb] = the token each running beam is fed next, `flags` [G][3] = (heuristic still
  * open, every candidate hit EOS / max_length, every finished slot filled) from which the host forms HF's loop condition.
- * Limits: num_beams in 2 .. 8, K <= 8192, any V (num_beams V < 2^31), greedy beams, no types_first lookback renormalisation.  Two
+ * Limits: num_beams in 2 .. 8, K <= 8192, any V (num_beams V < 2^31), greedy beams, no types_first lookback renormalisation (that
+ * is mh_beam_step_tf below, which carries the state it needs).  Two
  * kernels with the same contract and the same bits: where K <= 4096 and 4 num_beams V + 8 K' bytes (K' = K rounded up to a power of
  * two) fit 120 KB of LDS the scores live in LDS; otherwise the streaming kernel keeps the K candidates in LDS only and recomputes a
  * score from the logits in every pass (option "beam_step_path": 0 = that rule, 1 = the LDS kernel or MH_ERR_ARG, 2 = the streaming
@@ -638,6 +639,22 @@ int mh_beam_step(const MhBeamStep* bs, void* stream);
 /* Which kernel mh_beam_step runs for this shape under the current "beam_step_path": 0 = refused (a limit above), 1 = LDS kernel, 2 =
  * streaming kernel.  Additive at ABI 11 (one symbol, one option; no struct changes layout): a library without it is an older 11. */
 int mh_beam_step_path(int num_beams, int V, int K);
+/* mh_beam_step with the types_first branch of LookbackBiasLogitsWarper (logit_processors.py:116-133; sp.lookback_types_first = 1 and
+ * sp.lookback_mask_end > sp.ts_start, which mh_beam_step refuses).  Per beam row, x = the scores that ENTER the processor (log_softmax
+ * -> guidance -> MonotonicTimeShift -> TimeshiftBias -> temperature):
+ *   the row renormalises iff its last id is a timed event (bit 0 of tok_flags; an id >= V is not timed) and its slot of
+ *   `lookback_prev` is >= 0:  prob_eos = lookback_prev[slot], prob_event = 1 - prob_eos, s = 1 / (softmax(x)[ids outside [ts_start,
+ *   lookback_mask_end)].sum() prob_event + prob_eos); ids in [ts_start, lookback_mask_end) get -inf except ts_start, which gets
+ *   log(clip((s - 1) prob_eos / prob_event, 0, 1)); every other id gets log(softmax(x) s).  Any other row passes x through -- this
+ *   branch does NOT mask;
+ *   afterwards lookback_prev[slot] = softmax(x)[bit-4 ids of tok_flags (eos + context eos)].sum(), renormalised or not.
+ * `lookback_prev`: device fp32 [G num_beams], one value per row SLOT, updated in place; the caller fills it with a negative value
+ * ("no previous call") before the first step and does NOT gather it by `src`: the reference's `last_scores` is indexed by the row
+ * slot of the previous step and never sees HF's beam reordering (reproduced verbatim).  A workgroup touches its own chunk's slots only.
+ * Everything else -- limits, messages, the two kernels and their dispatch rule ("beam_step_path"), same bits from both -- is
+ * mh_beam_step's; with the types_first lookback off the call IS mh_beam_step (lookback_prev may then be NULL).  tok_flags must be
+ * set.  Additive at ABI 11 (one symbol; no struct changes layout). */
+int mh_beam_step_tf(const MhBeamStep* bs, float* lookback_prev, void* stream);
 
 /* Step-wise decode for host-driven search.  Replaces the per-position `self(**model_inputs)` of HF
  * `GenerationMixin._beam_search` (num_beams > 1: osuT5/osuT5/inference/processor.py:147,159; server.py:137) and

@@ -22,7 +22,10 @@ form (`beam_search` with use_kernel=False; ~40 ATen launches per token) stays fo
 torch.multinomial / an injected sampler, and as the cross-check of the kernel (tests run both against the reference goldens).  The logits processors of
 server.py:106-134 are applied here with torch ops (the in-kernel sampler of the greedy / sampling path selects per row and
 cannot rank across beams): classifier-free guidance, MonotonicTimeShift, TimeshiftBias, (Conditional)Temperature and the lookback
-mask; the types_first lookback renormalisation is refused in beam mode.
+warper, both branches.  Its types_first branch (logit_processors.py:116-133) keeps `last_scores` from call to call and indexes them by
+ROW SLOT: HF reorders the beams between two steps and the warper never sees `beam_idx`, so slot r renormalises with the EOS mass of
+whatever beam sat in slot r one step earlier.  Reproduced verbatim by both forms -- `BeamProcessors.last_scores` here, one fp32 per
+slot (`lookback_prev`, never gathered by `src`) in mh_beam_step_tf -- and pinned by tests/golden/t5_tiny_tf_beam.npz.
 
 Beam-sample (`do_sample` with beams, round 5; processor.py:147-160 hands both to `generate`): HF appends its top-k / top-p warpers
 BEHIND the reference's processor list with `min_tokens_to_keep = #eos + 1` (utils.py `_get_logits_processor`), and
@@ -64,12 +67,16 @@ class BeamProcessors:
 
     def __init__(self, sp, device, min_tokens_to_keep: int = 1):
         self.min_tokens_to_keep = int(min_tokens_to_keep)
-        if sp.lookback_types_first and sp.lookback_mask_end > sp.ts_start:
-            raise NotImplementedError("beam search with the types_first lookback renormalisation is not on the HIP path")
         self.sp = sp
         self.sos = torch.tensor([sp.sos_ids[i] for i in range(sp.n_sos)], dtype=torch.long, device=device)
         flags = getattr(sp, "host_tok_flags", None)
         self.flags = None if flags is None else torch.as_tensor(flags, dtype=torch.uint8, device=device)
+        self.last_scores = None          # LookbackBiasLogitsWarper types_first: what entered it at the previous call, BY ROW SLOT
+
+    def _flag(self, ids: torch.Tensor, bit: int) -> torch.Tensor:
+        """bit `bit` of tok_flags per id; an input-only id (>= vocab_out) has no flags"""
+        n = self.flags.shape[0]
+        return (ids < n) & ((self.flags[ids.clamp(0, n - 1)] & bit) != 0)
 
     def __call__(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
         sp = self.sp
@@ -99,11 +106,30 @@ class BeamProcessors:
             for j in range(sp.n_cond):
                 off = int(sp.cond_offset[j])
                 if T >= off:
-                    hit = ((self.flags[rows[:, T - off]] & (2 << j)) != 0) & ~chosen
+                    hit = self._flag(rows[:, T - off], 2 << j) & ~chosen
                     temp = torch.where(hit, torch.full_like(temp, float(sp.cond_temp[j])), temp)
                     chosen |= hit
         scores = scores / temp[:, None]
-        if sp.lookback_mask_end > sp.ts_start:                                # LookbackBiasLogitsWarper, types_first False (:111-114)
+        if sp.lookback_mask_end > sp.ts_start and sp.lookback_types_first:    # LookbackBiasLogitsWarper, types_first True (:116-133)
+            if self.flags is None:
+                raise ValueError("the types_first lookback needs tok_flags")
+            entered = scores
+            if T != 0 and self.last_scores is not None:
+                last_timed = self._flag(ids[:, -1], 1)
+                if bool(last_timed.any()):
+                    lo, hi = sp.ts_start, sp.lookback_mask_end
+                    last_probs = torch.softmax(self.last_scores, dim=-1)           # (row r of the PREVIOUS call, whichever beam it held)
+                    probs = torch.softmax(scores, dim=-1)
+                    prob_eos = last_probs[:, (self.flags & 16) != 0].sum(dim=-1)
+                    prob_event = 1 - prob_eos
+                    other = torch.cat((probs[:, :lo], probs[:, hi:]), 1).sum(dim=-1)     # probs[:, other_range], same order
+                    s = 1 / (other * prob_event + prob_eos)
+                    probs = probs * s.unsqueeze(1)
+                    probs[:, lo:hi] = 0
+                    probs[:, lo] = torch.clip((s - 1) * prob_eos / prob_event, 0, 1)
+                    scores = torch.where(last_timed.unsqueeze(1), torch.log(probs), scores)
+            self.last_scores = entered
+        elif sp.lookback_mask_end > sp.ts_start:                              # ... types_first False (:111-114)
             scores[:, sp.ts_start:sp.lookback_mask_end] = float("-inf")
         if sp.do_sample:      # HF's own warpers, appended behind the list: TopK then TopP, at least #eos + 1 tokens kept under beams
             keep = self.min_tokens_to_keep
@@ -119,9 +145,9 @@ class BeamProcessors:
 
 
 def kernel_path_available(sp, num_beams: int, vocab_out: int, n_eos: int) -> bool:
-    """mh_beam_step covers greedy beams (no beam-sample), 2 .. 8 beams, K <= 8192 candidates and any vocabulary: the library says
-    which of its two kernels a shape runs (mh_beam_step_path; 0 = refused).  (The types_first lookback renormalisation is refused
-    by both forms of the search.)"""
+    """mh_beam_step / mh_beam_step_tf cover greedy beams (no beam-sample: `do_sample` decides before anything else is read), 2 .. 8
+    beams, K <= 8192 candidates and any vocabulary: the library says which of its two kernels a shape runs (mh_beam_step_path; 0 =
+    refused)."""
     K = min(max(2, 1 + n_eos) * num_beams, num_beams * vocab_out)
     return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), int(K)) != 0
 
@@ -157,7 +183,8 @@ def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P
 def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
                         kv_fp8=None) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
-    D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs."""
+    D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs.  With the
+    types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is."""
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = neg_mask = None
@@ -180,8 +207,6 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     max_length = int(sp.max_length)
     if not (1 <= P < max_length <= p.tgt_len):
         raise ValueError("prompt / max_length do not fit the cache")
-    if sp.lookback_types_first and sp.lookback_mask_end > sp.ts_start:
-        raise NotImplementedError("beam search with the types_first lookback renormalisation is not on the HIP path")
     eos_list = [int(e) for e in eos_ids]
     K = min(max(2, 1 + len(eos_list)) * nb, nb * V)
     fill = int(sp.pad_id) or (eos_list[0] if eos_list else -1)
@@ -190,12 +215,16 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     good = [e for e in eos_list if 0 <= e < V]
     if good:
         eos_table[torch.tensor(good, dtype=torch.long, device=dev)] = 1
+    types_first = bool(sp.lookback_types_first) and sp.lookback_mask_end > sp.ts_start
     flags_h = getattr(sp, "host_tok_flags", None)
+    flags_d = None                                   # (alive until the last step has run: the kernel reads it through bs.sp.tok_flags)
     if flags_h is not None:
         flags_d = torch.as_tensor(flags_h, dtype=torch.uint8).to(dev)
-        sp.tok_flags = flags_d.data_ptr()
-    elif sp.n_cond:
-        raise ValueError("conditional temperature needs tok_flags (build the sampling struct with server.build_sampling)")
+    elif sp.n_cond or types_first:
+        raise ValueError("conditional temperature / the types_first lookback need tok_flags (build the sampling struct with "
+                         "server.build_sampling)")
+    # LookbackBiasLogitsWarper types_first: prob_eos of what entered the processor one step earlier, per row SLOT; < 0 = no call yet
+    lookback_prev = torch.full((R,), -1.0, dtype=torch.float32, device=dev) if types_first else None
     ids0 = prompt.to(dev, torch.int32).repeat_interleave(nb, 0)
     mask = None if prompt_mask is None else prompt_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0).contiguous()
     ids0e = ids0
@@ -229,7 +258,9 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     bs.G, bs.num_beams, bs.V, bs.P, bs.max_length, bs.K = G, nb, V, P, max_length, K
     bs.cfg, bs.cfg_scale, bs.length_penalty = int(cfg), float(sp.cfg_scale), float(length_penalty)
     bs.early_stopping = 2 if early_stopping == "never" else (1 if early_stopping is True else 0)
-    bs.sp = sp
+    bs.sp = sp                                       # (a copy: the caller's struct keeps its tok_flags)
+    if flags_d is not None:
+        bs.sp.tok_flags = flags_d.data_ptr()
     bs.heuristic_open, bs.src, bs.last, bs.flags = heuristic_open.data_ptr(), src.data_ptr(), feed.data_ptr(), flags.data_ptr()
 
     def step(tokens: torch.Tensor, pos: int):
@@ -249,7 +280,10 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
             bs.seq_in, bs.bs_in, bs.bb_in, bs.fin_in = a["seq"].data_ptr(), a["bs"].data_ptr(), a["bb"].data_ptr(), a["fin"].data_ptr()
             bs.run_out, bs.rs_out, bs.rb_out = b["run"].data_ptr(), b["rs"].data_ptr(), b["rb"].data_ptr()
             bs.seq_out, bs.bs_out, bs.bb_out, bs.fin_out = b["seq"].data_ptr(), b["bs"].data_ptr(), b["bb"].data_ptr(), b["fin"].data_ptr()
-            _lib.check(lib.mh_beam_step(C.byref(bs), stream), "mh_beam_step")
+            if types_first:
+                _lib.check(lib.mh_beam_step_tf(C.byref(bs), lookback_prev.data_ptr(), stream), "mh_beam_step_tf")
+            else:
+                _lib.check(lib.mh_beam_step(C.byref(bs), stream), "mh_beam_step")
             par ^= 1
             # (`src` / `feed` were written by the kernel for all RE rows: under guidance `beam_idx.repeat(2)`, cache_utils.py:18, and the
             # beam's token for both halves)

@@ -83,10 +83,16 @@ __device__ inline unsigned long long beam_rank_key(float sc, int pos) {
 // the negative row under guidance), MonotonicTimeShift bound, temperature of the step, running score
 struct BeamRow { float mp, lse_p, mn, lse_n, temp, rs; int ltv; };
 
+// LookbackBiasLogitsWarper, types_first = True (logit_processors.py:116-133), per beam row of the step: does the row renormalise
+// (its last id is a timed event and a previous call exists), the maximum of the scores x that enter the processor, log(sum exp(x -
+// mc)) - log(s), and log(prob_eos_extra), the value of the first TIME_SHIFT id.  kTf instantiations only (mh_beam_step_tf).
+struct BeamTf { int renorm; float mc, log_norm, log_extra; };
+
 // accumulated score of column v of a beam from its raw logit(s): log_softmax -> guidance -> the processor list -> + running score.
 // THE definition for every pass of both kernels (nothing here may contract into an FMA: the guidance combine is spelled out, the
 // rest is subtract / add / divide)
-__device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, float lp, float ln, int v) {
+// beam_pre is the part in front of LookbackBiasLogitsWarper (what the types_first branch keeps as `last_scores` and renormalises).
+__device__ inline float beam_pre(const MhBeamStep& p, const BeamRow& b, float lp, float ln, int v) {
   const MhSampling& sp = p.sp;
   float x = (lp - b.mp) - b.lse_p;
   if (p.cfg) {   // HF ClassifierFreeGuidanceLogitsProcessor, first in the list, on the reference's row order: second + (first - second) * scale
@@ -95,16 +101,52 @@ __device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, float 
   }
   if (b.ltv >= 0 && v >= sp.ts_start && v < sp.ts_start + b.ltv) x = -INFINITY;
   if (sp.timeshift_bias != 0.f && v >= sp.ts_start && v < sp.ts_end) x += sp.timeshift_bias;
-  x = x / b.temp;
-  if (sp.lookback_mask_end > sp.ts_start && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
+  return x / b.temp;
+}
+
+template <bool kTf>
+__device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, const BeamTf& t, float lp, float ln, int v) {
+  const MhSampling& sp = p.sp;
+  float x = beam_pre(p, b, lp, ln, v);
+  if constexpr (kTf) {   // renormalise: log(softmax(x)[v] * s) kept in the log domain; the other rows pass x through, NOT masked
+    if (t.renorm) {
+      if (v >= sp.ts_start && v < sp.lookback_mask_end) x = v == sp.ts_start ? t.log_extra : -INFINITY;
+      else x = (x - t.mc) - t.log_norm;
+    }
+  } else {
+    if (sp.lookback_mask_end > sp.ts_start && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
+  }
   return x + b.rs;
 }
 
+// the types_first state of one beam row from the three reductions over exp(x - mc) -- all columns, the columns outside [ts_start,
+// lookback_mask_end), the bit-4 ids (eos + context eos) -- and the slot's state of the previous step.  Returns the slot's next state:
+// prob_eos of THIS step's x.  (Rounded operation by operation: the two kernels must agree bit for bit.)
+__device__ inline float beam_tf_state(BeamTf& t, bool timed, float prev, float mc, float s_all, float s_other, float s_eos) {
+  t.renorm = timed && prev >= 0.f;
+  t.mc = mc;
+  t.log_norm = t.log_extra = 0.f;
+  if (t.renorm) {
+    const float prob_eos = prev, prob_event = __fsub_rn(1.f, prob_eos);
+    const float sc = __fdiv_rn(1.f, __fadd_rn(__fmul_rn(__fdiv_rn(s_other, s_all), prob_event), prob_eos));
+    const float extra = fminf(fmaxf(__fdiv_rn(__fmul_rn(__fsub_rn(sc, 1.f), prob_eos), prob_event), 0.f), 1.f);
+    t.log_norm = __fsub_rn(logf(s_all), logf(sc));
+    t.log_extra = logf(extra);
+  }
+  return __fdiv_rn(s_eos, s_all);
+}
+
+// bit `bit` of tok_flags for a history id; an input-only id (>= vocab_out) has no flags
+__device__ inline bool beam_tok_flag(const MhBeamStep& p, int id, int bit) {
+  return id >= 0 && id < p.V && (p.sp.tok_flags[id] & bit) != 0;
+}
+
 // where a pass gets the chunk's scores from: the LDS array (kStream = false) or the logits + the beams' BeamRow (kStream = true)
-template <bool kStream> struct BeamSrc {
+template <bool kStream, bool kTf> struct BeamSrc {
   const MhBeamStep& p;
   const float* val;         // LDS [nb V] (LDS kernel)
   const BeamRow* rows;      // LDS [nb]
+  const BeamTf* tf;         // LDS [nb] (kTf)
   const float* lg_pos;      // the chunk's prompt rows of the logits, [nb][V]
   const float* lg_neg;      // ... negative rows (guidance)
 };
@@ -112,12 +154,14 @@ template <bool kStream> struct BeamSrc {
 // One wave's sweep over columns base0 + lane, + step, ... < end of beam j: f(flat index, score, in range) runs for the WHOLE wave
 // (lanes past `end` get in range = false), so f may vote across the wave.  Four columns per lane are loaded before the first is used
 // (eight changed the streaming kernel's time by 1 %: it is bound by the 512 threads' arithmetic, not by the loads).
-template <bool kStream, typename F>
-__device__ inline void beam_sweep(const BeamSrc<kStream>& s, int j, int base0, int step, int end, F&& f) {
+template <bool kStream, bool kTf, typename F>
+__device__ inline void beam_sweep(const BeamSrc<kStream, kTf>& s, int j, int base0, int step, int end, F&& f) {
   const int lane = threadIdx.x & 63, V = s.p.V;
   constexpr int kU = 4;
   BeamRow b;
+  BeamTf t{};
   if (kStream) b = s.rows[j];
+  if (kStream && kTf) t = s.tf[j];
   for (int vb = base0; vb < end; vb += kU * step) {
     float lp[kU], ln[kU];
 #pragma unroll
@@ -134,15 +178,15 @@ __device__ inline void beam_sweep(const BeamSrc<kStream>& s, int j, int base0, i
       if (vb + u * step < end) {           // (wave-uniform)
         const int v = vb + u * step + lane;
         const bool ok = v < end;
-        const float x = !ok ? 0.f : kStream ? beam_score(s.p, b, lp[u], ln[u], v) : lp[u];
+        const float x = !ok ? 0.f : kStream ? beam_score<kTf>(s.p, b, t, lp[u], ln[u], v) : lp[u];
         f(j * V + v, x, ok);
       }
     }
   }
 }
 
-template <bool kStream>
-__global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
+template <bool kStream, bool kTf>
+__global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, float* lookback_prev) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float red[kBeamThreads / 64];
   __shared__ int s_hist[256];
@@ -154,6 +198,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
   __shared__ int s_sel_run[kBeamMaxBeams], s_sel_fin[kBeamMaxBeams];   // selected candidate / merged-list positions (num_beams <= 8)
   __shared__ float s_run_lp[kBeamMaxBeams], s_fin_sc[kBeamMaxBeams];
   __shared__ BeamRow s_row[kBeamMaxBeams];                          // ltv: value of the last TIME_SHIFT after the last SOS (-1: none)
+  __shared__ BeamTf s_tf[kBeamMaxBeams];                            // (kTf)
+  __shared__ uint8_t s_timed[kBeamMaxBeams];                        // (kTf) the beam's last id is a timed event
   __shared__ int s_seg_above[kBeamMaxBeams * kBeamWaves], s_seg_ties[kBeamMaxBeams * kBeamWaves];   // compaction: per (beam, wave) slice
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nb = p.num_beams, V = p.V, T = p.cur_len, L = p.max_length, R = p.G * nb;
@@ -165,7 +211,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
   BeamKV* arr = reinterpret_cast<BeamKV*>(smem + (kStream ? 0 : (((size_t)n * 4 + 15) & ~(size_t)15)));   // [k_pad] the K best, sorted
   const float* lg_pos_g = p.logits + (long)(p.cfg ? R + g * nb : g * nb) * V;    // under guidance the prompt rows are the SECOND half
   const float* lg_neg_g = p.logits + (long)g * nb * V;
-  const BeamSrc<kStream> scores{p, val, s_row, lg_pos_g, lg_neg_g};
+  const BeamSrc<kStream, kTf> scores{p, val, s_row, s_tf, lg_pos_g, lg_neg_g};
 
   // ---- per-beam processor state from the beam's own sequence: MonotonicTimeShiftLogitsProcessor (logit_processors.py:136-183)
   // and the (Conditional)Temperature of the step (:47-82; row 0 of the WHOLE call picks it unless cond_per_row) ------------------
@@ -190,10 +236,11 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
       const int32_t* hist = sp.cond_per_row ? ids : p.run_in;       // (row 0 of the call = chunk 0, beam 0)
       for (int q = 0; q < sp.n_cond; ++q) {
         const int off = sp.cond_offset[q];
-        if (T >= off && (sp.tok_flags[hist[T - off]] & (2 << q))) { temp = sp.cond_temp[q]; break; }
+        if (T >= off && beam_tok_flag(p, hist[T - off], 2 << q)) { temp = sp.cond_temp[q]; break; }
       }
       s_row[j].temp = temp;
       s_row[j].rs = p.rs_in[g * nb + j];
+      if constexpr (kTf) s_timed[j] = beam_tok_flag(p, ids[T - 1], 1) ? 1 : 0;
     }
   }
   __syncthreads();
@@ -226,6 +273,31 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
         if (tid == 0) { s_row[j].mp = mp[j]; s_row[j].lse_p = logf(sp_[j]); s_row[j].mn = mn[j]; s_row[j].lse_n = p.cfg ? logf(sn_[j]) : 0.f; }
       }
     __syncthreads();
+    if constexpr (kTf) {
+      // the three reductions of the types_first lookback over x = beam_pre(): per beam, same thread -> column order as the LDS kernel
+      for (int j = 0; j < nb; ++j) {
+        const BeamRow b = s_row[j];
+        float mc = -INFINITY;
+        for (int v = tid; v < V; v += kBeamThreads)
+          mc = fmaxf(mc, beam_pre(p, b, lg_pos_g[(long)j * V + v], p.cfg ? lg_neg_g[(long)j * V + v] : 0.f, v));
+        mc = block_max(mc, red);
+        float s_all = 0.f, s_other = 0.f, s_eos = 0.f;
+        for (int v = tid; v < V; v += kBeamThreads) {
+          const float e = expf(beam_pre(p, b, lg_pos_g[(long)j * V + v], p.cfg ? lg_neg_g[(long)j * V + v] : 0.f, v) - mc);
+          s_all += e;
+          if (!(v >= sp.ts_start && v < sp.lookback_mask_end)) s_other += e;
+          if (sp.tok_flags[v] & 16) s_eos += e;
+        }
+        s_all = block_sum(s_all, red);
+        s_other = block_sum(s_other, red);
+        s_eos = block_sum(s_eos, red);
+        if (tid == 0) {
+          const int slot = g * nb + j;
+          lookback_prev[slot] = beam_tf_state(s_tf[j], s_timed[j] != 0, lookback_prev[slot], mc, s_all, s_other, s_eos);
+        }
+      }
+      __syncthreads();
+    }
   } else {
     // ---- log_softmax (+ guidance) + processors + running score -> val[] ------------------------------------------------------
     // the prompt rows' logits are staged in LDS once (one round of independent loads); the per-beam maximum / sum then read LDS in
@@ -244,8 +316,28 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p) {
       sp_ = block_sum(sp_, red);
       if (p.cfg) sn_ = block_sum(sn_, red);
       const BeamRow b{mp, logf(sp_), mn, p.cfg ? logf(sn_) : 0.f, s_row[j].temp, s_row[j].rs, s_row[j].ltv};
+      BeamTf t{};
+      if constexpr (kTf) {   // the types_first lookback's three reductions over x = beam_pre() (the logits stay in LDS for beam_score)
+        float mc = -INFINITY;
+        for (int v = tid; v < V; v += kBeamThreads) mc = fmaxf(mc, beam_pre(p, b, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v));
+        mc = block_max(mc, red);
+        float s_all = 0.f, s_other = 0.f, s_eos = 0.f;
+        for (int v = tid; v < V; v += kBeamThreads) {
+          const float e = expf(beam_pre(p, b, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v) - mc);
+          s_all += e;
+          if (!(v >= sp.ts_start && v < sp.lookback_mask_end)) s_other += e;
+          if (sp.tok_flags[v] & 16) s_eos += e;
+        }
+        s_all = block_sum(s_all, red);
+        s_other = block_sum(s_other, red);
+        s_eos = block_sum(s_eos, red);
+        const int slot = g * nb + j;
+        const float next = beam_tf_state(t, s_timed[j] != 0, lookback_prev[slot], mc, s_all, s_other, s_eos);   // (every thread: same inputs)
+        __syncthreads();                                  // ... all have read the slot
+        if (tid == 0) lookback_prev[slot] = next;
+      }
       for (int v = tid; v < V; v += kBeamThreads)       // (each thread rewrites exactly the columns it read)
-        lg_pos[v] = beam_score(p, b, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);
+        lg_pos[v] = beam_score<kTf>(p, b, t, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);
     }
     __syncthreads();
   }
@@ -491,35 +583,52 @@ extern "C" int mh_beam_step_path(int num_beams, int V, int K) {
   return fits ? 1 : want == 1 ? 0 : 2;
 }
 
-extern "C" int mh_beam_step(const MhBeamStep* bs, void* stream) {
+// mh_beam_step (lookback_prev = nullptr, `tf` false) and mh_beam_step_tf: one set of checks, one dispatch rule
+static int beam_step_launch(const char* who, const MhBeamStep* bs, float* lookback_prev, bool tf_entry, void* stream) {
   MH_REQUIRE(bs && bs->logits && bs->eos_table && bs->run_in && bs->run_out && bs->rs_in && bs->rs_out && bs->rb_in && bs->rb_out &&
              bs->seq_in && bs->seq_out && bs->bs_in && bs->bs_out && bs->bb_in && bs->bb_out && bs->fin_in && bs->fin_out &&
-             bs->heuristic_open && bs->src && bs->last && bs->flags, "mh_beam_step: null argument");
-  MH_REQUIRE(bs->G >= 1 && bs->V >= 1 && bs->num_beams >= 2 && bs->num_beams <= kBeamMaxBeams, "mh_beam_step: %d chunks x %d beams (2 .. %d beams)", bs->G, bs->num_beams, kBeamMaxBeams);
-  MH_REQUIRE(bs->K >= bs->num_beams && bs->K <= kBeamMaxK && bs->K <= (int64_t)bs->num_beams * bs->V, "mh_beam_step: K = %d candidates not in [num_beams, %d]", bs->K, kBeamMaxK);
-  MH_REQUIRE(bs->P >= 1 && bs->cur_len >= bs->P && bs->cur_len < bs->max_length, "mh_beam_step: cur_len %d not in [P, max_length)", bs->cur_len);
-  MH_REQUIRE(bs->sp.do_sample == 0, "mh_beam_step: greedy beams only (beam-sample draws on the host side)");
-  MH_REQUIRE(!(bs->sp.lookback_types_first && bs->sp.lookback_mask_end > bs->sp.ts_start), "mh_beam_step: the types_first lookback renormalisation is not built for beams");
-  MH_REQUIRE(bs->sp.tok_flags || bs->sp.n_cond == 0, "mh_beam_step: conditional temperature needs tok_flags");
-  MH_REQUIRE(bs->sp.temperature > 0.f && bs->sp.n_sos >= 0 && bs->sp.n_sos <= 16 && bs->sp.n_cond >= 0 && bs->sp.n_cond <= 3, "mh_beam_step: bad sampling parameters");
-  MH_REQUIRE((int64_t)bs->num_beams * bs->V <= 0x7fffffff, "mh_beam_step: num_beams x V = %d x %d exceeds the 31-bit flat index", bs->num_beams, bs->V);
+             bs->heuristic_open && bs->src && bs->last && bs->flags, "%s: null argument", who);
+  MH_REQUIRE(bs->G >= 1 && bs->V >= 1 && bs->num_beams >= 2 && bs->num_beams <= kBeamMaxBeams, "%s: %d chunks x %d beams (2 .. %d beams)", who, bs->G, bs->num_beams, kBeamMaxBeams);
+  MH_REQUIRE(bs->K >= bs->num_beams && bs->K <= kBeamMaxK && bs->K <= (int64_t)bs->num_beams * bs->V, "%s: K = %d candidates not in [num_beams, %d]", who, bs->K, kBeamMaxK);
+  MH_REQUIRE(bs->P >= 1 && bs->cur_len >= bs->P && bs->cur_len < bs->max_length, "%s: cur_len %d not in [P, max_length)", who, bs->cur_len);
+  MH_REQUIRE(bs->sp.do_sample == 0, "%s: greedy beams only (beam-sample draws on the host side)", who);
+  const bool tf = bs->sp.lookback_types_first && bs->sp.lookback_mask_end > bs->sp.ts_start;
+  MH_REQUIRE(!tf || tf_entry, "%s: the types_first lookback renormalisation is not built for beams", who);
+  MH_REQUIRE(!tf || lookback_prev, "%s: the types_first lookback renormalisation needs lookback_prev", who);
+  MH_REQUIRE(!tf || bs->sp.tok_flags, "%s: the types_first lookback renormalisation needs tok_flags", who);
+  MH_REQUIRE(!tf || bs->sp.lookback_mask_end <= bs->V, "%s: lookback_mask_end %d beyond the vocabulary (%d)", who, bs->sp.lookback_mask_end, bs->V);
+  MH_REQUIRE(bs->sp.tok_flags || bs->sp.n_cond == 0, "%s: conditional temperature needs tok_flags", who);
+  MH_REQUIRE(bs->sp.temperature > 0.f && bs->sp.n_sos >= 0 && bs->sp.n_sos <= 16 && bs->sp.n_cond >= 0 && bs->sp.n_cond <= 3, "%s: bad sampling parameters", who);
+  MH_REQUIRE((int64_t)bs->num_beams * bs->V <= 0x7fffffff, "%s: num_beams x V = %d x %d exceeds the 31-bit flat index", who, bs->num_beams, bs->V);
   const int path = mh_beam_step_path(bs->num_beams, bs->V, bs->K);
-  MH_REQUIRE(path != 0, "mh_beam_step: num_beams x V = %d x %d (+ %d candidates) does not fit the LDS kernel (120 KB of LDS, K <= %d) and beam_step_path = 1 rules the streaming kernel out",
-             bs->num_beams, bs->V, bs->K, kBeamLdsMaxK);
+  MH_REQUIRE(path != 0, "%s: num_beams x V = %d x %d (+ %d candidates) does not fit the LDS kernel (120 KB of LDS, K <= %d) and beam_step_path = 1 rules the streaming kernel out",
+             who, bs->num_beams, bs->V, bs->K, kBeamLdsMaxK);
   int64_t k_pad = 1;
   while (k_pad < bs->K) k_pad <<= 1;
   static PerDeviceOnce attr_set;
   const int arc = attr_set.run([] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kBeamLdsBytes) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(beam_step_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kBeamMaxK * 8) == hipSuccess
+    auto set = [](const void* f, int bytes) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess; };
+    return set(reinterpret_cast<const void*>(beam_step_kernel<false, false>), kBeamLdsBytes) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<true, false>), kBeamMaxK * 8) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<false, true>), kBeamLdsBytes) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<true, true>), kBeamMaxK * 8)
                ? MH_OK : check_launch("mh_beam_step: LDS attribute");
   });
   if (arc != MH_OK) return arc;
+  const size_t lds = path == 1 ? (size_t)(mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8) : (size_t)(k_pad * 8);
+  const dim3 grid(bs->G), block(kBeamThreads);
   if (path == 1) {
-    const int64_t lds = mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8;
-    hipLaunchKernelGGL(beam_step_kernel<false>, dim3(bs->G), dim3(kBeamThreads), (size_t)lds, (hipStream_t)stream, *bs);
-    return check_launch("beam_step_kernel<lds>");
+    if (tf) hipLaunchKernelGGL((beam_step_kernel<false, true>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+    else hipLaunchKernelGGL((beam_step_kernel<false, false>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+    return check_launch(tf ? "beam_step_kernel<lds, types_first>" : "beam_step_kernel<lds>");
   }
-  hipLaunchKernelGGL(beam_step_kernel<true>, dim3(bs->G), dim3(kBeamThreads), (size_t)(k_pad * 8), (hipStream_t)stream, *bs);
-  return check_launch("beam_step_kernel<streaming>");
+  if (tf) hipLaunchKernelGGL((beam_step_kernel<true, true>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+  else hipLaunchKernelGGL((beam_step_kernel<true, false>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+  return check_launch(tf ? "beam_step_kernel<streaming, types_first>" : "beam_step_kernel<streaming>");
+}
+
+extern "C" int mh_beam_step(const MhBeamStep* bs, void* stream) { return beam_step_launch("mh_beam_step", bs, nullptr, false, stream); }
+
+extern "C" int mh_beam_step_tf(const MhBeamStep* bs, float* lookback_prev, void* stream) {
+  return beam_step_launch("mh_beam_step_tf", bs, lookback_prev, true, stream);
 }

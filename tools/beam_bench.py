@@ -1,12 +1,14 @@
 """Beam search throughput (`num_beams = 2`: the reference's timing pass, super_timing_generator.py:28; cache reorder per step,
 inference/cache_utils.py:16-20): G windows x 2 beams through mapperatorinator_amd.beam.beam_search on osuT5-base bf16.
-Prints one JSON line: tokens/s of the returned hypotheses and ms per beam step.    python tools/beam_bench.py [--chunks 1] [--beams 2]"""
+Prints one JSON line: tokens/s of the returned hypotheses and ms per beam step.    python tools/beam_bench.py [--chunks 1] [--beams 2]
+`--types-first`: the types_first processors with a lookback window (ConditionalTemperature + LookbackBiasLogitsWarper(types_first=True):
+the step is mh_beam_step_tf); `--step-path 2`: the streaming kernel instead of the automatic choice (option "beam_step_path")."""
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(chunks=1, beams=2, new_tokens=128, device="cuda:0", model_tuple=None):
+def run(chunks=1, beams=2, new_tokens=128, device="cuda:0", model_tuple=None, types_first=False):
     from mapperatorinator_amd.server import build_sampling
     from mh_testing import synthetic_audio_varied
     import importlib.util
@@ -20,6 +22,8 @@ def run(chunks=1, beams=2, new_tokens=128, device="cuda:0", model_tuple=None):
     audio = synthetic_audio_varied(chunks, (frames - 1) * 128, seed=5).to(dev)
     prompt = torch.full((chunks, 1), tok.sos_id, dtype=torch.long)
     gk = dict(do_sample=False, num_beams=beams, max_length=tgt, temperature=1.0, context_type="map", pad_token_id=0)
+    if types_first:
+        gk.update(types_first=True, timing_temperature=0.9, lookback_time=500)
     sp, eos = build_sampling(tok, gk, tgt)
     eos = []          # random-init weights: keep every hypothesis running to max_length
     res = {}
@@ -37,6 +41,8 @@ def run(chunks=1, beams=2, new_tokens=128, device="cuda:0", model_tuple=None):
         outs[name] = out["tokens"]
         res[name] = {"seconds": round(dt, 4), "ms_per_beam_step": round(dt * 1e3 / max(n, 1), 3), "tokens_per_s": round(chunks * n / dt, 1)}
     res["same_ids"] = bool(torch.equal(outs["beam_step_kernel"], outs["torch_op_bookkeeping"]))
+    if types_first:      # a row renormalises after a timed event (the three reductions of the step run for every row either way)
+        res["timed_ids_in_best_hypotheses"] = int(torch.from_numpy(sp.host_tok_flags & 1).bool()[outs["beam_step_kernel"][:, 1:-1]].sum())
     res["workload"] = (f"osuT5-base bf16, {chunks} window(s) x {beams} beams, {n} steps: mel + encoder + beam search (per token mh_t5_step -> "
                        "mh_beam_step -> mh_t5_reorder_cache; torch_op_bookkeeping = the ~40 ATen launches per token of round 5)")
     return res
@@ -46,5 +52,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=1)
     ap.add_argument("--beams", type=int, default=2)
+    ap.add_argument("--types-first", action="store_true")
+    ap.add_argument("--step-path", type=int, default=0, choices=(0, 1, 2))
     a = ap.parse_args()
-    print(json.dumps(run(a.chunks, a.beams)))
+    from mapperatorinator_amd import _lib
+    _lib.set_option("beam_step_path", a.step_path)
+    print(json.dumps(dict(run(a.chunks, a.beams, types_first=a.types_first), types_first=a.types_first, step_path=a.step_path)))

@@ -8,7 +8,9 @@ per launch from device events around `--launches` back-to-back launches (the ste
 median / maximum over `--repeats` such windows -- the spread to hold a difference against.
 `--per-token` adds what a token costs end to end through beam_search on a tiny T5 with that vocabulary, once with the kernel and once
 with the torch-op bookkeeping (`use_kernel=False`: ~40 ATen launches and several host round trips): their difference plus the kernel's
-own time is the torch-op bookkeeping's cost per token."""
+own time is the torch-op bookkeeping's cost per token.
+`--types-first` times mh_beam_step_tf with the types_first lookback on: every id is flagged as a timed event and the state starts
+non-negative, so every beam row renormalises at every launch (the three extra reductions run for every row whether it does or not)."""
 import argparse
 import ctypes as C
 import json
@@ -23,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from mapperatorinator_amd import _lib   # noqa: E402
 
 
-def time_step(G, nb, V, n_eos, path, launches=200, repeats=7, cfg=False, seed=0):
+def time_step(G, nb, V, n_eos, path, launches=200, repeats=7, cfg=False, seed=0, types_first=False):
     lib = _lib.load()
     old = _lib.set_option("beam_step_path", path)
     try:
@@ -54,6 +56,13 @@ def time_step(G, nb, V, n_eos, path, launches=200, repeats=7, cfg=False, seed=0)
         sp.top_p, sp.temperature, sp.timeshift_bias, sp.cfg_scale = 1.0, 0.9, 0.3, 1.5 if cfg else 1.0
         sp.ts_start, sp.ts_end, sp.n_sos, sp.max_length = 3, min(3 + 1001, V), 1, L
         sp.sos_ids[0] = 1
+        prev = None
+        if types_first:      # ids [ts_start, ts_start + 50) are the lookback range; every id counts as timed, id 2 as the warper's eos
+            tok_flags = torch.ones(V, dtype=torch.uint8)
+            tok_flags[2] |= 16
+            tok_flags = tok_flags.to(dev)
+            sp.lookback_types_first, sp.lookback_mask_end, sp.tok_flags = 1, sp.ts_start + 50, tok_flags.data_ptr()
+            prev = torch.full((G * nb,), 1e-3, dtype=torch.float32, device=dev)
         bs = _lib.MhBeamStep()
         bs.logits, bs.eos_table = logits.data_ptr(), eos_table.data_ptr()
         bs.G, bs.num_beams, bs.V, bs.P, bs.max_length, bs.K, bs.cur_len = G, nb, V, P, L, K, T
@@ -66,7 +75,10 @@ def time_step(G, nb, V, n_eos, path, launches=200, repeats=7, cfg=False, seed=0)
 
         def launch(n):
             for _ in range(n):
-                _lib.check(lib.mh_beam_step(C.byref(bs), stream), "mh_beam_step")
+                if types_first:
+                    _lib.check(lib.mh_beam_step_tf(C.byref(bs), prev.data_ptr(), stream), "mh_beam_step_tf")
+                else:
+                    _lib.check(lib.mh_beam_step(C.byref(bs), stream), "mh_beam_step")
         launch(20)
         torch.cuda.synchronize()
         us = []
@@ -77,7 +89,7 @@ def time_step(G, nb, V, n_eos, path, launches=200, repeats=7, cfg=False, seed=0)
             e1.record()
             torch.cuda.synchronize()
             us.append(e0.elapsed_time(e1) * 1e3 / launches)
-        return dict(G=G, beams=nb, V=V, eos=n_eos, K=K, path=path, kernel={1: "lds", 2: "streaming"}[chosen],
+        return dict(G=G, beams=nb, V=V, eos=n_eos, K=K, path=path, kernel={1: "lds", 2: "streaming"}[chosen], types_first=types_first,
                     us_min=round(min(us), 2), us_median=round(statistics.median(us), 2), us_max=round(max(us), 2))
     finally:
         _lib.set_option("beam_step_path", old)
@@ -133,6 +145,7 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--per-token", action="store_true")
     ap.add_argument("--table", action="store_true")
+    ap.add_argument("--types-first", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("beam_step_bench: no GPU (there is nothing to time without one)")
@@ -146,6 +159,6 @@ if __name__ == "__main__":
             if paths == (2,):
                 print(json.dumps(time_per_token(a.chunks, nb, V)), flush=True)
     else:
-        print(json.dumps(time_step(a.chunks, a.beams, a.vocab, a.eos, a.path, a.launches, a.repeats, cfg=a.guidance)), flush=True)
+        print(json.dumps(time_step(a.chunks, a.beams, a.vocab, a.eos, a.path, a.launches, a.repeats, cfg=a.guidance, types_first=a.types_first)), flush=True)
         if a.per_token:
             print(json.dumps(time_per_token(a.chunks, a.beams, a.vocab)), flush=True)
