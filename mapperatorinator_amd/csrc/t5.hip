@@ -7,6 +7,7 @@
 //   bias, no 1/sqrt(d) scaling, gated gelu_new FFN), HF GenerationMixin._sample under
 //   model_generate (osuT5/osuT5/inference/server.py:83-156) with the reference logits processors.
 #include <stdlib.h>
+#include <string.h>
 
 #include <atomic>
 #include <functional>
@@ -66,6 +67,38 @@ inline bool is_local_layer(const MhT5Config* c, int l) { return c->arch == 1 && 
     int _rc = (expr);             \
     if (_rc != MH_OK) return _rc; \
   } while (0)
+
+// f(a value of the storage type): one call site for both instantiations of a kernel or launcher (`using T = decltype(t)`)
+template <typename F>
+auto dispatch_dtype(int dtype, F&& f) { return dtype == MH_BF16 ? f(bf16_t{}) : f(float{}); }
+// f(std::integral_constant<int, KC>) for d_model = 128 KC of the attention kernels that project their own q (/ k / v), KC in 1..7;
+// any other d_model runs KC = 8 (check_decode_shape guards the range)
+template <int KC = 1, typename F>
+int dispatch_kc(int d, F&& f) {
+  if constexpr (KC == 8) return f(std::integral_constant<int, 8>{});
+  else return d == 128 * KC ? f(std::integral_constant<int, KC>{}) : dispatch_kc<KC + 1>(d, f);
+}
+int check_arch2_weights(const MhT5Config* c, const MhT5Weights* w, const char* who) {
+  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "%s: arch 2 needs decoder.embed_positions and the LayerNorm biases", who);
+  return MH_OK;
+}
+
+// The packed e4m3 copies the token steps stream, laid out HERE and nowhere else: 2 n_dec_layers planes (layer, k | v) of `n` units of
+// `unit_bytes` e4m3 bytes, then -- 256-byte aligned -- one fp32 scale per unit, plane by plane
+struct Kv8Layout {
+  int64_t plane_bytes, plane_scales;   // one plane: its e4m3 bytes, its scales
+  int64_t scales_offset, total;        // bytes from the start of the copy to its scales, bytes of the whole copy
+  int64_t data(int l, int kv) const { return (int64_t)(l * 2 + kv) * plane_bytes; }     // byte offset of plane (l, kv)
+  int64_t scale(int l, int kv) const { return (int64_t)(l * 2 + kv) * plane_scales; }   // index of its first scale
+};
+inline Kv8Layout kv8_layout(const MhT5Config* c, int64_t n, int64_t unit_bytes) {
+  const int64_t planes = 2 * (int64_t)c->n_dec_layers, data = align256(planes * n * unit_bytes);
+  return {n * unit_bytes, n, data, data + align256(planes * n * 4)};
+}
+// cross K/V of kvB rows (mh_t5_quantize_cross_kv): a unit = one (row, head) slab of src_len x 64; the shadow of the self-attention
+// cache of B rows (mh_t5_generate_skv8): a unit = one cached row of 64 at (row, head, position)
+inline Kv8Layout cross_kv8_layout(const MhT5Config* c, int kvB) { return kv8_layout(c, (int64_t)kvB * c->n_heads, (int64_t)c->src_len * 64); }
+inline Kv8Layout self_kv8_layout(const MhT5Config* c, int B) { return kv8_layout(c, (int64_t)B * c->n_heads * c->tgt_len, 64); }
 
 }  // namespace
 }  // namespace mh
@@ -1141,19 +1174,6 @@ int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inne
     hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
   return check_launch("dec_self_attn_qkv_kernel");
 }
-template <typename T>
-int launch_self_qkv_d(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8 = nullptr) {
-  switch (hp.d) {
-    case 128: return launch_self_qkv<T, 1>(sa, hp, inner, s, f8);
-    case 256: return launch_self_qkv<T, 2>(sa, hp, inner, s, f8);
-    case 384: return launch_self_qkv<T, 3>(sa, hp, inner, s, f8);
-    case 512: return launch_self_qkv<T, 4>(sa, hp, inner, s, f8);
-    case 640: return launch_self_qkv<T, 5>(sa, hp, inner, s, f8);
-    case 768: return launch_self_qkv<T, 6>(sa, hp, inner, s, f8);
-    case 896: return launch_self_qkv<T, 7>(sa, hp, inner, s, f8);
-    default: return launch_self_qkv<T, 8>(sa, hp, inner, s, f8);
-  }
-}
 template <typename T, int KC>
 int launch_cross_q(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d, "decode: dense residual rows / projection weights expected");
@@ -1178,47 +1198,88 @@ int launch_cross_q(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStrea
 }
 template <typename T>
 int launch_cross_q_d(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s) {
-  switch (hp.d) {
-    case 128: return launch_cross_q<T, 1>(ca, hp, s);
-    case 256: return launch_cross_q<T, 2>(ca, hp, s);
-    case 384: return launch_cross_q<T, 3>(ca, hp, s);
-    case 512: return launch_cross_q<T, 4>(ca, hp, s);
-    case 640: return launch_cross_q<T, 5>(ca, hp, s);
-    case 768: return launch_cross_q<T, 6>(ca, hp, s);
-    case 896: return launch_cross_q<T, 7>(ca, hp, s);
-    default: return launch_cross_q<T, 8>(ca, hp, s);
-  }
+  return dispatch_kc(hp.d, [&](auto kc) { return launch_cross_q<T, decltype(kc)::value>(ca, hp, s); });
 }
 
 // measurement hook (mh_t5_decode_timing): device buffer that receives per-launch timestamps of the dominant kernel
 struct DecodeTiming { unsigned long long* buf = nullptr; int ring = 0; };
 DecodeTiming g_timing;
 
+// Everything ONE enqueue of a token step depends on: enqueue_step() reads this and option(), nothing else, and step_graph_key() makes
+// a step graph's cache key of exactly this -- a new input of the step is a new field here and so cannot be missing from the key.  Made by
+// step_call_init() (zero bytes, padding included), then assigned field by field.  Every pointer is at the chain's first row.
+struct StepCall {
+  const MhT5Config* c; const MhT5Weights* w;
+  const void* cross_kv;                  // kvB rows per (layer, k | v) slab: B/2 under CFG (a pair shares its encoder output, row b
+  int Bc, Bfull, kvB;                    // reads K/V row b % kvB); Bc = rows of this chain, Bfull = of the whole batch
+  const uint8_t* prompt_mask; int P;
+  DecBuffers bf;
+  SampleP smp;                           // (all zero without the sampler)
+  const void* kv8; const float* kv8_scales;   // the e4m3 copy of cross_kv and its scales (mh_t5_quantize_cross_kv), or NULL
+  int with_sampler;                      // 0: the step ends with the logits (mh_t5_step: the host selects)
+  int kv_group;                          // > 1: rows are (chunk, beam) pairs and row b reads cross K/V row b / kv_group
+  int has_rows; RowSetP rows;            // has_rows: the sampler reads its settings per returned row (mh_t5_generate_rows)
+  unsigned long long* timing_buf; int timing_ring;   // the timing hook as it stood when the call was built
+};
+static_assert(std::is_trivially_copyable<StepCall>::value, "StepCall is keyed by its bytes");
+void step_call_init(StepCall* k, const MhT5Config* c, const MhT5Weights* w) {
+  memset(k, 0, sizeof(*k));
+  k->c = c; k->w = w; k->timing_buf = g_timing.buf; k->timing_ring = g_timing.ring;
+}
+
+// The operands of a layer's GEMVs, each described ONCE: the three launches behind the cross-attention and the fused tail (TailP) read
+// the same.  resid_gemv: h += A W^T (+ bias), A [Bc, K]: the output projection of either attention (o_gemv), the FFN's wo / fc2 (ffn_out)
+dec::SkinnyP resid_gemv(const StepCall& k, const void* A, int K, const void* W, const float* bias) {
+  dec::SkinnyP p{};
+  p.A = A; p.lda = K; p.W = W; p.ldw = K; p.B = k.Bc; p.N = k.c->d_model; p.K = K; p.h = k.bf.h; p.ldh = k.c->d_model;
+  p.bias = k.c->arch >= 1 ? bias : nullptr;
+  return p;
+}
+dec::SkinnyP o_gemv(const StepCall& k, const void* W, const float* bias) { return resid_gemv(k, k.bf.attn, k.c->n_heads * 64, W, bias); }
+dec::SkinnyP ffn_out(const StepCall& k, int l) { return resid_gemv(k, k.bf.ff, k.c->d_ff, k.w->dec_wo[l], k.w->dec_fc2_b[l]); }
+// ffn_in: ff = act(norm(h) Wi^T): T5 gated GELU (wi_0 / wi_1 interleaved, N = 2 d_ff), the Whisper family's biased fc1 + erf GELU
+dec::SkinnyP ffn_in(const StepCall& k, int l) {
+  const MhT5Config* c = k.c;
+  dec::SkinnyP p{};
+  p.A = k.bf.h; p.lda = c->d_model; p.ln_w = k.w->dec_ln3[l]; p.eps = c->eps; p.W = k.w->dec_wi[l]; p.ldw = c->d_model; p.B = k.Bc;
+  p.K = c->d_model; p.out = k.bf.ff; p.ldo = c->d_ff; p.N = c->arch >= 1 ? c->d_ff : 2 * c->d_ff;
+  if (c->arch >= 1) p.bias = k.w->dec_fc1_b[l];
+  if (c->arch == 2) p.ln_b = k.w->dec_ln3_b[l];
+  return p;
+}
+// the projection an attention kernel does for itself: norm(h) W^T (ln_b: the affine LayerNorm of arch 2, else NULL)
+dec::HeadProjP head_proj(const MhT5Config* c, const float* h, const float* ln_w, const float* ln_b, const void* W) {
+  dec::HeadProjP hp{};
+  hp.h = h; hp.ldh = c->d_model; hp.ln_w = ln_w; hp.eps = c->eps; hp.W = W; hp.ldw = c->d_model; hp.d = c->d_model; hp.ln_b = ln_b;
+  return hp;
+}
+// cross-attention of B rows over layer l of a cross_kv of kvB rows (the plain T5 form: the step adds the rest)
+dec::CrossAttnP cross_attn(const MhT5Config* c, const void* cross_kv, int kvB, int l, void* out, int B) {
+  const long kv_layer = (long)kvB * c->n_heads * c->src_len * 64 * es_of(c->dtype);
+  dec::CrossAttnP ca{};
+  ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer; ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer;
+  ca.out = out; ca.ldo = c->n_heads * 64; ca.B = B; ca.H = c->n_heads; ca.L = c->src_len;
+  return ca;
+}
+
 template <typename T>
-int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int Bfull, int kvB,
-                 const uint8_t* prompt_mask, int P, const DecBuffers& bf, const SampleP& smp, hipStream_t s,
-                 const void* kv8 = nullptr, const float* kv8_scales = nullptr, bool with_sampler = true, int kv_group = 0,
-                 const RowSetP* rows = nullptr) {
-  // rows != NULL: the sampler reads its settings per returned row (mh_t5_generate_rows)
-  // with_sampler = false: the step ends with the logits (mh_t5_step: the host selects); kv_group > 1: rows are (chunk, beam)
-  // pairs and row b reads cross K/V row b / kv_group
-  // kv8 / kv8_scales: the chain's first row of the e4m3 copy of cross_kv and of its scales (mh_t5_quantize_cross_kv)
-  // B rows of one chain; every pointer in `bf` / `cross_kv` / `prompt_mask` already points at the chain's first
-  // row, only the per-layer strides of the caches use the full batch size.  kvB = rows of cross_kv (B/2 under CFG:
-  // a pair shares its encoder output, row b reads K/V row b % kvB).
-  const int d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff, L = c->src_len, tgt = c->tgt_len;
-  const int es = (int)sizeof(T);
+int enqueue_step(const StepCall& k, hipStream_t s) {
+  const MhT5Config* c = k.c;
+  const MhT5Weights* w = k.w;
+  const DecBuffers& bf = k.bf;
+  const int B = k.Bc, Bfull = k.Bfull, kvB = k.kvB, H = c->n_heads, inner = H * 64, tgt = c->tgt_len, es = (int)sizeof(T);
   const int* posp = &bf.st->pos;
   // arch 1 / 2: the Whisper family (VarWhisperDecoderLayer, modeling_varwhisper.py:633-741); arch 2: affine LayerNorm
   // prologues, the identity rotary table the host packs.  Every arch runs the same six dependent kernels per layer.
   const bool wh = c->arch >= 1, hf = c->arch == 2;
   MH_REQUIRE(!wh || w->dec_rope, "decode: the Whisper family needs its rotary table");
+  const Kv8Layout self8 = self_kv8_layout(c, Bfull), cross8 = cross_kv8_layout(c, kvB);
   for (int l = 0; l < c->n_dec_layers; ++l) {
     const long cache_off = (long)l * Bfull * H * tgt * 64 * es;
     MH_REQUIRE(!hf || (w->dec_ln1_b[l] && w->dec_ln2_b[l] && w->dec_ln3_b[l]), "decode: arch 2 needs the LayerNorm biases of layer %d", l);
     // self attention (+ q / k / v projection and self-KV append)
     dec::SelfAttnP sa{};
-    sa.kc = (char*)bf.self_k + cache_off; sa.vc = (char*)bf.self_v + cache_off; sa.prompt_mask = prompt_mask; sa.P = P;
+    sa.kc = (char*)bf.self_k + cache_off; sa.vc = (char*)bf.self_v + cache_off; sa.prompt_mask = k.prompt_mask; sa.P = k.P;
     sa.out = bf.attn; sa.ldo = inner; sa.B = B; sa.H = H; sa.tgt_len = tgt; sa.pos = posp;
     if (wh) {   // biased fused Wqkv, RoPE, scaled scores, optional window
       const bool local = is_local_layer(c, l);
@@ -1227,85 +1288,52 @@ int enqueue_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv
     } else {    // T5: the shared relative position bias
       sa.bias = w->dec_rel_bias;
     }
-    dec::HeadProjP hp{};
-    hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln1[l]; hp.eps = c->eps; hp.W = w->dec_qkv[l]; hp.ldw = d; hp.d = d;
-    hp.ln_b = hf ? w->dec_ln1_b[l] : nullptr;
     dec::SelfKv8P f8{};
-    if (bf.self8) {   // this layer's k | v slabs of the shadow: the chain's first row, the strides those of the full batch
-      const long rows = (long)Bfull * H * tgt;
-      f8.k8 = bf.self8 + (long)(l * 2 + 0) * rows * 64; f8.v8 = bf.self8 + (long)(l * 2 + 1) * rows * 64;
-      f8.ks = bf.self8_scales + (long)(l * 2 + 0) * rows; f8.vs = bf.self8_scales + (long)(l * 2 + 1) * rows;
+    if (bf.self8) {   // this layer's k | v planes of the shadow: the chain's first row, the strides those of the full batch
+      f8.k8 = bf.self8 + self8.data(l, 0); f8.v8 = bf.self8 + self8.data(l, 1);
+      f8.ks = bf.self8_scales + self8.scale(l, 0); f8.vs = bf.self8_scales + self8.scale(l, 1);
     }
-    MH_TRY(launch_self_qkv_d<T>(sa, hp, inner, s, bf.self8 ? &f8 : nullptr));
-    dec::SkinnyP sk{};
-    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_o[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
-    sk.bias = wh ? w->dec_o_b[l] : nullptr;
-    MH_TRY(skinny_resid<T>(sk, s));
+    const dec::HeadProjP qkv = head_proj(c, bf.h, w->dec_ln1[l], hf ? w->dec_ln1_b[l] : nullptr, w->dec_qkv[l]);
+    MH_TRY(dispatch_kc(qkv.d, [&](auto kc) { return launch_self_qkv<T, decltype(kc)::value>(sa, qkv, inner, s, bf.self8 ? &f8 : nullptr); }));
+    MH_TRY(skinny_resid<T>(o_gemv(k, w->dec_o[l], w->dec_o_b[l]), s));
     // cross attention (+ query projection)
-    dec::CrossAttnP ca{};
-    const long kv_layer = (long)kvB * H * L * 64 * es;
-    ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer; ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer;
-    ca.out = bf.attn; ca.ldo = inner; ca.B = B; ca.H = H; ca.L = L; ca.kv_B = kv_group > 1 ? -kv_group : (kvB < Bfull ? kvB : 0);
+    dec::CrossAttnP ca = cross_attn(c, k.cross_kv, kvB, l, bf.attn, B);
+    ca.kv_B = k.kv_group > 1 ? -k.kv_group : (kvB < Bfull ? kvB : 0);
     if (wh) { ca.q_bias = w->dec_cq_b[l]; ca.scale = c->attn_scale; }
-    if (kv8) {
-      const long slab = (long)kvB * H * L * 64;
-      ca.k = (const char*)kv8 + (long)(l * 2 + 0) * slab; ca.v = (const char*)kv8 + (long)(l * 2 + 1) * slab;
-      ca.kscale = kv8_scales + (long)(l * 2 + 0) * kvB * H; ca.vscale = kv8_scales + (long)(l * 2 + 1) * kvB * H;
+    if (k.kv8) {
+      ca.k = (const char*)k.kv8 + cross8.data(l, 0); ca.v = (const char*)k.kv8 + cross8.data(l, 1);
+      ca.kscale = k.kv8_scales + cross8.scale(l, 0); ca.vscale = k.kv8_scales + cross8.scale(l, 1);
     }
-    if (g_timing.buf) {   // one region of ring x layers slots per chain (chain index = first row / rows of a full chain)
-      ca.tstamp = g_timing.buf + 2L * bf.chain * g_timing.ring * c->n_dec_layers;
-      ca.pos = posp; ca.ts_ring = g_timing.ring; ca.ts_layers = c->n_dec_layers; ca.ts_layer = l;
+    if (k.timing_buf) {   // one region of ring x layers slots per chain (chain index = first row / rows of a full chain)
+      ca.tstamp = k.timing_buf + 2L * bf.chain * k.timing_ring * c->n_dec_layers;
+      ca.pos = posp; ca.ts_ring = k.timing_ring; ca.ts_layers = c->n_dec_layers; ca.ts_layer = l;
     }
-    hp = dec::HeadProjP{};
-    hp.h = bf.h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
-    hp.ln_b = hf ? w->dec_ln2_b[l] : nullptr;
-    MH_TRY(launch_cross_q_d<T>(ca, hp, s));
-    if (with_sampler && option(OPT_DECODE_FUSED_TAIL) != 0 &&
-        tail_covers<T>(c, B, wh, wh ? w->dec_co_b[l] : nullptr, wh ? w->dec_fc1_b[l] : nullptr, wh ? w->dec_fc2_b[l] : nullptr)) {
+    MH_TRY(launch_cross_q_d<T>(ca, head_proj(c, bf.h, w->dec_ln2[l], hf ? w->dec_ln2_b[l] : nullptr, w->dec_cq[l]), s));
+    const dec::SkinnyP co = o_gemv(k, w->dec_co[l], w->dec_co_b[l]), wi = ffn_in(k, l), wo = ffn_out(k, l);
+    if (k.with_sampler && option(OPT_DECODE_FUSED_TAIL) != 0 && tail_covers<T>(c, B, wh, co.bias, wi.bias, wo.bias)) {
       // cross O GEMV + residual, norm + wi + activation, wo + residual as ONE launch (the same device code per phase)
       dec::TailP tp{};
-      tp.o.A = bf.attn; tp.o.lda = inner; tp.o.W = w->dec_co[l]; tp.o.ldw = inner; tp.o.B = B; tp.o.N = d; tp.o.K = inner; tp.o.h = bf.h; tp.o.ldh = d;
-      tp.wi.A = bf.h; tp.wi.lda = d; tp.wi.ln_w = w->dec_ln3[l]; tp.wi.eps = c->eps; tp.wi.W = w->dec_wi[l]; tp.wi.ldw = d; tp.wi.B = B;
-      tp.wi.K = d; tp.wi.out = bf.ff; tp.wi.ldo = dff; tp.wi.N = wh ? dff : 2 * dff;
-      tp.wo.A = bf.ff; tp.wo.lda = dff; tp.wo.W = w->dec_wo[l]; tp.wo.ldw = dff; tp.wo.B = B; tp.wo.N = d; tp.wo.K = dff; tp.wo.h = bf.h; tp.wo.ldh = d;
+      tp.o = co; tp.wi = wi; tp.wo = wo;
       const int n_chains = ceil_div(Bfull, B);
-      if (!wh) {
-        MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GEGLU, false>(tp, bf.st, l, n_chains, s)));
-      } else {
-        tp.o.bias = w->dec_co_b[l]; tp.wi.bias = w->dec_fc1_b[l]; tp.wo.bias = w->dec_fc2_b[l];
-        if (hf) { tp.wi.ln_b = w->dec_ln3_b[l]; MH_TRY((launch_tail<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s))); }
-        else MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s)));
-      }
+      if (!wh) MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GEGLU, false>(tp, bf.st, l, n_chains, s)));
+      else if (hf) MH_TRY((launch_tail<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s)));
+      else MH_TRY((launch_tail<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(tp, bf.st, l, n_chains, s)));
       continue;
     }
-    sk = dec::SkinnyP{};
-    sk.A = bf.attn; sk.lda = inner; sk.W = w->dec_co[l]; sk.ldw = inner; sk.B = B; sk.N = d; sk.K = inner; sk.h = bf.h; sk.ldh = d;
-    sk.bias = wh ? w->dec_co_b[l] : nullptr;
-    MH_TRY(skinny_resid<T>(sk, s));
-    // feed forward: T5 gated GELU (wi_0 / wi_1 interleaved, N = 2 d_ff), the Whisper family's biased fc1 + erf GELU
-    sk = dec::SkinnyP{};
-    sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_ln3[l]; sk.eps = c->eps; sk.W = w->dec_wi[l]; sk.ldw = d; sk.B = B;
-    sk.K = d; sk.out = bf.ff; sk.ldo = dff;
-    if (!wh) {
-      sk.N = 2 * dff;
-      MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GEGLU>(sk, s)));
-    } else {
-      sk.N = dff; sk.bias = w->dec_fc1_b[l];
-      if (hf) { sk.ln_b = w->dec_ln3_b[l]; MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(sk, s))); }
-      else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(sk, s)));
-    }
-    sk = dec::SkinnyP{};
-    sk.A = bf.ff; sk.lda = dff; sk.W = w->dec_wo[l]; sk.ldw = dff; sk.B = B; sk.N = d; sk.K = dff; sk.h = bf.h; sk.ldh = d;
-    sk.bias = wh ? w->dec_fc2_b[l] : nullptr;
-    MH_TRY(skinny_resid<T>(sk, s));
+    MH_TRY(skinny_resid<T>(co, s));
+    if (!wh) MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GEGLU>(wi, s)));
+    else if (hf) MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_GELU_ERF, true>(wi, s)));
+    else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_GELU_ERF, true>(wi, s)));
+    MH_TRY(skinny_resid<T>(wo, s));
   }
   dec::SkinnyP sk{};
-  sk.A = bf.h; sk.lda = d; sk.ln_w = w->dec_final_ln; sk.eps = c->eps; sk.W = w->lm_head; sk.ldw = d; sk.B = B;
-  sk.N = c->vocab_out; sk.K = d; sk.out = bf.logits; sk.ldo = c->vocab_out;
+  sk.A = bf.h; sk.lda = c->d_model; sk.ln_w = w->dec_final_ln; sk.eps = c->eps; sk.W = w->lm_head; sk.ldw = c->d_model; sk.B = B;
+  sk.N = c->vocab_out; sk.K = c->d_model; sk.out = bf.logits; sk.ldo = c->vocab_out;
   if (hf) { sk.ln_b = w->dec_final_ln_b; MH_TRY((skinny<T, dec::PRO_LAYERNORM, dec::SK_LOGITS>(sk, s))); }
   else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_LOGITS>(sk, s)));
-  if (!with_sampler) return MH_OK;
-  if (rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, *rows);
+  if (!k.with_sampler) return MH_OK;
+  const SampleP& smp = k.smp;
+  if (k.has_rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, k.rows);
   else hipLaunchKernelGGL((dec_sample_kernel<T, false>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, NoRowSetP{});
   return check_launch("dec_sample_kernel");
 }
@@ -1355,25 +1383,6 @@ __global__ __launch_bounds__(256) void cache_scatter_kernel(T* kc, T* vc, const 
   const int n16 = n_pos * 64 * (int)sizeof(T) / 16;
   for (int i = threadIdx.x; i < n16; i += 256) t4[i] = f4[i];
 }
-
-}  // namespace
-}  // namespace mh
-
-namespace mh {
-namespace {
-struct PrefillBuf;
-int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64_t size, PrefillBuf* out);
-}  // namespace
-}  // namespace mh
-
-extern "C" int64_t mh_t5_decode_workspace_bytes(const MhT5Config* c, int B) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0) return -1;
-  return decode_layout(c, B, nullptr).end + prefill_layout(c, B, c->tgt_len - 1, nullptr, 0, nullptr);   // + batched prompt prefill
-}
-
-namespace mh {
-namespace {
 
 // rows r = b*np + i  <-  dec_embed[prompt[b][i]]   (fp32 residual stream of the prompt prefill)
 template <typename T>
@@ -1435,14 +1444,13 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
   // arch 2 (HF WhisperDecoderLayer): the same with affine LayerNorms, absolute positions added to the embedding, no rotation
   const bool wh = c->arch >= 1, hf = c->arch == 2;
   if (wh && !hf) MH_REQUIRE(w->dec_rope != nullptr, "prefill: the Whisper family needs its rotary table");
-  if (hf) MH_REQUIRE(w->dec_pos && w->dec_final_ln_b, "prefill: arch 2 needs decoder.embed_positions and the LayerNorm biases");
+  MH_TRY(check_arch2_weights(c, w, "prefill"));
   const float* dpos = hf ? w->dec_pos : nullptr;
   const uint8_t* pmask = (hf && c->dec_pos_from_mask) ? prompt_mask : nullptr;
-  if (c->dtype == MH_BF16)
-    hipLaunchKernelGGL(prefill_embed_kernel<bf16_t>, dim3(rows), dim3(256), 0, s, prompt, P, np, (const bf16_t*)w->dec_embed, d, pb.h, dpos, pmask);
-  else
-    hipLaunchKernelGGL(prefill_embed_kernel<float>, dim3(rows), dim3(256), 0, s, prompt, P, np, (const float*)w->dec_embed, d, pb.h, dpos, pmask);
-  MH_TRY(check_launch("prefill_embed_kernel"));
+  MH_TRY(dispatch_dtype(c->dtype, [&](auto t) {
+    hipLaunchKernelGGL(prefill_embed_kernel<decltype(t)>, dim3(rows), dim3(256), 0, s, prompt, P, np, (const decltype(t)*)w->dec_embed, d, pb.h, dpos, pmask);
+    return check_launch("prefill_embed_kernel");
+  }));
   if (hipMemsetAsync(pb.vt, 0, (size_t)B * inner * np_pad * es, s) != hipSuccess) return check_launch("memset prefill vt");
   if (hipMemsetAsync(pb.cross_vt, 0, (size_t)c->n_dec_layers * kvB * inner * pb.Lpad * es, s) != hipSuccess)
     return check_launch("memset cross vt");
@@ -1466,14 +1474,12 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
     if (wh && !hf) {   // rotate-half RoPE on q (all prompt positions) and on the keys just cached; position = column of the padded prompt
       const long wq = (long)rows * H * 4, wk = (long)B * H * np * 4;
       const float* rope = (local && w->dec_rope_local) ? w->dec_rope_local : w->dec_rope;
-      if (c->dtype == MH_BF16) {
-        hipLaunchKernelGGL(mh::rope_qk_kernel<bf16_t>, dim3((unsigned)((wq + 255) / 256)), dim3(256), 0, s, (bf16_t*)pb.q, inner, (long)rows, np, H, rope);
-        hipLaunchKernelGGL(mh::rope_cache_kernel<bf16_t>, dim3((unsigned)((wk + 255) / 256)), dim3(256), 0, s, (bf16_t*)kc, (long)B * H, tgt, np, rope);
-      } else {
-        hipLaunchKernelGGL(mh::rope_qk_kernel<float>, dim3((unsigned)((wq + 255) / 256)), dim3(256), 0, s, (float*)pb.q, inner, (long)rows, np, H, rope);
-        hipLaunchKernelGGL(mh::rope_cache_kernel<float>, dim3((unsigned)((wk + 255) / 256)), dim3(256), 0, s, (float*)kc, (long)B * H, tgt, np, rope);
-      }
-      MH_TRY(check_launch("rope (prefill)"));
+      MH_TRY(dispatch_dtype(c->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mh::rope_qk_kernel<T>, dim3((unsigned)((wq + 255) / 256)), dim3(256), 0, s, (T*)pb.q, inner, (long)rows, np, H, rope);
+        hipLaunchKernelGGL(mh::rope_cache_kernel<T>, dim3((unsigned)((wk + 255) / 256)), dim3(256), 0, s, (T*)kc, (long)B * H, tgt, np, rope);
+        return check_launch("rope (prefill)");
+      }));
     }
     AttnArgs a{};
     a.q = pb.q; a.q_rs = (long)inner * es; a.q_bs = (long)np * inner * es;
@@ -1574,6 +1580,12 @@ DevicePool* device_pool(int dev) {
 }  // namespace
 }  // namespace mh
 
+extern "C" int64_t mh_t5_decode_workspace_bytes(const MhT5Config* c, int B) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  if (!c || B <= 0) return -1;
+  return decode_layout(c, B, nullptr).end + prefill_layout(c, B, c->tgt_len - 1, nullptr, 0, nullptr);   // + batched prompt prefill
+}
+
 // ---- e4m3 copy of the cross-attention K / V -------------------------------------------------------------------------
 // one workgroup per (layer, k|v, row, head) slab of L x 64 bf16: absolute maximum, then x / scale -> OCP e4m3
 __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(const bf16_t* src, uint8_t* dst, float* scales, int L) {
@@ -1617,8 +1629,7 @@ __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(const bf16_t* src, ui
 extern "C" int64_t mh_t5_cross_kv_fp8_bytes(const MhT5Config* c, int B) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   if (!c || B <= 0) return -1;
-  const int64_t data = (int64_t)c->n_dec_layers * 2 * B * c->n_heads * c->src_len * 64;
-  return align256(data) + align256((int64_t)c->n_dec_layers * 2 * B * c->n_heads * 4);
+  return cross_kv8_layout(c, B).total;
 }
 
 extern "C" int mh_t5_quantize_cross_kv(const MhT5Config* c, const void* cross_kv, int B, void* out, void* stream) {
@@ -1626,10 +1637,10 @@ extern "C" int mh_t5_quantize_cross_kv(const MhT5Config* c, const void* cross_kv
   MH_TRY(check_cfg(c, "mh_t5_quantize_cross_kv"));
   MH_REQUIRE(cross_kv && out && B > 0, "mh_t5_quantize_cross_kv: null argument");
   MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_quantize_cross_kv: needs bf16 storage");
-  const int64_t data = (int64_t)c->n_dec_layers * 2 * B * c->n_heads * c->src_len * 64;
-  const int slabs = c->n_dec_layers * 2 * B * c->n_heads;
+  const Kv8Layout ly = cross_kv8_layout(c, B);
+  const int slabs = c->n_dec_layers * 2 * (int)ly.plane_scales;   // one workgroup and one scale per (layer, k|v, row, head)
   hipLaunchKernelGGL(kv_quant_fp8_kernel, dim3(slabs), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)cross_kv,
-                     (uint8_t*)out, reinterpret_cast<float*>((char*)out + align256(data)), c->src_len);
+                     (uint8_t*)out, reinterpret_cast<float*>((char*)out + ly.scales_offset), c->src_len);
   return check_launch("kv_quant_fp8_kernel");
 }
 
@@ -1668,8 +1679,7 @@ extern "C" int64_t mh_t5_self_kv_fp8_bytes(const MhT5Config* c, int B) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
   if (!c || B <= 0) return -1;
   if (c->dtype != MH_BF16) { mh::set_error("mh_t5_self_kv_fp8_bytes: the e4m3 self-attention cache needs bf16 storage"); return -1; }
-  const int64_t rows = (int64_t)c->n_dec_layers * 2 * B * c->n_heads * c->tgt_len;
-  return align256(rows * 64) + align256(rows * 4);
+  return self_kv8_layout(c, B).total;
 }
 
 extern "C" int mh_t5_decode_self_cache(const MhT5Config* c, int B, void* workspace, void** k, void** v) {
@@ -1688,12 +1698,12 @@ namespace mh {
 // sampling struct and the kernel choice (the position and every per-call state live in device memory), so a later call
 // whose inputs are byte-for-byte the same description -- the normal case of an engine that decodes window after window out
 // of the same workspace with the same prompt length -- replays the graph of the earlier one instead of capturing and
-// instantiating ~75 nodes again.  The key is the exact byte string of everything enqueue_step() receives plus every option
-// value and the timing hook (exact compare: a spurious difference costs a capture, never a wrong graph).  Small LRU; an entry in
-// use by a concurrent call is never shared (hipGraphExec objects are single-flight) nor evicted.  Option decode_graph_cache = 0
-// switches it off.
+// instantiating ~75 nodes again.  The key comes from ONE place: step_graph_key() over the StepCall that enqueue_step() is given,
+// the only thing it reads besides the options -- so whatever a step depends on is in its key (exact compare: a spurious
+// difference costs a capture, never a wrong graph).  Small LRU; an entry in use by a concurrent call is never shared
+// (hipGraphExec objects are single-flight) nor evicted.  Option decode_graph_cache = 0 switches it off.
 struct StepGraphEntry {
-  std::vector<unsigned char> key;
+  std::vector<unsigned char> key;      // step_graph_key(StepCall)
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   uint64_t stamp = 0;
@@ -1704,6 +1714,35 @@ static std::mutex g_step_graph_mu;
 static std::vector<StepGraphEntry*> g_step_graphs;
 static uint64_t g_step_graph_clock = 0;
 static std::atomic<long> g_step_graph_hits{0}, g_step_graph_misses{0};
+
+// The bytes of the StepCall, then what it depends on beyond them: *c without the address of its option set, *w, every option value,
+// the device, the storage type.  Scrubbed, here and nowhere else: the addresses of c and w (their contents follow); seed and rng_row0
+// (they reach the sampler through DecState, not through the graph); under the row form what that sampler reads per row instead.
+static std::vector<unsigned char> step_graph_key(const StepCall& call) {
+  std::vector<unsigned char> key;
+  auto put = [&key](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
+  StepCall k;
+  memcpy(&k, &call, sizeof(k));
+  k.c = nullptr; k.w = nullptr;
+  MhSampling& sp = k.smp.sp;
+  sp.seed = 0; sp.rng_row0 = 0;
+  if (k.has_rows) {
+    k.smp.eos_table = nullptr;
+    sp.cfg_scale = sp.cfg_scale > 1.0f ? 2.f : 1.f;   // (guidance on / off is the call's, the scale each pair's own)
+    sp.temperature = sp.top_p = sp.timeshift_bias = 0.f;
+    sp.top_k = sp.lookback_mask_end = 0;
+    for (int j = 0; j < 3; ++j) sp.cond_temp[j] = 0.f;
+  }
+  MhT5Config cc = *call.c;
+  cc.options = nullptr;
+  long opts[OPT_COUNT];
+  for (int o = 0; o < OPT_COUNT; ++o) opts[o] = option(o);
+  int dev_id = 0;
+  (void)hipGetDevice(&dev_id);
+  const int ids[2] = {dev_id, call.c->dtype == MH_BF16 ? 1 : 0};
+  put(&k, sizeof(k)); put(&cc, sizeof(cc)); put(call.w, sizeof(*call.w)); put(opts, sizeof(opts)); put(ids, sizeof(ids));
+  return key;
+}
 
 static StepGraphEntry* step_graph_acquire(const std::vector<unsigned char>& key) {
   std::lock_guard<std::mutex> lk(g_step_graph_mu);
@@ -1744,49 +1783,187 @@ static void step_graph_release(StepGraphEntry* e) {
   std::lock_guard<std::mutex> lk(g_step_graph_mu);
   e->in_use = false;
 }
-}  // namespace mh
 
-extern "C" int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset) {
-  if (hits) *hits = mh::g_step_graph_hits.load();
-  if (misses) *misses = mh::g_step_graph_misses.load();
-  if (reset) { mh::g_step_graph_hits.store(0); mh::g_step_graph_misses.store(0); }
+// A chain of the running call and the owner of its step graph: the cross-call cache (`cached`: handed back when the call ends) or the
+// call itself (destroyed with it, after the call's last synchronise)
+struct Chain {
+  hipStream_t stream = nullptr; DecState* st = nullptr;
+  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; StepGraphEntry* cached = nullptr;
+  Chain() = default;
+  Chain(const Chain&) = delete;
+  Chain& operator=(const Chain&) = delete;
+  ~Chain() {
+    if (cached) { step_graph_release(cached); return; }
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+  }
+};
+
+// A chain enters the call on its own stream, behind the caller's work so far (`fork`): dec_init_kernel, then one step of the chain (every
+// kernel reads the position from device memory) as a graph for replay: an earlier call's, if its key is this one's, else captured now
+static int start_chain(const StepCall& call, int start_pos, hipEvent_t fork, const char* who, Chain* ch) {
+  hipStream_t cs = ch->stream;
+  ch->st = call.bf.st;
+  if (hipStreamWaitEvent(cs, fork, 0) != hipSuccess) return check_launch("fork wait");
+  if (call.c->dtype == MH_BF16) hipLaunchKernelGGL(dec_init_kernel<bf16_t>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
+  else hipLaunchKernelGGL(dec_init_kernel<float>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
+  MH_TRY(check_launch("dec_init_kernel"));
+  std::vector<unsigned char> key;
+  if (option(OPT_DECODE_GRAPH_CACHE) != 0) {
+    key = step_graph_key(call);
+    if ((ch->cached = step_graph_acquire(key))) { ch->exec = ch->cached->exec; g_step_graph_hits.fetch_add(1); return MH_OK; }
+    g_step_graph_misses.fetch_add(1);
+  }
+  if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) return check_launch("begin capture");
+  const int rce = dispatch_dtype(call.c->dtype, [&](auto t) { return enqueue_step<decltype(t)>(call, cs); });
+  const hipError_t ce = hipStreamEndCapture(cs, &ch->graph);
+  if (rce != MH_OK) return rce;
+  if (ce != hipSuccess || !ch->graph) { set_error("%s: stream capture failed: %s", who, hipGetErrorString(ce)); return MH_ERR_LAUNCH; }
+  if (hipGraphInstantiate(&ch->exec, ch->graph, nullptr, nullptr, 0) != hipSuccess) return check_launch("graph instantiate");
+  if (!key.empty() && (ch->cached = step_graph_insert(std::move(key), ch->graph, ch->exec))) ch->graph = nullptr;   // the cache owns both now
   return MH_OK;
 }
 
-// mh_t5_generate (self_kv_fp8 == NULL), mh_t5_generate_skv8 (the caller's e4m3 shadow of the self-attention cache) and
-// mh_t5_generate_rows (rowset != NULL: the sampler's settings per returned row)
-static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                         const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
-                         const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
-                         const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                         void* stream, void* self_kv_fp8, const char* who,   // who: the entry the caller used (error messages)
-                         const mh::RowSetP* rowset = nullptr) {
+// The host's look at a chain between two bursts of replays: DecState::n_running and ::tail_err in one 8-byte read
+static int poll_chain(const Chain& ch, bool* running) {
+  int word[2] = {1, 0};
+  if (hipMemcpyAsync(word, &ch.st->n_running, 8, hipMemcpyDeviceToHost, ch.stream) != hipSuccess ||
+      hipStreamSynchronize(ch.stream) != hipSuccess)
+    return MH_ERR_LAUNCH;
+  *running = word[0] != 0;
+  return word[1] != 0 ? MH_ERR_DECODE_TAIL_TIMEOUT : MH_OK;
+}
+
+// The launcher of `n` chains from the calling thread: bursts of poll_every replays each, interleaved, then a poll of each (none behind the
+// last burst, none under teacher forcing: poll = false).  A chain is left out once its rows are done or it failed (rcs[i]).
+static void run_chains(const Chain* chains, int n, int total_steps, int poll_every, bool poll, int* rcs) {
+  bool alive[kMaxChains];
+  for (int ci = 0; ci < n; ++ci) alive[ci] = true;
+  for (int step = 0; step < total_steps;) {
+    const int burst = total_steps - step < poll_every ? total_steps - step : poll_every;
+    for (int i = 0; i < burst; ++i)
+      for (int ci = 0; ci < n; ++ci)
+        if (alive[ci] && rcs[ci] == MH_OK && hipGraphLaunch(chains[ci].exec, chains[ci].stream) != hipSuccess) rcs[ci] = MH_ERR_LAUNCH;
+    step += burst;
+    bool any = false;
+    for (int ci = 0; ci < n; ++ci) {
+      if (!alive[ci] || rcs[ci] != MH_OK) continue;
+      if (step < total_steps && poll && (rcs[ci] = poll_chain(chains[ci], &alive[ci])) != MH_OK) continue;
+      any = any || alive[ci];
+    }
+    if (!any) break;
+  }
+}
+// Replaying a ~110-node graph costs ~0.4 ms of HOST time on ROCm 7.2, so every chain gets a launcher thread of its own (the chains are
+// independent); option decode_launch_threads = 0: one launcher for all (slower on the host side; the same kernels and arguments)
+static int launch_chains(const Chain* chains, int used, int total_steps, int poll_every, bool poll, const char* who) {
+  int rcs[kMaxChains] = {};
+  if (used <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
+    run_chains(chains, used, total_steps, poll_every, poll, rcs);
+  } else {
+    std::vector<std::thread> th;
+    const MhOptionSet* set = current_option_set();   // thread-local in the caller: re-installed in every launcher
+    for (int ci = 1; ci < used; ++ci)
+      th.emplace_back([&, ci, set] { OptionScope sc(set); run_chains(&chains[ci], 1, total_steps, poll_every, poll, &rcs[ci]); });
+    run_chains(&chains[0], 1, total_steps, poll_every, poll, &rcs[0]);
+    for (auto& t : th) t.join();
+  }
+  int rc = MH_OK;
+  for (int ci = 0; ci < used; ++ci)
+    if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
+    else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
+  return rc;
+}
+
+// What mh_t5_generate, mh_t5_generate_skv8 (self_kv_fp8: the caller's e4m3 shadow of the self-attention cache, else NULL) and
+// mh_t5_generate_rows (rowset: the sampler's settings per returned row, else NULL) were given; who: the entry, for error messages
+struct GenerateArgs {
+  const MhT5Config* c; const MhT5Weights* w; const void* cross_kv; int B; const int32_t* prompt; const uint8_t* prompt_mask; int P;
+  const uint8_t* eos_table; const MhSampling* sp; int32_t* tokens; int32_t* n_steps_out; float* logits_dump; const int32_t* forced;
+  void* workspace; int64_t workspace_bytes; int poll_every; void* stream; void* self_kv_fp8; const RowSetP* rowset; const char* who;
+};
+
+static int check_generate_args(const GenerateArgs& a) {
+  const MhT5Config* c = a.c;
+  const MhSampling* sp = a.sp;
+  const char* who = a.who;
   MH_TRY(check_cfg(c, who));
   MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && cross_kv && prompt && (eos_table || rowset) && sp && tokens && n_steps_out && workspace,
+  MH_REQUIRE(a.w && a.cross_kv && a.prompt && (a.eos_table || a.rowset) && sp && a.tokens && a.n_steps_out && a.workspace,
              "%s: null argument", who);
-  MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
-  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, B);
-  MH_REQUIRE(P >= 1 && P < sp->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
+  MH_REQUIRE(a.stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
+  MH_REQUIRE(a.B > 0 && a.B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, a.B);
+  MH_REQUIRE(a.P >= 1 && a.P < sp->max_length, "%s: prompt length %d must be in [1, max_length)", who, a.P);
   MH_REQUIRE(sp->max_length <= c->tgt_len, "%s: max_length %d exceeds tgt_len %d", who, sp->max_length, c->tgt_len);
-  MH_REQUIRE(rowset || sp->temperature > 0.f, "%s: temperature must be > 0", who);
+  MH_REQUIRE(a.rowset || sp->temperature > 0.f, "%s: temperature must be > 0", who);
   MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "%s: too many sos ids", who);
-  const bool cfg = sp->cfg_scale > 1.0f;
-  MH_REQUIRE(!cfg || B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
+  MH_REQUIRE(!(sp->cfg_scale > 1.0f) || a.B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
   MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "%s: n_cond %d not in [0, 3]", who, sp->n_cond);
   for (int j = 0; j < sp->n_cond; ++j)
-    MH_REQUIRE((rowset || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
+    MH_REQUIRE((a.rowset || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
   MH_REQUIRE(sp->tok_flags || (sp->n_cond == 0 && !sp->lookback_types_first),
              "%s: tok_flags is required by the conditional temperature / types_first lookback processors", who);
-  const int kvB = cfg ? B / 2 : B;
   MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "%s: workspace too small", who);
-  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "%s: arch 2 needs decoder.embed_positions and the LayerNorm biases", who);
-  hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
+  MH_REQUIRE(a.workspace_bytes >= mh_t5_decode_workspace_bytes(c, a.B), "%s: workspace too small", who);
+  return check_arch2_weights(c, a.w, who);
+}
 
-  const DecodeLayout ly = decode_layout(c, B, workspace);
+// Chain ci of the call as a StepCall: rows [ci rows_per, + Bc) of every buffer, of the e4m3 copies and of the sampler's view
+// (Bc <= 0: the batch has no such chain).  self8: the shadow of the whole batch, or NULL.
+static void chain_call(const GenerateArgs& a, const DecodeLayout& ly, int ci, int rows_per, uint8_t* self8, StepCall* k) {
+  const MhT5Config* c = a.c;
+  const MhSampling* sp = a.sp;
   const DecBuffers& all = ly.bf;
+  const int B = a.B, P = a.P, es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
+  const bool cfg = sp->cfg_scale > 1.0f;
+  const int b0 = ci * rows_per;
+  step_call_init(k, c, a.w);
+  k->Bc = (b0 + rows_per <= B) ? rows_per : B - b0;
+  k->Bfull = B; k->kvB = cfg ? B / 2 : B; k->P = P; k->with_sampler = 1;
+  k->cross_kv = (const char*)a.cross_kv + (long)b0 * H * c->src_len * 64 * es;
+  k->prompt_mask = a.prompt_mask ? a.prompt_mask + (long)b0 * P : nullptr;
+  if (a.rowset) { k->has_rows = 1; k->rows.rows = a.rowset->rows; k->rows.eos_tables = a.rowset->eos_tables; k->rows.n_eos_sets = a.rowset->n_eos_sets; }
+  DecBuffers& bf = k->bf;
+  bf.chain = ci;
+  bf.h = all.h + (long)b0 * d;
+  bf.attn = (char*)all.attn + (long)b0 * inner * es;
+  bf.ff = (char*)all.ff + (long)b0 * c->d_ff * es;
+  bf.logits = all.logits + (long)b0 * V;
+  bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
+  bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
+  if (self8) {   // the chain's first row of the shadow and of its scales (the same b0 offsets as the bf16 caches)
+    bf.self8 = self8 + (long)b0 * inner * c->tgt_len;
+    bf.self8_scales = reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset) + (long)b0 * H * c->tgt_len;
+  }
+  bf.finished = all.finished + b0;
+  bf.finish_col = all.finish_col; bf.last_ts = all.last_ts;
+  bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
+  if (sp->cross_kv_fp8) {   // the chain's first row of the packed e4m3 copy and of its scales
+    k->kv8 = (const char*)sp->cross_kv_fp8 + (long)b0 * H * c->src_len * 64;
+    k->kv8_scales = reinterpret_cast<const float*>((const char*)sp->cross_kv_fp8 + cross_kv8_layout(c, k->kvB).scales_offset) + (long)b0 * H;
+  }
+  SampleP& smp = k->smp;
+  smp.logits = bf.logits; smp.ldl = V; smp.V = V; smp.tokens = a.tokens; smp.max_length = sp->max_length;
+  smp.forced = a.forced; smp.eos_table = a.eos_table; smp.finished = all.finished; smp.finish_col = all.finish_col;
+  smp.last_ts_val = all.last_ts; smp.logits_dump = a.logits_dump; smp.dec_embed = a.w->dec_embed; smp.h = bf.h;
+  smp.d = d; smp.st = bf.st; smp.B = B; smp.P = P; smp.b0 = b0;
+  memcpy(&smp.sp, sp, sizeof(*sp));
+  smp.proc = ly.proc; smp.hist_scores = ly.hist_scores; smp.pair = cfg ? B / 2 : 0; smp.chain_rows = k->Bc;
+  if (c->arch == 2) {
+    smp.dec_pos = a.w->dec_pos;
+    smp.pos_off = c->dec_pos_from_mask ? ly.pos_off : nullptr;
+    smp.prompt_mask = a.prompt_mask;
+  }
+}
+
+static int generate_impl(const GenerateArgs& a) {
+  MH_TRY(check_generate_args(a));
+  const MhT5Config* c = a.c;
+  const MhSampling* sp = a.sp;
+  const int B = a.B, P = a.P;
+  hipStream_t s = (hipStream_t)a.stream;
+  const bool cfg = sp->cfg_scale > 1.0f;
+  const DecodeLayout ly = decode_layout(c, B, a.workspace);
   // a CFG pair spans both halves of the batch and the (batch-wide) conditional temperature reads row 0's history: one chain
   const int n_chains = (cfg || (sp->n_cond > 0 && !sp->cond_per_row)) ? 1 : pick_chains(B);
   const int rows_per = ceil_div(B, n_chains);
@@ -1801,235 +1978,72 @@ static int generate_impl(const MhT5Config* c, const MhT5Weights* w, const void* 
   std::lock_guard<std::mutex> pool_guard(dp->mu);
   ChainPool& g_pool = dp->pool;
   MH_TRY(g_pool.init());
-  hipStream_t chain_stream[kMaxChains];
-  for (int i = 0; i < kMaxChains; ++i) chain_stream[i] = g_pool.streams[i];
+  Chain chains[kMaxChains];   // (their graphs are released / destroyed on every return path below)
+  for (int i = 0; i < kMaxChains; ++i) chains[i].stream = g_pool.streams[i];
 
   // tokens[:, :P] = prompt; the remainder is produced by the sampler
-  if (hipMemcpy2DAsync(tokens, (size_t)sp->max_length * 4, prompt, (size_t)P * 4, (size_t)P * 4, B,
+  if (hipMemcpy2DAsync(a.tokens, (size_t)sp->max_length * 4, a.prompt, (size_t)P * 4, (size_t)P * 4, B,
                        hipMemcpyDeviceToDevice, s) != hipSuccess)
     return check_launch("prompt copy");
   // batched prompt prefill (positions 0..P-2); MH_DECODE_PREFILL=0 feeds the prompt token by token instead
   int start_pos = 0;
-  {
-    if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {
-      PrefillBuf pb;
-      prefill_layout(c, B, P - 1, (char*)workspace + ly.end, workspace_bytes - ly.end, &pb);
-      MH_REQUIRE(ly.end + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= workspace_bytes,
-                 "%s: workspace too small for the prompt prefill", who);
-      MH_TRY(prefill_prompt(c, w, cross_kv, B, kvB, prompt, prompt_mask, P, P - 1, all.self_k, all.self_v, pb, s));
-      start_pos = P - 1;
-    }
+  if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {
+    PrefillBuf pb;
+    prefill_layout(c, B, P - 1, (char*)a.workspace + ly.end, a.workspace_bytes - ly.end, &pb);
+    MH_REQUIRE(ly.end + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= a.workspace_bytes,
+               "%s: workspace too small for the prompt prefill", a.who);
+    MH_TRY(prefill_prompt(c, a.w, a.cross_kv, B, cfg ? B / 2 : B, a.prompt, a.prompt_mask, P, P - 1, ly.bf.self_k, ly.bf.self_v, pb, s));
+    start_pos = P - 1;
   }
-  // the shadow: e4m3 rows, then (256-byte aligned) their scales.  The prompt positions the batched prefill wrote (they attended each
-  // other through the bf16 cache) are quantised in one pass before the first token step; every token step appends its own row
-  uint8_t* self8 = (uint8_t*)self_kv_fp8;
-  float* self8_scales = nullptr;
-  if (self8) {
-    const int64_t rows = (int64_t)c->n_dec_layers * 2 * B * H * c->tgt_len;
-    self8_scales = reinterpret_cast<float*>(self8 + align256(rows * 64));
-    if (start_pos > 0) {
-      const long n_slabs = (long)B * H;
-      hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
-                         (const bf16_t*)all.self_k, (const bf16_t*)all.self_v, self8, self8_scales, n_slabs, (long)start_pos,
-                         (long)c->tgt_len);
-      MH_TRY(check_launch("self_kv_quant_rows_kernel"));
-    }
+  // the shadow: the prompt positions the batched prefill wrote (they attended each other through the bf16 cache) are quantised in
+  // one pass before the first token step; every token step appends its own row
+  uint8_t* self8 = (uint8_t*)a.self_kv_fp8;
+  if (self8 && start_pos > 0) {
+    const long n_slabs = (long)B * c->n_heads;
+    hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
+                       (const bf16_t*)ly.bf.self_k, (const bf16_t*)ly.bf.self_v, self8,
+                       reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)start_pos, (long)c->tgt_len);
+    MH_TRY(check_launch("self_kv_quant_rows_kernel"));
   }
   if (hipEventRecord(g_pool.fork, s) != hipSuccess) return check_launch("fork record");
 
-  const bool bf16 = c->dtype == MH_BF16;
-  hipGraph_t graphs[kMaxChains] = {};
-  hipGraphExec_t execs[kMaxChains] = {};
-  StepGraphEntry* cached[kMaxChains] = {};     // chains whose graph lives in the cross-call cache (not destroyed below)
-  DecState* states[kMaxChains] = {};
   int used = 0, rc = MH_OK;
   for (int ci = 0; ci < n_chains && rc == MH_OK; ++ci) {
-    const int b0 = ci * rows_per;
-    const int Bc = (b0 + rows_per <= B) ? rows_per : B - b0;
-    if (Bc <= 0) break;
-    hipStream_t cs = chain_stream[ci];
-    if (hipStreamWaitEvent(cs, g_pool.fork, 0) != hipSuccess) { rc = check_launch("fork wait"); break; }
-    DecBuffers bf = all;
-    bf.chain = ci;
-    bf.h = all.h + (long)b0 * d;
-    bf.attn = (char*)all.attn + (long)b0 * inner * es;
-    bf.ff = (char*)all.ff + (long)b0 * c->d_ff * es;
-    bf.logits = all.logits + (long)b0 * V;
-    bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
-    bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
-    if (self8) {   // the chain's first row of the shadow and of its scales (the same b0 offsets as the bf16 caches)
-      bf.self8 = self8 + (long)b0 * inner * c->tgt_len;
-      bf.self8_scales = self8_scales + (long)b0 * H * c->tgt_len;
-    }
-    bf.finished = all.finished + b0;
-    bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
-    states[ci] = bf.st;
-    const void* ckv = (const char*)cross_kv + (long)b0 * H * c->src_len * 64 * es;
-    const uint8_t* pm = prompt_mask ? prompt_mask + (long)b0 * P : nullptr;
-
-    SampleP smp{};
-    smp.logits = bf.logits; smp.ldl = V; smp.V = V; smp.tokens = tokens; smp.max_length = sp->max_length;
-    smp.forced = forced; smp.eos_table = eos_table; smp.finished = all.finished; smp.finish_col = all.finish_col;
-    smp.last_ts_val = all.last_ts; smp.logits_dump = logits_dump; smp.dec_embed = w->dec_embed; smp.h = bf.h;
-    smp.d = d; smp.sp = *sp; smp.st = bf.st; smp.B = B; smp.P = P; smp.b0 = b0;
-    smp.proc = ly.proc; smp.hist_scores = ly.hist_scores; smp.pair = cfg ? B / 2 : 0; smp.chain_rows = Bc;
-    if (c->arch == 2) {
-      smp.dec_pos = w->dec_pos;
-      smp.pos_off = c->dec_pos_from_mask ? ly.pos_off : nullptr;
-      smp.prompt_mask = prompt_mask;
-    }
-
-    if (bf16) hipLaunchKernelGGL(dec_init_kernel<bf16_t>, dim3(Bc), dim3(256), 0, cs, smp, Bc, start_pos);
-    else hipLaunchKernelGGL(dec_init_kernel<float>, dim3(Bc), dim3(256), 0, cs, smp, Bc, start_pos);
-    rc = check_launch("dec_init_kernel");
-    if (rc != MH_OK) break;
-    const void* kv8 = nullptr;
-    const float* kv8_scales = nullptr;
-    if (sp->cross_kv_fp8) {   // packed e4m3 copy: data, then (256-byte aligned) the scales
-      const int64_t data_bytes = (int64_t)c->n_dec_layers * 2 * kvB * H * c->src_len * 64;
-      kv8 = (const char*)sp->cross_kv_fp8 + (long)b0 * H * c->src_len * 64;
-      kv8_scales = reinterpret_cast<const float*>((const char*)sp->cross_kv_fp8 + align256(data_bytes)) + (long)b0 * H;
-    }
-    // one step of this chain (every kernel reads the position from device memory) as a graph for replay: an earlier call's, if
-    // its description is byte for byte this one's, else captured now
-    std::vector<unsigned char> key;
-    if (option(OPT_DECODE_GRAPH_CACHE) != 0) {
-      auto put = [&key](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
-      MhT5Config cc = *c;
-      cc.options = nullptr;
-      long opts[OPT_COUNT];
-      for (int o = 0; o < OPT_COUNT; ++o) opts[o] = option(o);
-      int dev_id = 0;
-      (void)hipGetDevice(&dev_id);
-      // (the row form is another sampler with two more pointers in its arguments: keyed apart from the uniform form)
-      const void* ptrs[] = {ckv, pm, kv8, kv8_scales, (const void*)g_timing.buf, rowset ? (const void*)rowset->rows : nullptr,
-                            rowset ? (const void*)rowset->eos_tables : nullptr};
-      const int ints[] = {Bc, B, kvB, P, g_timing.ring, dev_id, bf16 ? 1 : 0, rowset ? 1 : 0, rowset ? rowset->n_eos_sets : 0};
-      put(&cc, sizeof(cc)); put(opts, sizeof(opts)); put(w, sizeof(*w)); put(ptrs, sizeof(ptrs)); put(ints, sizeof(ints));
-      SampleP smp_key = smp;          // (seed and rng_row0 reach the sampler through DecState, not through the graph)
-      smp_key.sp.seed = 0;
-      smp_key.sp.rng_row0 = 0;
-      if (rowset) {                   // the row form ignores these: calls that differ in them alone replay one graph
-        smp_key.eos_table = nullptr;
-        smp_key.sp.cfg_scale = cfg ? 2.f : 1.f;   // (guidance on / off is the call's, the scale each pair's own)
-        smp_key.sp.temperature = smp_key.sp.top_p = smp_key.sp.timeshift_bias = 0.f;
-        smp_key.sp.top_k = smp_key.sp.lookback_mask_end = 0;
-        for (int j = 0; j < 3; ++j) smp_key.sp.cond_temp[j] = 0.f;
-      }
-      put(&bf, sizeof(bf)); put(&smp_key, sizeof(smp_key));
-      if (StepGraphEntry* e = step_graph_acquire(key)) {
-        cached[ci] = e;
-        execs[ci] = e->exec;
-        g_step_graph_hits.fetch_add(1);
-        ++used;
-        continue;
-      }
-      g_step_graph_misses.fetch_add(1);
-    }
-    if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) { rc = check_launch("begin capture"); break; }
-    int rce = bf16 ? enqueue_step<bf16_t>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales, true, 0, rowset)
-                   : enqueue_step<float>(c, w, ckv, Bc, B, kvB, pm, P, bf, smp, cs, kv8, kv8_scales, true, 0, rowset);
-    hipError_t ce = hipStreamEndCapture(cs, &graphs[ci]);
+    StepCall call;
+    chain_call(a, ly, ci, rows_per, self8, &call);
+    if (call.Bc <= 0) break;
     ++used;
-    if (rce != MH_OK) { rc = rce; break; }
-    if (ce != hipSuccess || !graphs[ci]) { set_error("%s: stream capture failed: %s", who, hipGetErrorString(ce)); rc = MH_ERR_LAUNCH; break; }
-    if (hipGraphInstantiate(&execs[ci], graphs[ci], nullptr, nullptr, 0) != hipSuccess) { rc = check_launch("graph instantiate"); break; }
-    if (!key.empty()) {
-      if (StepGraphEntry* e = step_graph_insert(std::move(key), graphs[ci], execs[ci])) {
-        cached[ci] = e;          // the cache owns graph and exec now
-        graphs[ci] = nullptr;
-      }
-    }
+    rc = start_chain(call, start_pos, g_pool.fork, a.who, &chains[ci]);
   }
 
   const int total_steps = sp->max_length - 1 - start_pos;   // positions start_pos .. max_length-2 are fed
-  if (poll_every <= 0) poll_every = 16;
-  // One launcher per chain.  Replaying a ~110-node graph costs ~0.4 ms of HOST time on ROCm 7.2, so with more
-  // than one chain the launches are issued from one host thread per chain (the chains are independent: each
-  // polls only its own "rows still running" word and stops launching when its rows are done).
-  auto run_chain = [&](int ci) -> int {
-    int step = 0;
-    while (step < total_steps) {
-      const int burst = total_steps - step < poll_every ? total_steps - step : poll_every;
-      for (int i = 0; i < burst; ++i) {
-        if (hipGraphLaunch(execs[ci], chain_stream[ci]) != hipSuccess) return MH_ERR_LAUNCH;
-      }
-      step += burst;
-      if (step < total_steps && !forced) {
-        int word[2] = {1, 0};   // DecState::n_running, ::tail_err
-        if (hipMemcpyAsync(word, &states[ci]->n_running, 8, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
-            hipStreamSynchronize(chain_stream[ci]) != hipSuccess)
-          return MH_ERR_LAUNCH;
-        if (word[1] != 0) return MH_ERR_DECODE_TAIL_TIMEOUT;
-        if (word[0] == 0) break;
-      }
-    }
-    return MH_OK;
-  };
-  if (rc == MH_OK) {
-    int rcs[kMaxChains] = {};
-    if (used <= 1) {
-      if (used == 1) rcs[0] = run_chain(0);
-    } else if (option(OPT_DECODE_LAUNCH_THREADS) == 0) {
-      // one thread, the chains' steps interleaved (slower on the host side; the same kernels with the same arguments)
-      bool alive[kMaxChains];
-      for (int ci = 0; ci < used; ++ci) alive[ci] = true;
-      for (int step = 0; step < total_steps;) {
-        const int burst = total_steps - step < poll_every ? total_steps - step : poll_every;
-        for (int i = 0; i < burst; ++i)
-          for (int ci = 0; ci < used; ++ci) {
-            if (!alive[ci] || rcs[ci] != MH_OK) continue;
-            if (hipGraphLaunch(execs[ci], chain_stream[ci]) != hipSuccess) rcs[ci] = MH_ERR_LAUNCH;
-          }
-        step += burst;
-        bool any = false;
-        for (int ci = 0; ci < used; ++ci) {
-          if (!alive[ci] || rcs[ci] != MH_OK) continue;
-          if (step < total_steps && !forced) {
-            int word[2] = {1, 0};   // DecState::n_running, ::tail_err
-            if (hipMemcpyAsync(word, &states[ci]->n_running, 8, hipMemcpyDeviceToHost, chain_stream[ci]) != hipSuccess ||
-                hipStreamSynchronize(chain_stream[ci]) != hipSuccess) { rcs[ci] = MH_ERR_LAUNCH; continue; }
-            if (word[1] != 0) { rcs[ci] = MH_ERR_DECODE_TAIL_TIMEOUT; continue; }
-            if (word[0] == 0) alive[ci] = false;
-          }
-          any = any || alive[ci];
-        }
-        if (!any) break;
-      }
-    } else {
-      std::vector<std::thread> th;
-      const MhOptionSet* set = current_option_set();   // thread-local in the caller: re-installed in every launcher
-      for (int ci = 1; ci < used; ++ci) th.emplace_back([&, ci, set] { OptionScope sc(set); rcs[ci] = run_chain(ci); });
-      rcs[0] = run_chain(0);
-      for (auto& t : th) t.join();
-    }
-    for (int ci = 0; ci < used; ++ci)
-      if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
-      else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
-  }
+  if (rc == MH_OK) rc = launch_chains(chains, used, total_steps, a.poll_every <= 0 ? 16 : a.poll_every, !a.forced, a.who);
   // join the chains back into the caller's stream
   for (int ci = 0; ci < used; ++ci) {
-    (void)hipEventRecord(g_pool.join[ci], chain_stream[ci]);
+    (void)hipEventRecord(g_pool.join[ci], chains[ci].stream);
     (void)hipStreamWaitEvent(s, g_pool.join[ci], 0);
   }
   if (rc == MH_OK) {
-    hipLaunchKernelGGL(dec_finalize_kernel, dim3(1), dim3(64), 0, s, all.finish_col, B, n_steps_out);
+    hipLaunchKernelGGL(dec_finalize_kernel, dim3(1), dim3(64), 0, s, ly.bf.finish_col, B, a.n_steps_out);
     rc = check_launch("dec_finalize_kernel");
   }
   (void)hipStreamSynchronize(s);   // the graph objects must outlive their launches
   if (rc == MH_OK && option(OPT_DECODE_FUSED_TAIL) != 0) {   // the chains are idle: their last word on the bounded hand-offs
     for (int ci = 0; ci < used && rc == MH_OK; ++ci) {
       int err = 0;
-      if (hipMemcpy(&err, &states[ci]->tail_err, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = check_launch("tail status");
+      if (hipMemcpy(&err, &chains[ci].st->tail_err, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = check_launch("tail status");
       else rc = mh_t5_decode_tail_status(err);
     }
   }
-  for (int ci = 0; ci < kMaxChains; ++ci) {
-    if (cached[ci]) { step_graph_release(cached[ci]); continue; }
-    if (execs[ci]) (void)hipGraphExecDestroy(execs[ci]);
-    if (graphs[ci]) (void)hipGraphDestroy(graphs[ci]);
-  }
   return rc;
+}
+}  // namespace mh
+
+extern "C" int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset) {
+  if (hits) *hits = mh::g_step_graph_hits.load();
+  if (misses) *misses = mh::g_step_graph_misses.load();
+  if (reset) { mh::g_step_graph_hits.store(0); mh::g_step_graph_misses.store(0); }
+  return MH_OK;
 }
 
 extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
@@ -2038,8 +2052,8 @@ extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const v
                               const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
                               void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
-  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                       workspace_bytes, poll_every, stream, nullptr, "mh_t5_generate");
+  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                        workspace_bytes, poll_every, stream, nullptr, nullptr, "mh_t5_generate"});
 }
 
 extern "C" int mh_t5_generate_skv8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
@@ -2051,8 +2065,8 @@ extern "C" int mh_t5_generate_skv8(const MhT5Config* c, const MhT5Weights* w, co
   MH_TRY(check_cfg(c, "mh_t5_generate_skv8"));
   MH_REQUIRE(self_kv_fp8, "mh_t5_generate_skv8: null argument (self_kv_fp8: mh_t5_self_kv_fp8_bytes(cfg, B) bytes owned by the caller)");
   MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_generate_skv8: the e4m3 self-attention cache needs bf16 storage");
-  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                       workspace_bytes, poll_every, stream, self_kv_fp8, "mh_t5_generate_skv8");
+  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                        workspace_bytes, poll_every, stream, self_kv_fp8, nullptr, "mh_t5_generate_skv8"});
 }
 
 extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
@@ -2068,8 +2082,8 @@ extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, co
   MH_REQUIRE(n_eos_sets >= 1, "mh_t5_generate_rows: n_eos_sets %d must be >= 1", n_eos_sets);
   MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "mh_t5_generate_rows: the e4m3 self-attention cache needs bf16 storage");
   const mh::RowSetP rowset{rows, eos_tables, n_eos_sets};
-  return generate_impl(c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                       workspace_bytes, poll_every, stream, self_kv_fp8, "mh_t5_generate_rows", &rowset);
+  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
+                        workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, "mh_t5_generate_rows"});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2251,11 +2265,9 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
   MH_REQUIRE(w && cross_kv && ms_out && workspace && B > 0 && B <= 64 && reps > 0, "mh_t5_cross_attn_probe: bad argument");
   MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_cross_attn_probe: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype), H = c->n_heads, inner = H * 64, L = c->src_len, d = c->d_model;
   const DecodeLayout ly = decode_layout(c, B, workspace);
   float* h = ly.bf.h;
-  if (hipMemsetAsync(h, 0, (size_t)B * d * 4, s) != hipSuccess) return check_launch("probe memset");
-  const long kv_layer = (long)B * H * L * 64 * es;
+  if (hipMemsetAsync(h, 0, (size_t)B * c->d_model * 4, s) != hipSuccess) return check_launch("probe memset");
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return check_launch("event create");
   int rc = MH_OK;
@@ -2263,13 +2275,9 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
     if (pass == 1) (void)hipEventRecord(e0, s);
     for (int r = 0; r < reps && rc == MH_OK; ++r) {
       const int l = r % c->n_dec_layers;
-      dec::CrossAttnP ca{};
-      ca.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer;
-      ca.v = (const char*)cross_kv + (long)(l * 2 + 1) * kv_layer; ca.out = ly.bf.attn; ca.ldo = inner;
-      ca.B = B; ca.H = H; ca.L = L;
-      dec::HeadProjP hp{};
-      hp.h = h; hp.ldh = d; hp.ln_w = w->dec_ln2[l]; hp.eps = c->eps; hp.W = w->dec_cq[l]; hp.ldw = d; hp.d = d;
-      rc = c->dtype == MH_BF16 ? launch_cross_q_d<bf16_t>(ca, hp, s) : launch_cross_q_d<float>(ca, hp, s);
+      const dec::CrossAttnP ca = cross_attn(c, cross_kv, B, l, ly.bf.attn, B);
+      const dec::HeadProjP hp = head_proj(c, h, w->dec_ln2[l], nullptr, w->dec_cq[l]);
+      rc = dispatch_dtype(c->dtype, [&](auto t) { return launch_cross_q_d<decltype(t)>(ca, hp, s); });
     }
     if (pass == 1) (void)hipEventRecord(e1, s);
   }
@@ -2290,31 +2298,41 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
 // Step-wise decode for host-driven search (beam search: HF `GenerationMixin._beam_search` drives the model one position at a
 // time and reorders its cache, osuT5/osuT5/inference/cache_utils.py:16-20).  The workspace is the one of mh_t5_generate
 // (mh_t5_decode_workspace_bytes) and holds the self-attention K/V caches between calls.
+// mh_t5_step (fp8 = false) and mh_t5_step_fp8
+static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, bool fp8, const void* cross_kv_fp8, int B,
+                     int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
+                     int64_t workspace_bytes, void* stream, const char* who) {   // who: the entry the caller used (error messages)
+  MH_TRY(check_cfg(c, who));
+  MH_TRY(check_decode_shape(c, who));
+  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace, "%s: null argument", who);
+  MH_REQUIRE(!fp8 || c->dtype == MH_BF16, "%s: the fp8 cross K/V copy needs bf16 storage", who);
+  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64]", who, B);
+  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "%s: %d rows are not whole groups of %d", who, B, kv_group);
+  MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "%s: position %d outside the cache (tgt_len %d)", who, pos, c->tgt_len);
+  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "%s: workspace too small", who);
+  MH_TRY(check_arch2_weights(c, w, who));
+  hipStream_t s = (hipStream_t)stream;
+  StepCall k;
+  step_call_init(&k, c, w);
+  k.cross_kv = cross_kv; k.Bc = k.Bfull = B; k.kvB = B / kv_group; k.prompt_mask = prompt_mask; k.P = P; k.kv_group = kv_group;
+  k.bf = decode_layout(c, B, workspace).bf;
+  k.bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
+  if (fp8) { k.kv8 = cross_kv_fp8; k.kv8_scales = (const float*)((const char*)cross_kv_fp8 + cross_kv8_layout(c, k.kvB).scales_offset); }
+  const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
+  const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
+  return dispatch_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(step_embed_kernel<T>, dim3(B), dim3(256), 0, s, ids, (const T*)w->dec_embed, c->d_model, k.bf.h, k.bf.st, pos, dpos, pmask, P);
+    MH_TRY(check_launch("step_embed_kernel"));
+    return enqueue_step<T>(k, s);
+  });
+}
+
 extern "C" int mh_t5_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kv_group, const int32_t* ids,
                           int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace, int64_t workspace_bytes,
                           void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_step"));
-  MH_TRY(check_decode_shape(c, "mh_t5_step"));
-  MH_REQUIRE(w && cross_kv && ids && logits && workspace, "mh_t5_step: null argument");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step: batch %d not in [1, 64]", B);
-  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_step: %d rows are not whole groups of %d", B, kv_group);
-  MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "mh_t5_step: position %d outside the cache (tgt_len %d)", pos, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int d = c->d_model;
-  DecBuffers bf = decode_layout(c, B, workspace).bf;
-  bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
-  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "mh_t5_step: arch 2 needs decoder.embed_positions and the LayerNorm biases");
-  const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
-  const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
-  if (c->dtype == MH_BF16) hipLaunchKernelGGL(step_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, s, ids, (const bf16_t*)w->dec_embed, d, bf.h, bf.st, pos, dpos, pmask, P);
-  else hipLaunchKernelGGL(step_embed_kernel<float>, dim3(B), dim3(256), 0, s, ids, (const float*)w->dec_embed, d, bf.h, bf.st, pos, dpos, pmask, P);
-  MH_TRY(check_launch("step_embed_kernel"));
-  SampleP smp{};
-  const int kvB = B / kv_group;
-  return c->dtype == MH_BF16 ? enqueue_step<bf16_t>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, smp, s, nullptr, nullptr, false, kv_group)
-                             : enqueue_step<float>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, smp, s, nullptr, nullptr, false, kv_group);
+  return step_impl(c, w, cross_kv, false, nullptr, B, kv_group, ids, pos, prompt_mask, P, logits, workspace, workspace_bytes, stream, "mh_t5_step");
 }
 
 // mh_t5_step with the packed e4m3 copy of cross_kv (mh_t5_quantize_cross_kv over its B / kv_group rows) as one more argument: every
@@ -2323,27 +2341,8 @@ extern "C" int mh_t5_step_fp8(const MhT5Config* c, const MhT5Weights* w, const v
                               int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
                               void* workspace, int64_t workspace_bytes, void* stream) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_step_fp8"));
-  MH_TRY(check_decode_shape(c, "mh_t5_step_fp8"));
-  MH_REQUIRE(w && cross_kv && cross_kv_fp8 && ids && logits && workspace, "mh_t5_step_fp8: null argument");
-  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_step_fp8: the fp8 cross K/V copy needs bf16 storage");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step_fp8: batch %d not in [1, 64]", B);
-  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_step_fp8: %d rows are not whole groups of %d", B, kv_group);
-  MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "mh_t5_step_fp8: position %d outside the cache (tgt_len %d)", pos, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step_fp8: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  DecBuffers bf = decode_layout(c, B, workspace).bf;
-  bf.logits = logits;
-  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "mh_t5_step_fp8: arch 2 needs decoder.embed_positions and the LayerNorm biases");
-  const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
-  const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
-  hipLaunchKernelGGL(step_embed_kernel<bf16_t>, dim3(B), dim3(256), 0, s, ids, (const bf16_t*)w->dec_embed, c->d_model, bf.h, bf.st, pos, dpos, pmask, P);
-  MH_TRY(check_launch("step_embed_kernel"));
-  const int kvB = B / kv_group;
-  // packed copy: data, then (256-byte aligned) the scales [layer][k|v][kvB][H]
-  const int64_t data_bytes = (int64_t)c->n_dec_layers * 2 * kvB * c->n_heads * c->src_len * 64;
-  const float* scales = reinterpret_cast<const float*>((const char*)cross_kv_fp8 + align256(data_bytes));
-  return enqueue_step<bf16_t>(c, w, cross_kv, B, B, kvB, prompt_mask, P, bf, SampleP{}, s, cross_kv_fp8, scales, false, kv_group);
+  return step_impl(c, w, cross_kv, true, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace, workspace_bytes, stream,
+                   "mh_t5_step_fp8");
 }
 
 // self-attention cache rows of every layer: row b <- row src[b] for positions 0 .. n_pos-1 (`cache.reorder_cache(beam_idx)`).
@@ -2367,12 +2366,10 @@ extern "C" int mh_t5_reorder_cache(const MhT5Config* c, int B, const int32_t* sr
   void* self_v = bf.self_v;
   const long layer_stride = (long)B * H * c->tgt_len * 64;
   const dim3 grid(B * H, c->n_dec_layers, 2);
-  if (c->dtype == MH_BF16) {
-    hipLaunchKernelGGL(cache_gather_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)self_k, (const bf16_t*)self_v, (bf16_t*)scratch, src, B, H, c->tgt_len, n_pos, layer_stride);
-    hipLaunchKernelGGL(cache_scatter_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)self_k, (bf16_t*)self_v, (const bf16_t*)scratch, B, H, c->tgt_len, n_pos, layer_stride);
-  } else {
-    hipLaunchKernelGGL(cache_gather_kernel<float>, grid, dim3(256), 0, s, (const float*)self_k, (const float*)self_v, (float*)scratch, src, B, H, c->tgt_len, n_pos, layer_stride);
-    hipLaunchKernelGGL(cache_scatter_kernel<float>, grid, dim3(256), 0, s, (float*)self_k, (float*)self_v, (const float*)scratch, B, H, c->tgt_len, n_pos, layer_stride);
-  }
-  return check_launch("cache reorder");
+  return dispatch_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(cache_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)self_k, (const T*)self_v, (T*)scratch, src, B, H, c->tgt_len, n_pos, layer_stride);
+    hipLaunchKernelGGL(cache_scatter_kernel<T>, grid, dim3(256), 0, s, (T*)self_k, (T*)self_v, (const T*)scratch, B, H, c->tgt_len, n_pos, layer_stride);
+    return check_launch("cache reorder");
+  });
 }

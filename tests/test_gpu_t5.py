@@ -1124,6 +1124,101 @@ def test_step_graphs_are_replayed_across_generate_calls():
     assert not torch.equal(outs[0][0], outs[0][1]), "different seeds must draw different tokens"
 
 
+def test_a_step_graph_is_never_replayed_for_a_different_description():
+    """Every input that is baked into a chain's step graph is part of the graph's cache key: a call `A'` that differs from a cached
+    call `A` in ONE such input (top_k, temperature, the prompt mask, the e4m3 cross K/V copy, the e4m3 self-attention shadow, the
+    row form of the sampler, the timing hook) gives bit for bit what an engine that captures per call (`decode_graph_cache=0`)
+    gives for it, differs from `A`, and leaves `A`'s graph in place: the returning `A` replays it (one hit per chain -- the buffers
+    sat at the same addresses, so a key without the varied input WOULD have replayed `A`'s graph for `A'`) with `A`'s result."""
+    import ctypes as C
+
+    from mapperatorinator_amd import _lib
+    from mapperatorinator_amd.modeling import MapperatorinatorHIP
+    from mapperatorinator_amd.server import build_row_sampling, build_sampling
+    from mapperatorinator_amd.t5_engine import T5_PRESETS
+    g, size, tok, sd, audio, src, tgt = golden_case("t5_tiny")
+    lib = _lib.load()
+
+    def make(options):
+        return MapperatorinatorHIP(sd, T5_PRESETS[size], vocab_size_in=tok.vocab_size_in, vocab_size_out=tok.vocab_size_out,
+                                   src_seq_len=src, tgt_seq_len=tgt, dtype=torch.bfloat16, device="cuda", options=options)
+
+    def stats(reset=0):
+        h, m = C.c_long(0), C.c_long(0)
+        lib.mh_t5_step_graph_cache_stats(C.byref(h), C.byref(m), reset)
+        return h.value, m.value
+    cached, percall = make(None), make(dict(decode_graph_cache=0))
+    prompt = torch.from_numpy(g["prompt"])          # rows 0 and 2 are left-padded
+    B = prompt.shape[0]
+    base = gen_kwargs(tgt, do_sample=True, top_p=0.9, temperature=1.3, seed=100, seed_call_index=0)
+
+    def run(model, gk=base, mask=True, rows=None, **kw):
+        """-> (ids, logits dump as int32 bit patterns on the CPU); nothing of the call stays allocated on the device"""
+        if rows is not None:
+            rs = build_row_sampling(tok, rows, tgt)
+            sp, eos, kw = rs[0], None, dict(kw, row_sampling=rs)
+        else:
+            sp, eos = build_sampling(tok, gk, tgt)
+        out = model.engine.generate(audio, prompt, prompt.ne(0) if mask else None, eos, sp, dump_logits=True, **kw)
+        return out["tokens"], out["logits"].cpu().view(torch.int32)
+
+    def same(x, y):
+        return x[0].shape == y[0].shape and torch.equal(x[0], y[0]) and torch.equal(x[1], y[1])
+    n_chains = lib.mh_t5_decode_chains_cfg(C.byref(cached.engine.packed.cfg), B)
+    # the buffers the variants keep (the shadow cache, the row settings, the stamps) exist before `A` settles, so that they do not
+    # take the blocks `A`'s own per-call buffers return to
+    ring, L = 8, T5_PRESETS[size].n_dec_layers
+    tbuf = torch.zeros((n_chains, ring, L, 2), dtype=torch.int64, device="cuda")
+    for m in (cached, percall):
+        m.engine._workspace("skv8", lib.mh_t5_self_kv_fp8_bytes(C.byref(m.engine.packed.cfg), B))
+        m.engine._workspace("row_sampling", 64 * C.sizeof(_lib.MhRowSampling))
+        m.engine._workspace("row_eos_tables", 64 * tok.vocab_size_out)
+    stats(reset=1)
+    first = run(cached)
+    for _ in range(5):      # (as in the test above: the allocator settles after a call or two)
+        again = run(cached)
+        assert same(again, first)
+        if stats()[0] >= n_chains:
+            break
+    assert stats()[0] >= n_chains, "the repeated call did not find its graphs"
+
+    def check(name, **variant):
+        got = run(cached, **variant)
+        h0, m0 = stats()
+        back = run(cached)
+        h1, m1 = stats()
+        want = run(percall, **variant)
+        assert stats() == (h1, m1)               # (the per-call engine never touches the cache)
+        print(name, "ids differ from A:", not torch.equal(got[0], first[0]) if got[0].shape == first[0].shape else True,
+              "dump differs:", got[1].shape != first[1].shape or not torch.equal(got[1], first[1]), "hits", h0, "->", h1)
+        assert same(got, want), f"{name}: the cached engine and the per-call engine disagree"
+        assert not same(got, first), f"{name}: the variant gives A's result -- the comparison has no teeth"
+        assert same(back, first), f"{name}: A after the variant is not the first A"
+        assert (h1 - h0, m1 - m0) == (n_chains, 0), f"{name}: the returning A did not replay its graphs ({h0, m0} -> {h1, m1})"
+    check("top_k", gk=dict(base, top_k=5))
+    check("temperature", gk=dict(base, temperature=0.7))
+    check("prompt mask", mask=False)
+    check("cross_kv_fp8", cross_kv_fp8=True)
+    check("self_kv_fp8", self_kv_fp8=True)
+    check("row form", rows=[dict(base, top_k=5)] + [base] * (B - 1))
+    # the timing hook: its buffer is part of the description -- a call under the hook stamps, the next one without it must not
+    tbuf[..., 0] = -1       # (= UINT64_MAX for the kernel's atomicMin)
+    _lib.check(lib.mh_t5_decode_timing(tbuf.data_ptr(), ring), "mh_t5_decode_timing")
+    try:
+        timed = run(cached)
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(lib.mh_t5_decode_timing(None, 0), "mh_t5_decode_timing")
+    t = tbuf.cpu()
+    assert same(timed, first) and bool(((t[..., 1] != 0) & (t[..., 0] != -1)).any()), "the call under the hook wrote no stamps"
+    tbuf.zero_()
+    h0, m0 = stats()
+    back = run(cached)
+    torch.cuda.synchronize()
+    assert same(back, first) and stats() == (h0 + n_chains, m0)
+    assert not bool(tbuf.any()), "a call without the hook replayed a graph that stamps"
+
+
 @pytest.mark.parametrize("beams,n_eos", [(2, 0), (2, 1), (3, 40), (2, 700), (5, 300), (8, 2)])
 def test_beam_step_kernel_matches_torch_bookkeeping_across_candidate_counts(beams, n_eos):
     """mh_beam_step picks its K = max(2, 1 + #eos) x beams candidates with a radix select + a sort of the K only; the torch-op form

@@ -816,6 +816,32 @@ def test_kernels_with_asm_issued_loads_have_no_scratch_and_no_spills():
     assert ckr.main([lib]) == 0
 
 
+def test_device_code_diff_tells_equal_builds_from_a_changed_instruction(tmp_path):
+    """tools/device_code_diff.py (the check behind "a host-only change": DESIGN 4.2): the built library against itself is exit 0; a
+    copy with ONE byte of one code object's .text flipped is exit 1."""
+    import importlib.util
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    try:
+        spec = importlib.util.spec_from_file_location("dcd", os.path.join(root, "tools", "device_code_diff.py"))
+        dcd = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(dcd)
+    finally:
+        sys.path.remove(os.path.join(root, "tools"))
+    lib = os.path.join(root, "mapperatorinator_amd", "lib", "libmapperhip.so")
+    assert dcd.main([lib, lib]) == 0
+    blob = bytearray(open(lib, "rb").read())
+    text = dcd.describe(min(dcd.code_objects(lib), key=len))[0][".text"]
+    at = bytes(blob).find(text)
+    assert len(text) > 64 and at > 0 and bytes(blob).find(text, at + 1) < 0
+    blob[at + len(text) // 2] ^= 0x01
+    changed = tmp_path / "changed.so"
+    changed.write_bytes(bytes(blob))
+    assert dcd.main([lib, str(changed)]) == 1
+
+
 def test_mx8_host_packer_oracle_and_torch_restatement_agree():
     """three statements of the MX-fp8 quantisation rule (numpy oracle, its torch form used inside the model oracles, the
     product's weight packer) produce the same bytes / values, including zero blocks, outliers and the 448 boundary"""
