@@ -606,7 +606,8 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
  * [negative | prompt]: modeling_mapperatorinator.py:243-254] -> the reference's processor list on log-probabilities (server.py:
  * 106-134; logit_processors.py:36-44,47-82,111-114,136-183) -> + running beam scores -> the K best continuations of every chunk
  * (sorted, ties by flat index) -> EOS / max_length split -> the next running beams -> merge of the finished hypotheses by score /
- * length ** penalty -> the early_stopping = False heuristic.  Greedy beams only (sp.do_sample = 0).
+ * length ** penalty -> the early_stopping = False heuristic.  Greedy beams only (sp.do_sample = 0; beam-sample is
+ * mh_beam_step_sample below).
  * State: G chunks x num_beams rows, int32 sequences [G][nb][max_length] (columns beyond the current length hold the fill value),
  * fp32 scores [G][nb], int32 beam-index trails [G][nb][max_length - P], finished flags [G][nb]; the kernel reads the *_in arrays
  * and writes the *_out arrays (the caller swaps them every step), `heuristic_open` [G] in place.  Outputs for the caller (G nb entries,
@@ -655,6 +656,33 @@ int mh_beam_step_path(int num_beams, int V, int K);
  * mh_beam_step's; with the types_first lookback off the call IS mh_beam_step (lookback_prev may then be NULL).  tok_flags must be
  * set.  Additive at ABI 11 (one symbol; no struct changes layout). */
 int mh_beam_step_tf(const MhBeamStep* bs, float* lookback_prev, void* stream);
+/* Beam-SAMPLE (HF `_beam_search` with do_sample, which the reference's defaults give whenever num_beams > 1: configs/inference/
+ * default.yaml do_sample / top_p, processor.py:147-161): mh_beam_step_tf with the K continuations of a chunk DRAWN inside the kernel.
+ * Requires bs->sp.do_sample = 1 and reads sp.top_k, sp.top_p, sp.seed and sp.rng_row0 beside what mh_beam_step reads.  Per beam row,
+ * x = the processed score in front of the running score (log_softmax -> guidance -> the processor list, lookback included):
+ *   TopK (sp.top_k > 0): k' = min(max(top_k, min_tokens_to_keep), V); ids with x < the k'-th largest x are removed.  Exact; ties at
+ *     the threshold stay, as in HF.
+ *   TopP (sp.top_p < 1): p = softmax(x) over what TopK left; an id is removed iff the summed p of all ids with value <= its own is
+ *     <= 1 - top_p and it is not among the min_tokens_to_keep largest.  HF may split a group of exactly equal values at the boundary
+ *     by its sort order; here such a group stays or goes WHOLE.  The sums are deterministic: every numerator is taken in fixed point,
+ *     (uint64) (exp(x - max x) 2^32), and added with 64-bit integer adds in LDS, so two launches, and the two kernels, agree bit for
+ *     bit; the threshold is (uint64) ((1.0 - (double) top_p) x the row's integer total).
+ *   Both leave the row ONE cut value; the accumulated score is acc = x >= cut ? x + running score : -inf (a dead beam's -1e9 running
+ *   score enters behind the warpers and cannot collapse its row into ties).
+ * The draw is Gumbel top-K: key = acc + g, g = -log(-log(u)) in fp32, u = min(uniform01(m, 0, flat), 1 - 2^-24) with uniform01 the
+ * sampler's counter-based generator (splitmix64 finaliser; (n + 0.5) / 2^24 of the top 24 bits), m = the 64-bit word that generator
+ * mixes from (sp.seed, row = sp.rng_row0 + chunk, step = bs->cur_len), flat = beam x V + id.  The K largest keys, best first, ties
+ * by ascending flat index, ARE the draw, in draw order (the descending order of Gumbel-perturbed scores is distributed as sequential
+ * sampling without replacement from softmax(acc); torch.multinomial runs the same race).  Each drawn candidate carries its acc (read
+ * back or recomputed, not key - g); "inside the top num_beams" means the first num_beams draws, and the EOS split, next-beam choice,
+ * finished-set merge, heuristic and flags are mh_beam_step's.  A -inf score has a -inf key: it is drawn only when the finite ones run
+ * out, then in flat-index order (HF leaves this case undefined).  Chunk g of a call draws what a one-chunk call with rng_row0 + g draws.
+ * `lookback_prev`: as in mh_beam_step_tf; may be NULL with the types_first lookback off.  `min_tokens_to_keep` >= 1 (HF passes #eos +
+ * 1 under beams).  `scores_dump`: NULL or device fp32 [G][num_beams][V], acc of every id (-inf where removed) -- the parity hook.
+ * MH_ERR_ARG before any launch, naming the value: do_sample = 0, min_tokens_to_keep < 1, top_p outside (0, 1], top_k < 0, and every
+ * limit of mh_beam_step in its wording.  Same two kernels, dispatch rule and bit equality between them as mh_beam_step.  Additive at
+ * ABI 11 (one symbol; no struct, no struct-size entry). */
+int mh_beam_step_sample(const MhBeamStep* bs, float* lookback_prev, int min_tokens_to_keep, float* scores_dump, void* stream);
 
 /* Step-wise decode for host-driven search.  Replaces the per-position `self(**model_inputs)` of HF
  * `GenerationMixin._beam_search` (num_beams > 1: osuT5/osuT5/inference/processor.py:147,159; server.py:137) and

@@ -200,6 +200,7 @@ SYMBOLS = {
     "mh_beam_step": (I, [C.POINTER(MhBeamStep), VP]),
     "mh_beam_step_path": (I, [I, I, I]),
     "mh_beam_step_tf": (I, [C.POINTER(MhBeamStep), VP, VP]),
+    "mh_beam_step_sample": (I, [C.POINTER(MhBeamStep), VP, I, VP, VP]),
     "mh_t5_step_fp8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, VP, I, I, VP, I, VP, I, VP, VP, I64, VP]),
     "mh_t5_reorder_cache_scratch_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
     "mh_t5_reorder_cache": (I, [C.POINTER(MhT5Config), I, VP, I, VP, I64, VP, I64, VP]),

@@ -18,8 +18,8 @@ logits out -- `mh_t5_step_fp8` when the search is handed the e4m3 copy of the cr
 (csrc/beam.hip: log_softmax, guidance, processors, top-K over beams x V by a radix select + a sort of the K, EOS split, next-beam
 selection, finished-set merge, the early-stopping heuristic; 2 .. 8 beams, K <= 8192, any vocabulary: the scores live in LDS where
 they fit 120 KB, else a streaming kernel recomputes them from the logits, same bits) -- `_beam_search_kernel` below; the host reads three flags per chunk and step.  The torch-op
-form (`beam_search` with use_kernel=False; ~40 ATen launches per token) stays for beam-SAMPLE, whose continuations are drawn by
-torch.multinomial / an injected sampler, and as the cross-check of the kernel (tests run both against the reference goldens).  The logits processors of
+form (`beam_search` with use_kernel=False; ~40 ATen launches per token) stays for beam-SAMPLE as HF draws it (torch.multinomial / an
+injected sampler: the default), and as the cross-check of the kernel (tests run both against the reference goldens).  The logits processors of
 server.py:106-134 are applied here with torch ops (the in-kernel sampler of the greedy / sampling path selects per row and
 cannot rank across beams): classifier-free guidance, MonotonicTimeShift, TimeshiftBias, (Conditional)Temperature and the lookback
 warper, both branches.  Its types_first branch (logit_processors.py:116-133) keeps `last_scores` from call to call and indexes them by
@@ -32,7 +32,12 @@ BEHIND the reference's processor list with `min_tokens_to_keep = #eos + 1` (util
 `_get_top_k_continuations` draws the K continuations with `torch.multinomial(softmax(accumulated), K)` -- without replacement, in
 draw order (not sorted: "inside the top num_beams" then means "among the first num_beams draws").  The draw uses torch's generator
 on the engine's device, like HF on a GPU; `sample_fn(probs, k)` replaces it (parity tests inject the sampler the reference golden
-was drawn with).
+was drawn with).  Opt-in, `device_draw=True`: the draw moves INTO the step kernel (`mh_beam_step_sample`: HF's two warpers as one
+cut value per beam row, then Gumbel top-K -- key = accumulated score + -log(-log(u)), u from the library's counter-based generator
+keyed by (sp.seed, sp.rng_row0 + chunk, decode column, beam x V + id); the K largest keys, ties by flat index, are K draws without
+replacement in draw order: include/mapperhip.h), one kernel per token like greedy beams.  It is another stream of random numbers than
+torch.multinomial's, with the same distribution; `use_kernel=False` then draws by the same rule with torch ops (`_device_draw`), the
+kernel's cross-check.
 
 Guidance under beams (round 5; the timing pass sets beams, `super_timing_generator.py:28`, and `processor.py:709` halves its batch
 for exactly this case) follows what the reference + HF do, quirk included:
@@ -152,6 +157,47 @@ def kernel_path_available(sp, num_beams: int, vocab_out: int, n_eos: int) -> boo
     return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), int(K)) != 0
 
 
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _s64(x: int) -> int:
+    """a 64-bit pattern as the int64 that holds it"""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _lsr(z: torch.Tensor, s: int) -> torch.Tensor:
+    """logical shift right of the 64-bit patterns in an int64 tensor"""
+    return (z >> s) & ((1 << (64 - s)) - 1)
+
+
+def _rng_mix64(seed: torch.Tensor, row: torch.Tensor, step: torch.Tensor) -> torch.Tensor:
+    """rng_mix64 of csrc/common.hpp on int64 tensors (the 64-bit patterns; int64 products wrap like the device's uint64_t)"""
+    z = seed + (row * 0x100000001 + step + 1) * _s64(_GOLDEN)
+    z = (z ^ _lsr(z, 30)) * _s64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr(z, 27)) * _s64(0x94D049BB133111EB)
+    return z ^ _lsr(z, 31)
+
+
+def _device_draw(acc: torch.Tensor, K: int, seed: int, row0: int, cur_len: int, keys_out: Optional[list] = None) -> torch.Tensor:
+    """The draw of mh_beam_step_sample in torch ops on acc fp32 (G, num_beams x V): int64 splitmix for u (bit-exact), fp32 keys
+    acc + -log(-log(u)), a stable descending sort so that ties fall by flat index.  -> indices (G, K) in draw order.  `keys_out`: a
+    list that receives the sorted keys (G, num_beams x V) of the call (tests measure how far apart the deciding keys are)."""
+    G, n = acc.shape
+    dev = acc.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    rows = (torch.arange(G, **i64) + int(row0)) & 0xFFFFFFFF
+    sub = _rng_mix64(torch.tensor(_s64(int(seed)), **i64), rows, torch.tensor(int(cur_len) & 0xFFFFFFFF, **i64))
+    z = _rng_mix64(sub[:, None], torch.zeros((), **i64), torch.arange(n, **i64)[None, :])
+    u = (_lsr(z, 40).to(torch.float64) + 0.5).to(torch.float32) * (1.0 / 16777216.0)
+    u = torch.clamp(u, max=1.0 - 2.0 ** -24)
+    key = acc + -torch.log(-torch.log(u))
+    srt, order = torch.sort(key, dim=1, descending=True, stable=True)
+    if keys_out is not None:
+        keys_out.append(srt)
+    return order[:, :K]
+
+
 def _step_kv_fp8(engine, cross_kv: torch.Tensor, kv_fp8):
     """The packed e4m3 copy the steps stream, or None.  `cross_kv` is the tensor the steps are handed -- under guidance the rows
     already doubled: a copy of the undoubled rows is made again, so that the packed layout stays [data | scales] of ONE tensor."""
@@ -181,10 +227,11 @@ def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P
 
 @torch.no_grad()
 def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                        kv_fp8=None) -> torch.Tensor:
+                        kv_fp8=None, sample_keep: Optional[int] = None) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
     D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs.  With the
-    types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is."""
+    types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is.
+    `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep."""
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = neg_mask = None
@@ -280,7 +327,10 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
             bs.seq_in, bs.bs_in, bs.bb_in, bs.fin_in = a["seq"].data_ptr(), a["bs"].data_ptr(), a["bb"].data_ptr(), a["fin"].data_ptr()
             bs.run_out, bs.rs_out, bs.rb_out = b["run"].data_ptr(), b["rs"].data_ptr(), b["rb"].data_ptr()
             bs.seq_out, bs.bs_out, bs.bb_out, bs.fin_out = b["seq"].data_ptr(), b["bs"].data_ptr(), b["bb"].data_ptr(), b["fin"].data_ptr()
-            if types_first:
+            if sample_keep is not None:
+                _lib.check(lib.mh_beam_step_sample(C.byref(bs), _lib.ptr(lookback_prev), int(sample_keep), None, stream),
+                           "mh_beam_step_sample")
+            elif types_first:
                 _lib.check(lib.mh_beam_step_tf(C.byref(bs), lookback_prev.data_ptr(), stream), "mh_beam_step_tf")
             else:
                 _lib.check(lib.mh_beam_step(C.byref(bs), stream), "mh_beam_step")
@@ -309,7 +359,7 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
 @torch.no_grad()
 def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids, sp,
                 num_beams: int, length_penalty: float = 1.0, early_stopping=False, sample_fn=None,
-                use_kernel: Optional[bool] = None, kv_fp8=None) -> torch.Tensor:
+                use_kernel: Optional[bool] = None, kv_fp8=None, device_draw: bool = False) -> torch.Tensor:
     """cross_kv: the G chunks' cross K/V (engine.cross_kv); prompt int (G, P) left-padded, prompt_mask (G, P) or None.
     Under guidance (sp.cfg_scale > 1) `prompt` / `prompt_mask` carry 2G rows, [negative-prompt rows | prompt rows] (what
     T5Engine.generate and the scheduler build), and cross_kv still has G rows.
@@ -318,8 +368,24 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     `use_kernel`: None = mh_beam_step whenever it covers the call (greedy beams, 2 .. 8 of them, K <= 8192: kernel_path_available), False = the torch-op
     bookkeeping below, True = the kernel or an error.
     `kv_fp8`: the packed e4m3 copy of `cross_kv` (engine.cross_kv_fp8(cross_kv)), or True to have it made here: every step streams
-    the copy (mh_t5_step_fp8) instead of `cross_kv`.  bf16 storage only."""
-    can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(list(eos_ids))) and sample_fn is None
+    the copy (mh_t5_step_fp8) instead of `cross_kv`.  bf16 storage only.
+    `device_draw` (beam-sample only; ignored under greedy beams): the continuations are drawn by the library's rule (Gumbel top-K on
+    its counter-based generator, seed sp.seed: module docstring) instead of torch.multinomial -- in the step kernel,
+    mh_beam_step_sample (`use_kernel` None / True), or by the same rule in torch ops (`use_kernel` False).  Not with `sample_fn`."""
+    if device_draw and sample_fn is not None:
+        raise ValueError("device_draw draws inside the library: it cannot be combined with sample_fn")
+    device_draw = bool(device_draw) and bool(sp.do_sample)
+    eos_ids = list(eos_ids)
+    if device_draw:
+        nb_, V_ = int(num_beams), engine.packed.vocab_out
+        can_draw = _lib.load().mh_beam_step_path(nb_, V_, min(max(2, 1 + len(eos_ids)) * nb_, nb_ * V_)) != 0
+        if use_kernel is True and not can_draw:
+            raise NotImplementedError("mh_beam_step_sample does not cover this call (beams outside 2 .. 8 or K = max(2, 1 + #eos) x "
+                                      "beams > 8192)")
+        if can_draw and use_kernel is not False:
+            return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
+                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2)
+    can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(eos_ids)) and sample_fn is None
     if use_kernel is True and not can:
         raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
                                   "K = max(2, 1 + #eos) x beams > 8192)")
@@ -351,7 +417,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     eos_list = [int(e) for e in eos_ids]
     procs = BeamProcessors(sp, dev, min_tokens_to_keep=len(eos_list) + 1 if eos_list else 2)
     do_sample = bool(sp.do_sample)
-    if do_sample and sample_fn is None:
+    if do_sample and sample_fn is None and not device_draw:
         sample_fn = torch.multinomial
     eos_t = torch.tensor(sorted(set(eos_list)), dtype=torch.long, device=dev)
     n_eos = len(eos_list)
@@ -406,7 +472,10 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
                 lsm = lsm[R:] + (lsm[:R] - lsm[R:]) * scale
             log_probs = procs(flat, lsm)
             acc = (log_probs.view(G, nb, V) + running_scores[:, :, None]).reshape(G, nb * V)
-            if do_sample:     # K continuations drawn without replacement, kept in draw order
+            if device_draw:   # ... by the rule of mh_beam_step_sample, on acc itself (dead beams order as in the kernel)
+                topk_idx = _device_draw(acc, K, int(sp.seed), int(sp.rng_row0), cur_len)
+                topk_lp = torch.gather(acc, 1, topk_idx)
+            elif do_sample:   # K continuations drawn without replacement, kept in draw order
                 topk_idx = sample_fn(torch.softmax(acc, dim=-1), K).to(dev)
                 topk_lp = torch.gather(acc, 1, topk_idx)
             else:

@@ -10,8 +10,16 @@
 // One workgroup per chunk: the K best of its num_beams x V accumulated scores are found in LDS -- a 4-pass radix select of the K-th
 // largest value, a deterministic compaction (ties by ascending flat index), then a bitonic sort of the K candidates only (the first
 // version sorted all 8192 values: 86 us per token against ~15 us) --, the selection logic runs on that sorted list, the surviving hypotheses are copied from the IN state to the OUT state (ping-pong: every
-// workgroup reads what the previous step wrote).  Greedy beams only (do_sample = 0): beam-SAMPLE draws its continuations with
-// torch.multinomial / an injected sampler and stays on the host-side path.
+// workgroup reads what the previous step wrote).  Greedy beams (do_sample = 0) are mh_beam_step / mh_beam_step_tf.
+// Beam-SAMPLE is a third template flag, beam_step_kernel<kStream, kTf, kSample> (mh_beam_step_sample; the greedy instantiations keep
+// their loops): HF's TopK / TopP warpers become ONE cut value per beam row (beam_row_select: radix selects by count and by softmax
+// mass, the masses summed as 64-bit fixed-point integers in LDS, so both kernels and every launch agree bit for bit; a group of equal
+// values at the top-p boundary stays or goes whole, where HF may split it by sort order), the accumulated score is beam_warp(), and
+// the draw is Gumbel top-K: the radix select, compaction and sort below run on key = score + -log(-log(u)) (beam_key; u from the
+// sampler's counter-based generator, folded in common.hpp), after which every candidate's key gives way to its score again.  The K
+// candidates are then K draws without replacement IN DRAW ORDER, which is what the selection logic behind the sort assumes of them.
+// A -inf score keeps a -inf key: drawn only when the finite ones run out, by flat index.  Without the opt-in (beam.py `device_draw`)
+// beam-sample still draws with torch.multinomial / an injected sampler on the host-side path.
 // Two kernels, one body (beam_step_kernel<kStream>): the LDS kernel keeps the num_beams x V accumulated scores in LDS (at most 120 KB
 // with the K <= 4096 candidates); the STREAMING kernel keeps per-beam softmax / processor state only (BeamRow) and recomputes a score
 // from the logits -- read once from HBM, from L2 afterwards -- in every pass that needs one, so any vocabulary and K <= 8192 fit.
@@ -104,8 +112,9 @@ __device__ inline float beam_pre(const MhBeamStep& p, const BeamRow& b, float lp
   return x / b.temp;
 }
 
+// beam_x is the processed score of the column in front of the running score (what HF's top-k / top-p warpers see under beam-sample)
 template <bool kTf>
-__device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, const BeamTf& t, float lp, float ln, int v) {
+__device__ inline float beam_x(const MhBeamStep& p, const BeamRow& b, const BeamTf& t, float lp, float ln, int v) {
   const MhSampling& sp = p.sp;
   float x = beam_pre(p, b, lp, ln, v);
   if constexpr (kTf) {   // renormalise: log(softmax(x)[v] * s) kept in the log domain; the other rows pass x through, NOT masked
@@ -116,8 +125,32 @@ __device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, const 
   } else {
     if (sp.lookback_mask_end > sp.ts_start && v >= sp.ts_start && v < sp.lookback_mask_end) x = -INFINITY;
   }
-  return x + b.rs;
+  return x;
 }
+
+template <bool kTf>
+__device__ inline float beam_score(const MhBeamStep& p, const BeamRow& b, const BeamTf& t, float lp, float ln, int v) {
+  return beam_x<kTf>(p, b, t, lp, ln, v) + b.rs;
+}
+
+// ---- beam-sample (kSample instantiations: mh_beam_step_sample) -------------------------------------------------------------------
+// HF's TopK / TopP warpers leave every beam row ONE cut value (beam_row_select below): the accumulated score of a column is
+// x >= cut ? x + running score : -inf.  THE definition for both kernels, like beam_score.
+__device__ inline float beam_warp(float x, float cut, float rs) { return x >= cut ? x + rs : -INFINITY; }
+
+// Gumbel top-K: key = accumulated score + g, g = -log(-log(u)), u = beam_uniform01(sub-seed of (seed, row, column), flat index)
+// clamped to 1 - 2^-24 (uniform01 reaches exactly 1.0, where g would be +inf): g lies in [-2.86, 16.64].  A -inf score keeps a -inf
+// key.  The K largest keys, best first, ties by ascending flat index, are K draws without replacement in draw order.
+// (Every selection pass -- four radix passes, two compaction sweeps -- recomputes the key: one splitmix and two logf per element and
+// pass, in both kernels; that is the 0.03 - 0.05 ms a sampled step costs over a greedy one.  Weighed against it: the LDS kernel could
+// store the key in `val` once and recompute the score of the K survivors only, as the streaming kernel does.  Not done: the two
+// kernels would then no longer share one body per pass, and the pass arithmetic is small beside the step's ~0.5 ms decoder position.)
+__device__ inline float beam_key(float acc, uint64_t subseed, int flat) {
+  const float u = fminf(beam_uniform01(subseed, (uint32_t)flat), 0x1.fffffep-1f);
+  return acc + -logf(-logf(u));
+}
+
+__device__ inline float beam_okey_inv(unsigned img) { return __uint_as_float((img & 0x80000000u) ? (img & 0x7fffffffu) : ~img); }
 
 // the types_first state of one beam row from the three reductions over exp(x - mc) -- all columns, the columns outside [ts_start,
 // lookback_mask_end), the bit-4 ids (eos + context eos) -- and the slot's state of the previous step.  Returns the slot's next state:
@@ -149,14 +182,23 @@ template <bool kStream, bool kTf> struct BeamSrc {
   const BeamTf* tf;         // LDS [nb] (kTf)
   const float* lg_pos;      // the chunk's prompt rows of the logits, [nb][V]
   const float* lg_neg;      // ... negative rows (guidance)
+  const float* cut;         // LDS [nb] (kSample): the row's cut value
+  uint64_t subseed;         // (kSample) beam_rng_subseed(seed, rng_row0 + chunk, cur_len)
 };
+
+// what a sweep hands to f: the accumulated score (greedy beams), or under beam-sample the processed score x in front of the warpers,
+// the Gumbel key of the warped accumulated score, or that accumulated score itself.  (The LDS array holds x until the cuts are known
+// and the accumulated score from then on: BEAM_X sweeps run before, BEAM_KEY / BEAM_ACC sweeps after.)
+enum { BEAM_SCORE = 0, BEAM_X = 1, BEAM_KEY = 2, BEAM_ACC = 3 };
 
 // One wave's sweep over columns base0 + lane, + step, ... < end of beam j: f(flat index, score, in range) runs for the WHOLE wave
 // (lanes past `end` get in range = false), so f may vote across the wave.  Four columns per lane are loaded before the first is used
 // (eight changed the streaming kernel's time by 1 %: it is bound by the 512 threads' arithmetic, not by the loads).
-template <bool kStream, bool kTf, typename F>
+template <int kWhat = BEAM_SCORE, bool kStream, bool kTf, typename F>
 __device__ inline void beam_sweep(const BeamSrc<kStream, kTf>& s, int j, int base0, int step, int end, F&& f) {
   const int lane = threadIdx.x & 63, V = s.p.V;
+  float cut = 0.f;
+  if constexpr (kStream && (kWhat == BEAM_KEY || kWhat == BEAM_ACC)) cut = s.cut[j];
   constexpr int kU = 4;
   BeamRow b;
   BeamTf t{};
@@ -178,15 +220,106 @@ __device__ inline void beam_sweep(const BeamSrc<kStream, kTf>& s, int j, int bas
       if (vb + u * step < end) {           // (wave-uniform)
         const int v = vb + u * step + lane;
         const bool ok = v < end;
-        const float x = !ok ? 0.f : kStream ? beam_score<kTf>(s.p, b, t, lp[u], ln[u], v) : lp[u];
-        f(j * V + v, x, ok);
+        if constexpr (kWhat == BEAM_SCORE) {
+          const float x = !ok ? 0.f : kStream ? beam_score<kTf>(s.p, b, t, lp[u], ln[u], v) : lp[u];
+          f(j * V + v, x, ok);
+        } else {
+          float x = 0.f;
+          if (ok) {
+            if constexpr (kStream) {
+              x = beam_x<kTf>(s.p, b, t, lp[u], ln[u], v);
+              if constexpr (kWhat != BEAM_X) x = beam_warp(x, cut, b.rs);
+            } else {
+              x = lp[u];
+            }
+            if constexpr (kWhat == BEAM_KEY) x = beam_key(x, s.subseed, j * V + v);
+          }
+          f(j * V + v, x, ok);
+        }
       }
     }
   }
 }
 
-template <bool kStream, bool kTf>
-__global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, float* lookback_prev) {
+__device__ inline unsigned long long beam_shfl_up_u64(unsigned long long x, int o) {
+  const unsigned lo = __shfl_up((unsigned)x, o, 64), hi = __shfl_up((unsigned)(x >> 32), o, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ inline unsigned long long beam_shfl_u64(unsigned long long x, int l) {
+  const unsigned lo = __shfl((unsigned)x, l, 64), hi = __shfl((unsigned)(x >> 32), l, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// scratch of beam_row_select, one set per beam row
+struct BeamSelect {
+  unsigned long long hist[kBeamMaxBeams][256];
+  unsigned long long thr[kBeamMaxBeams], below[kBeamMaxBeams];
+  unsigned img[kBeamMaxBeams];
+  int found[kBeamMaxBeams];
+  float row_max[kBeamMaxBeams], floor[kBeamMaxBeams];
+};
+
+// Per beam row, all rows at once: the smallest value c of the row's x with W(c) > thr, W(c) = the sum of the integer weights of the
+// columns with x <= c -- a radix select from the bottom over the order-preserving image, 8 bits per pass, the 256 bins of row j summed
+// up by wave j.  kMass = false: weight 1 per column and thr[j] set by the caller (thr = V - k gives the k-th largest value, ties
+// included).  kMass = true: weight = the column's softmax numerator in fixed point, (uint64) (exp(x - row_max[j]) 2^32), 0 for x <
+// floor[j] (what TopK removed) -- at most 2^32 each, V < 2^31 of them -- and thr[j] = (uint64) (drop x the row's total), `drop` = 1 -
+// top_p in double.  The sums are 64-bit INTEGER adds in LDS: any order gives the same bits, in every launch and in both kernels (a
+// float atomicAdd histogram would not).  Out: q.img[j] = image of c, q.found[j] = 0 when no value qualifies (a row without mass).
+template <bool kMass, bool kStream, bool kTf>
+__device__ inline void beam_row_select(const BeamSrc<kStream, kTf>& s, BeamSelect& q, double drop) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nb = s.p.num_beams, V = s.p.V;
+  if (tid < nb) { q.img[tid] = 0u; q.below[tid] = 0ull; q.found[tid] = 1; }
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    const unsigned mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+    for (int i = tid; i < nb * 256; i += kBeamThreads) q.hist[0][i] = 0ull;
+    __syncthreads();
+    for (int j = 0; j < nb; ++j) {
+      const unsigned prefix = q.img[j];
+      const float m = q.row_max[j], fl = q.floor[j];
+      beam_sweep<BEAM_X>(s, j, wid * 64, kBeamThreads, V, [&](int, float x, bool ok) {
+        const unsigned u = beam_okey(x);
+        if (ok && (u & mask) == prefix) {
+          unsigned long long w = 1ull;
+          if constexpr (kMass) w = (x < fl || x == -INFINITY) ? 0ull : (unsigned long long)(expf(x - m) * 4294967296.f);
+          if (w) atomicAdd(&q.hist[j][(u >> shift) & 255], w);
+        }
+      });
+    }
+    __syncthreads();
+    if (wid < nb) {      // wave j finishes row j: lane l owns bins 4 l .. 4 l + 3, ascending
+      const int j = wid;
+      unsigned long long h[4], sum = 0ull;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) { h[b] = q.hist[j][4 * lane + b]; sum += h[b]; }
+      unsigned long long inc = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = beam_shfl_up_u64(inc, o); if (lane >= o) inc += y; }
+      unsigned long long thr = q.thr[j];
+      if (kMass && pass == 0) thr = (unsigned long long)(drop * (double)beam_shfl_u64(inc, 63));
+      unsigned long long acc = q.below[j] + (inc - sum);
+      int hit = -1;
+      unsigned long long before = 0ull;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (hit < 0 && acc + h[b] > thr) { hit = b; before = acc; }
+        acc += h[b];
+      }
+      const unsigned long long votes = __ballot(hit >= 0);
+      if (votes == 0ull) { if (lane == 0) q.found[j] = 0; }
+      else if (lane == __ffsll((long long)votes) - 1) {
+        q.img[j] |= (unsigned)(4 * lane + hit) << shift;
+        q.below[j] = before;
+      }
+      if (kMass && pass == 0 && lane == 0) q.thr[j] = thr;
+    }
+    __syncthreads();
+  }
+}
+
+template <bool kStream, bool kTf, bool kSample = false>
+__global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, float* lookback_prev, int min_keep, float* scores_dump) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float red[kBeamThreads / 64];
   __shared__ int s_hist[256];
@@ -201,6 +334,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
   __shared__ BeamTf s_tf[kBeamMaxBeams];                            // (kTf)
   __shared__ uint8_t s_timed[kBeamMaxBeams];                        // (kTf) the beam's last id is a timed event
   __shared__ int s_seg_above[kBeamMaxBeams * kBeamWaves], s_seg_ties[kBeamMaxBeams * kBeamWaves];   // compaction: per (beam, wave) slice
+  __shared__ BeamSelect s_select;                                   // (kSample) the warpers' per-row selects
+  __shared__ float s_cut[kBeamMaxBeams], s_cut_k[kBeamMaxBeams];    // (kSample) the row's cut value; TopK's part of it
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nb = p.num_beams, V = p.V, T = p.cur_len, L = p.max_length, R = p.G * nb;
   const MhSampling& sp = p.sp;
@@ -211,7 +346,9 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
   BeamKV* arr = reinterpret_cast<BeamKV*>(smem + (kStream ? 0 : (((size_t)n * 4 + 15) & ~(size_t)15)));   // [k_pad] the K best, sorted
   const float* lg_pos_g = p.logits + (long)(p.cfg ? R + g * nb : g * nb) * V;    // under guidance the prompt rows are the SECOND half
   const float* lg_neg_g = p.logits + (long)g * nb * V;
-  const BeamSrc<kStream, kTf> scores{p, val, s_row, s_tf, lg_pos_g, lg_neg_g};
+  const BeamSrc<kStream, kTf> scores{p, val, s_row, s_tf, lg_pos_g, lg_neg_g, s_cut,
+                                     kSample ? beam_rng_subseed(sp.seed, sp.rng_row0 + (uint32_t)g, (uint32_t)T) : 0ull};
+  constexpr int kSel = kSample ? BEAM_KEY : BEAM_SCORE;             // what the selection below ranks
 
   // ---- per-beam processor state from the beam's own sequence: MonotonicTimeShiftLogitsProcessor (logit_processors.py:136-183)
   // and the (Conditional)Temperature of the step (:47-82; row 0 of the WHOLE call picks it unless cond_per_row) ------------------
@@ -336,10 +473,49 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
         __syncthreads();                                  // ... all have read the slot
         if (tid == 0) lookback_prev[slot] = next;
       }
-      for (int v = tid; v < V; v += kBeamThreads)       // (each thread rewrites exactly the columns it read)
-        lg_pos[v] = beam_score<kTf>(p, b, t, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);
+      for (int v = tid; v < V; v += kBeamThreads) {     // (each thread rewrites exactly the columns it read)
+        if constexpr (kSample) lg_pos[v] = beam_x<kTf>(p, b, t, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);   // (+ running score: below)
+        else lg_pos[v] = beam_score<kTf>(p, b, t, lg_pos[v], p.cfg ? lg_neg[v] : 0.f, v);
+      }
     }
     __syncthreads();
+  }
+
+  // ---- beam-sample: HF's TopKLogitsWarper, then TopPLogitsWarper (min_tokens_to_keep = min_keep), per beam row on x, as ONE cut value
+  // per row: cut = max(k'-th largest x, min(smallest x whose mass of values <= it exceeds 1 - top_p, min_keep-th largest x)) --------
+  if constexpr (kSample) {
+    const int keep = min(min_keep, V);
+    const bool top_k_on = sp.top_k > 0, top_p_on = sp.top_p < 1.0f;
+    if (tid < nb) { s_cut_k[tid] = -INFINITY; s_cut[tid] = -INFINITY; s_select.thr[tid] = (unsigned long long)(V - min(max(sp.top_k, keep), V)); }
+    if (top_k_on) {
+      beam_row_select<false>(scores, s_select, 0.0);
+      if (tid < nb) { s_cut_k[tid] = beam_okey_inv(s_select.img[tid]); s_cut[tid] = s_cut_k[tid]; }
+    }
+    if (top_p_on) {
+      __syncthreads();
+      for (int j = 0; j < nb; ++j) {         // the row's maximum (TopK keeps it)
+        float m = -INFINITY;
+        beam_sweep<BEAM_X>(scores, j, wid * 64, kBeamThreads, V, [&](int, float x, bool ok) { if (ok) m = fmaxf(m, x); });
+        m = block_max(m, red);
+        if (tid == 0) { s_select.row_max[j] = m; s_select.floor[j] = s_cut_k[j]; s_select.thr[j] = (unsigned long long)(V - keep); }
+      }
+      beam_row_select<false>(scores, s_select, 0.0);      // the min_keep-th largest x
+      float cut_keep = 0.f;
+      if (tid < nb) cut_keep = beam_okey_inv(s_select.img[tid]);
+      beam_row_select<true>(scores, s_select, 1.0 - (double)sp.top_p);
+      if (tid < nb) {
+        const float cut_p = s_select.found[tid] ? beam_okey_inv(s_select.img[tid]) : -INFINITY;
+        s_cut[tid] = fmaxf(s_cut_k[tid], fminf(cut_p, cut_keep));
+      }
+    }
+    __syncthreads();
+    if constexpr (!kStream) {      // x -> accumulated score, in place
+      for (int i = tid; i < n; i += kBeamThreads) { const int j = i / V; val[i] = beam_warp(val[i], s_cut[j], s_row[j].rs); }
+      __syncthreads();
+    }
+    if (scores_dump)
+      for (int j = 0; j < nb; ++j)
+        beam_sweep<BEAM_ACC>(scores, j, wid * 64, kBeamThreads, V, [&](int i, float x, bool ok) { if (ok) scores_dump[(long)g * n + i] = x; });
   }
 
   // ---- the K best of the chunk's num_beams x V accumulated scores, best first, ties by ascending flat index ----------------------
@@ -355,7 +531,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
     const unsigned prefix = s_prefix;
     const int rem = s_remaining;
     for (int j = 0; j < nb; ++j)
-      beam_sweep(scores, j, wid * 64, kBeamThreads, V, [&](int, float x, bool ok) {
+      beam_sweep<kSel>(scores, j, wid * 64, kBeamThreads, V, [&](int, float x, bool ok) {
         const unsigned u = beam_okey(x);
         if (ok && (u & mask) == prefix) atomicAdd(&s_hist[(u >> shift) & 255], 1);
       });
@@ -380,7 +556,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
   const int v_lo = min(wid * Vw, V), v_hi = min(v_lo + Vw, V);
   for (int j = 0; j < nb; ++j) {
     int above = 0, ties = 0;
-    beam_sweep(scores, j, v_lo, 64, v_hi, [&](int, float x, bool ok) {
+    beam_sweep<kSel>(scores, j, v_lo, 64, v_hi, [&](int, float x, bool ok) {
       const unsigned u = beam_okey(x);
       above += ok && u > kth;
       ties += ok && u == kth;
@@ -406,7 +582,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   for (int j = 0; j < nb; ++j) {
     int wpos = s_seg_above[j * kBeamWaves + wid], trank = s_seg_ties[j * kBeamWaves + wid];
-    beam_sweep(scores, j, v_lo, 64, v_hi, [&](int i, float x, bool ok) {
+    beam_sweep<kSel>(scores, j, v_lo, 64, v_hi, [&](int i, float x, bool ok) {
       const unsigned u = beam_okey(x);
       const bool is_above = ok && u > kth, is_tie = ok && u == kth;
       const unsigned long long m_above = __ballot(is_above), m_tie = __ballot(is_tie);
@@ -430,6 +606,23 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(MhBeamStep p, f
       }
       __syncthreads();
     }
+  }
+  if constexpr (kSample) {      // the K draws, in draw order: each key gives way to its accumulated score (read back / recomputed, not key - g)
+    for (int k = tid; k < K; k += kBeamThreads) {
+      const int i = arr[k].i;
+      float acc;
+      if constexpr (kStream) {
+        const int j = i / V, v = i - j * V;
+        const BeamRow b = s_row[j];
+        BeamTf t{};
+        if constexpr (kTf) t = s_tf[j];
+        acc = beam_warp(beam_x<kTf>(p, b, t, lg_pos_g[(long)j * V + v], p.cfg ? lg_neg_g[(long)j * V + v] : 0.f, v), s_cut[j], b.rs);
+      } else {
+        acc = val[i];
+      }
+      arr[k].v = acc;
+    }
+    __syncthreads();
   }
 
   // ---- stopping criteria on the K best candidates (d.) ------------------------------------------------------------------------
@@ -583,15 +776,23 @@ extern "C" int mh_beam_step_path(int num_beams, int V, int K) {
   return fits ? 1 : want == 1 ? 0 : 2;
 }
 
-// mh_beam_step (lookback_prev = nullptr, `tf` false) and mh_beam_step_tf: one set of checks, one dispatch rule
-static int beam_step_launch(const char* who, const MhBeamStep* bs, float* lookback_prev, bool tf_entry, void* stream) {
+// mh_beam_step (lookback_prev = nullptr, `tf` false), mh_beam_step_tf and mh_beam_step_sample: one set of checks, one dispatch rule
+static int beam_step_launch(const char* who, const MhBeamStep* bs, float* lookback_prev, bool tf_entry, void* stream,
+                            bool sample_entry = false, int min_keep = 0, float* scores_dump = nullptr) {
   MH_REQUIRE(bs && bs->logits && bs->eos_table && bs->run_in && bs->run_out && bs->rs_in && bs->rs_out && bs->rb_in && bs->rb_out &&
              bs->seq_in && bs->seq_out && bs->bs_in && bs->bs_out && bs->bb_in && bs->bb_out && bs->fin_in && bs->fin_out &&
              bs->heuristic_open && bs->src && bs->last && bs->flags, "%s: null argument", who);
   MH_REQUIRE(bs->G >= 1 && bs->V >= 1 && bs->num_beams >= 2 && bs->num_beams <= kBeamMaxBeams, "%s: %d chunks x %d beams (2 .. %d beams)", who, bs->G, bs->num_beams, kBeamMaxBeams);
   MH_REQUIRE(bs->K >= bs->num_beams && bs->K <= kBeamMaxK && bs->K <= (int64_t)bs->num_beams * bs->V, "%s: K = %d candidates not in [num_beams, %d]", who, bs->K, kBeamMaxK);
   MH_REQUIRE(bs->P >= 1 && bs->cur_len >= bs->P && bs->cur_len < bs->max_length, "%s: cur_len %d not in [P, max_length)", who, bs->cur_len);
-  MH_REQUIRE(bs->sp.do_sample == 0, "%s: greedy beams only (beam-sample draws on the host side)", who);
+  if (sample_entry) {
+    MH_REQUIRE(bs->sp.do_sample != 0, "%s: do_sample = %d: the sampled step needs do_sample = 1 (greedy beams are mh_beam_step)", who, bs->sp.do_sample);
+    MH_REQUIRE(min_keep >= 1, "%s: min_tokens_to_keep = %d (at least 1)", who, min_keep);
+    MH_REQUIRE(bs->sp.top_p > 0.f && bs->sp.top_p <= 1.f, "%s: top_p = %g outside (0, 1]", who, (double)bs->sp.top_p);
+    MH_REQUIRE(bs->sp.top_k >= 0, "%s: top_k = %d is negative", who, bs->sp.top_k);
+  } else {
+    MH_REQUIRE(bs->sp.do_sample == 0, "%s: greedy beams only (beam-sample is mh_beam_step_sample)", who);
+  }
   const bool tf = bs->sp.lookback_types_first && bs->sp.lookback_mask_end > bs->sp.ts_start;
   MH_REQUIRE(!tf || tf_entry, "%s: the types_first lookback renormalisation is not built for beams", who);
   MH_REQUIRE(!tf || lookback_prev, "%s: the types_first lookback renormalisation needs lookback_prev", who);
@@ -611,19 +812,34 @@ static int beam_step_launch(const char* who, const MhBeamStep* bs, float* lookba
     return set(reinterpret_cast<const void*>(beam_step_kernel<false, false>), kBeamLdsBytes) &&
                    set(reinterpret_cast<const void*>(beam_step_kernel<true, false>), kBeamMaxK * 8) &&
                    set(reinterpret_cast<const void*>(beam_step_kernel<false, true>), kBeamLdsBytes) &&
-                   set(reinterpret_cast<const void*>(beam_step_kernel<true, true>), kBeamMaxK * 8)
+                   set(reinterpret_cast<const void*>(beam_step_kernel<true, true>), kBeamMaxK * 8) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<false, false, true>), kBeamLdsBytes) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<true, false, true>), kBeamMaxK * 8) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<false, true, true>), kBeamLdsBytes) &&
+                   set(reinterpret_cast<const void*>(beam_step_kernel<true, true, true>), kBeamMaxK * 8)
                ? MH_OK : check_launch("mh_beam_step: LDS attribute");
   });
   if (arc != MH_OK) return arc;
   const size_t lds = path == 1 ? (size_t)(mh_beam_step_lds_bytes(bs->num_beams, bs->V) + k_pad * 8) : (size_t)(k_pad * 8);
   const dim3 grid(bs->G), block(kBeamThreads);
+  const hipStream_t st = (hipStream_t)stream;
+  if (sample_entry) {
+    if (path == 1) {
+      if (tf) hipLaunchKernelGGL((beam_step_kernel<false, true, true>), grid, block, lds, st, *bs, lookback_prev, min_keep, scores_dump);
+      else hipLaunchKernelGGL((beam_step_kernel<false, false, true>), grid, block, lds, st, *bs, lookback_prev, min_keep, scores_dump);
+      return check_launch(tf ? "beam_step_kernel<lds, types_first, sample>" : "beam_step_kernel<lds, sample>");
+    }
+    if (tf) hipLaunchKernelGGL((beam_step_kernel<true, true, true>), grid, block, lds, st, *bs, lookback_prev, min_keep, scores_dump);
+    else hipLaunchKernelGGL((beam_step_kernel<true, false, true>), grid, block, lds, st, *bs, lookback_prev, min_keep, scores_dump);
+    return check_launch(tf ? "beam_step_kernel<streaming, types_first, sample>" : "beam_step_kernel<streaming, sample>");
+  }
   if (path == 1) {
-    if (tf) hipLaunchKernelGGL((beam_step_kernel<false, true>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
-    else hipLaunchKernelGGL((beam_step_kernel<false, false>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+    if (tf) hipLaunchKernelGGL((beam_step_kernel<false, true>), grid, block, lds, st, *bs, lookback_prev, 0, (float*)nullptr);
+    else hipLaunchKernelGGL((beam_step_kernel<false, false>), grid, block, lds, st, *bs, lookback_prev, 0, (float*)nullptr);
     return check_launch(tf ? "beam_step_kernel<lds, types_first>" : "beam_step_kernel<lds>");
   }
-  if (tf) hipLaunchKernelGGL((beam_step_kernel<true, true>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
-  else hipLaunchKernelGGL((beam_step_kernel<true, false>), grid, block, lds, (hipStream_t)stream, *bs, lookback_prev);
+  if (tf) hipLaunchKernelGGL((beam_step_kernel<true, true>), grid, block, lds, st, *bs, lookback_prev, 0, (float*)nullptr);
+  else hipLaunchKernelGGL((beam_step_kernel<true, false>), grid, block, lds, st, *bs, lookback_prev, 0, (float*)nullptr);
   return check_launch(tf ? "beam_step_kernel<streaming, types_first>" : "beam_step_kernel<streaming>");
 }
 
@@ -631,4 +847,8 @@ extern "C" int mh_beam_step(const MhBeamStep* bs, void* stream) { return beam_st
 
 extern "C" int mh_beam_step_tf(const MhBeamStep* bs, float* lookback_prev, void* stream) {
   return beam_step_launch("mh_beam_step_tf", bs, lookback_prev, true, stream);
+}
+
+extern "C" int mh_beam_step_sample(const MhBeamStep* bs, float* lookback_prev, int min_tokens_to_keep, float* scores_dump, void* stream) {
+  return beam_step_launch("mh_beam_step_sample", bs, lookback_prev, true, stream, true, min_tokens_to_keep, scores_dump);
 }

@@ -143,6 +143,24 @@ __device__ inline float block_max(float v, float* scratch) {
   return r;
 }
 
+// ---- counter-based RNG -----------------------------------------------------------------------
+// (Philox-like mixing is overkill here; splitmix64 on (seed, row, step)).  rng_mix64 is the 64-bit word, uniform01 its top 24 bits
+// as a float in (0, 1]: (n + 0.5) / 2^24 rounded to fp32, so n = 2^24 - 1 gives exactly 1.0
+__device__ inline uint64_t rng_mix64(uint64_t seed, uint32_t row, uint32_t step) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)row * 0x100000001ull + step + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ inline float uniform01(uint64_t seed, uint32_t row, uint32_t step) {
+  const uint64_t z = rng_mix64(seed, row, step);
+  return (float)((z >> 40) + 0.5) * (1.0f / 16777216.0f);
+}
+// beam-sample (csrc/beam.hip, mh_beam_step_sample): one u per (seed, row, decode column, flat index beam * V + id).  The folding,
+// stated once: (seed, row, column) are mixed to a 64-bit sub-seed, and the flat index is the step counter of row 0 under that sub-seed
+__device__ inline uint64_t beam_rng_subseed(uint64_t seed, uint32_t row, uint32_t column) { return rng_mix64(seed, row, column); }
+__device__ inline float beam_uniform01(uint64_t subseed, uint32_t flat) { return uniform01(subseed, 0u, flat); }
+
 // exp: accurate expf for the fp32 parity path, hardware exp2-based fast path for bf16 storage
 template <typename T> __device__ inline float fexp(float x);
 template <> __device__ inline float fexp<float>(float x) { return expf(x); }

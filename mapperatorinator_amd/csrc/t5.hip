@@ -512,14 +512,7 @@ __device__ inline int history_id(const SampleP& p, int row, int i) {
   return (p.forced && i >= p.P) ? p.forced[(long)row * p.max_length + i] : p.tokens[(long)row * p.max_length + i];
 }
 
-// counter-based RNG (Philox-like mixing is overkill here; splitmix64 on (seed, row, step))
-__device__ inline float uniform01(uint64_t seed, uint32_t row, uint32_t step) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)row * 0x100000001ull + step + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (float)((z >> 40) + 0.5) * (1.0f / 16777216.0f);
-}
+// (the sampler's counter-based RNG, uniform01(seed, row, step), lives in common.hpp: the beam step draws from it too)
 
 // init: consume prompt columns 0..start_pos (processor state machine) and embed the token at start_pos, the first
 // position the per-token loop feeds (0 without prefill, P-1 after the batched prompt prefill)

@@ -418,6 +418,7 @@ class MapperatorinatorHIP:
             out = self.engine.generate_beam(audio, decoder_input_ids, decoder_attention_mask, eos, sp, int(num_beams),
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
                                             sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=kv_fp8,
+                                            **(dict(device_draw=True) if unused.get("beam_sample_kernel", False) else {}),
                                             **({} if row_bias is None else dict(row_bias=row_bias)))
             return out["tokens"].to(self.device)
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,

@@ -271,7 +271,8 @@ class SequentialWindowScheduler:
             # end early carry HF's fill (the first EOS id) and are cut at their first EOS-set id below like any other row
             from .beam import beam_search
             result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn"),
-                                 kv_fp8=True if gk.get("cross_kv_fp8") else None).to(torch.int64).cpu()
+                                 kv_fp8=True if gk.get("cross_kv_fp8") else None,
+                                 **(dict(device_draw=True) if gk.get("beam_sample_kernel") else {})).to(torch.int64).cpu()
         else:
             eng.synchronize()
             n_cols = int(n_out.item())

@@ -489,6 +489,8 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
         require_bf16_for_self_kv_fp8(model.dtype, int(getattr(sp, "num_beams", 1) or 1))
         extra["self_kv_fp8"] = True
     if getattr(sp, "num_beams", 1) > 1:
+        if generate_kwargs.get("beam_sample_kernel", False):      # opt-in: beam-sample draws inside the step kernel (beam.py `device_draw`)
+            extra["device_draw"] = True
         # HF beam search (processor.py:159 `num_beams`; the timing generator uses two beams): mapperatorinator_amd/beam.py
         out = model.engine.generate_beam(audio, prompt, mask, eos, sp, sp.num_beams, negative_prompt=neg,
                                          sample_fn=generate_kwargs.get("beam_sample_fn"),

@@ -531,11 +531,12 @@ class T5Engine:
     def generate_beam(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids,
                       sampling: _lib.MhSampling, num_beams: int, row_bias: Optional[torch.Tensor] = None,
                       length_penalty: float = 1.0, early_stopping=False, negative_prompt: Optional[torch.Tensor] = None,
-                      sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False):
+                      sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False, device_draw: bool = False):
         """mel -> encoder -> cross K/V, then HF-style beam search over the step-wise decode entry (beam.py).  Returns
         dict(tokens=int64 CPU (B, n_cols), n_cols, logits=None) like `generate`.  `negative_prompt` with sampling.cfg_scale > 1:
         classifier-free guidance under beams (the doubled batch of modeling_mapperatorinator.py:243-254; beam.py).  With
-        `sampling.do_sample` the continuations are drawn (beam-sample): `sample_fn(probs, k)` or torch.multinomial on the device.
+        `sampling.do_sample` the continuations are drawn (beam-sample): `sample_fn(probs, k)` or torch.multinomial on the device, or
+        with `device_draw=True` inside the step kernel (mh_beam_step_sample; seed sampling.seed: beam.py).
         `cross_kv_fp8`: every step streams the e4m3 copy of the cross-attention K / V (see `cross_kv_fp8()`; under guidance the copy
         is made of the doubled rows)."""
         from .beam import beam_search
@@ -558,7 +559,7 @@ class T5Engine:
             kv = self.cross_kv(self.encode_mel(self.mel(audio), row_bias=row_bias))
         self._leave()
         out = beam_search(self, kv, prompt, prompt_mask, eos_ids, sampling, num_beams, length_penalty, early_stopping,
-                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None)
+                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None, device_draw=device_draw)
         return dict(tokens=out.cpu(), n_cols=int(out.shape[1]), logits=None)
 
     def generate(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
