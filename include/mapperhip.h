@@ -710,6 +710,37 @@ int64_t mh_t5_reorder_cache_scratch_bytes(const MhT5Config* cfg, int B, int n_po
 int mh_t5_reorder_cache(const MhT5Config* cfg, int B, const int32_t* src, int n_pos, void* workspace, int64_t workspace_bytes,
                         void* scratch, int64_t scratch_bytes, void* stream);
 
+/* Beam search without cache copies (additive at ABI 11: five symbols, plain arguments, no struct).  What
+ * `MapperatorinatorCache.reorder_cache` (osuT5/osuT5/inference/cache_utils.py:16-20) does by copying whole cache rows is done by
+ * index: `origin`, device uint8 [B][tgt_len] (mh_t5_beam_index_bytes(cfg, B) bytes), names per decode row b and position j the cache
+ * row that holds that key / value.  A step writes position `pos` of cache row b and nothing else, so every (cache row, position) is
+ * written exactly once and an entry never goes stale.  tgt_len <= 2560 (one row's entries are staged in LDS), B <= 64.
+ *   mh_t5_step_indexed: mh_t5_step (cross_kv_fp8 NULL) or mh_t5_step_fp8 (cross_kv_fp8 = the packed copy) whose self-attention
+ *     reads cached row j < pos of decode row b from cache row origin[b][j] and writes its new row to cache row b.  Bias, masks,
+ *     window and the order of every sum are those of row b: with tables kept by mh_t5_reorder_index the logits are bit-identical to
+ *     mh_t5_step + mh_t5_reorder_cache.  Entries are clamped to [0, B).  No e4m3 self-cache form.
+ *   mh_t5_beam_index_init: origin[b][j] = b / kv_group for j < n_prefilled (the prompt rows of mh_t5_step_prefill), b beyond;
+ *     n_prefilled = 0 is the identity table.
+ *   mh_t5_reorder_index: origin_out[b][j] = origin_in[src[b]][j] for j < n_pos, b beyond -- `reorder_cache(beam_idx)` on the table;
+ *     src device int32 [B] may repeat rows and, under guidance, point second-half rows into the first half (`beam_idx.repeat(2)`).
+ *     origin_in != origin_out: the caller ping-pongs two tables.  One launch writing B x tgt_len bytes; no scratch.
+ *   mh_t5_step_prefill: positions 0 .. n_pos-1 (n_pos <= P, the row stride of prompt int32 [Bp][P] / prompt_mask uint8 [Bp][P] or
+ *     NULL) of Bp prompts go through the decoder at once -- HF's batched prefill, the one mh_t5_generate runs -- into cache rows
+ *     0 .. Bp-1 of the self-attention caches of a B-row step workspace (mh_t5_decode_workspace_bytes(cfg, B), which includes the
+ *     prefill's region).  cross_kv has Bp rows; B must be whole groups over the Bp prompts.  Follow it with
+ *     mh_t5_beam_index_init(cfg, B, B / Bp, n_pos, ...) and step from position n_pos.
+ * Every entry returns MH_ERR_ARG with a message before any launch for a null pointer, a pos / n_pos / n_prefilled outside the cache,
+ * rows that are not whole groups, and fp32 storage together with the e4m3 copy. */
+int64_t mh_t5_beam_index_bytes(const MhT5Config* cfg, int B);
+int mh_t5_beam_index_init(const MhT5Config* cfg, int B, int kv_group, int n_prefilled, void* origin, void* stream);
+int mh_t5_reorder_index(const MhT5Config* cfg, int B, const int32_t* src, int n_pos, const void* origin_in, void* origin_out,
+                        void* stream);
+int mh_t5_step_indexed(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
+                       int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
+                       int64_t workspace_bytes, const void* origin, void* stream);
+int mh_t5_step_prefill(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int Bp, const int32_t* prompt,
+                       const uint8_t* prompt_mask, int P, int n_pos, void* workspace, int64_t workspace_bytes, int B, void* stream);
+
 /* Teacher-forced decoder forward over whole sequences: `Mapperatorinator.forward` with `encoder_outputs` given
  * (seam B2, osuT5/osuT5/model/modeling_mapperatorinator.py:174-228; used by server.py:160-181 `model_forward`).
  *   ids  int32 [B, T] decoder_input_ids, mask uint8 [B, T] decoder_attention_mask (NULL = ones), T <= tgt_len

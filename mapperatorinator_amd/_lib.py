@@ -204,6 +204,11 @@ SYMBOLS = {
     "mh_t5_step_fp8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, VP, I, I, VP, I, VP, I, VP, VP, I64, VP]),
     "mh_t5_reorder_cache_scratch_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
     "mh_t5_reorder_cache": (I, [C.POINTER(MhT5Config), I, VP, I, VP, I64, VP, I64, VP]),
+    "mh_t5_beam_index_bytes": (I64, [C.POINTER(MhT5Config), I]),
+    "mh_t5_beam_index_init": (I, [C.POINTER(MhT5Config), I, I, I, VP, VP]),
+    "mh_t5_reorder_index": (I, [C.POINTER(MhT5Config), I, VP, I, VP, VP, VP]),
+    "mh_t5_step_indexed": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, VP, I, I, VP, I, VP, I, VP, VP, I64, VP, VP]),
+    "mh_t5_step_prefill": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, I, VP, I64, I, VP]),
     "mh_t5_forward_workspace_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
     "mh_t5_decoder_forward": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP, VP, I64, VP]),
     "mh_score_rows": (I, [VP, I64, I, I, VP, VP, VP, VP, VP, VP, VP]),

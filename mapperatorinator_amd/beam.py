@@ -49,6 +49,13 @@ for exactly this case) follows what the reference + HF do, quirk included:
   * `MapperatorinatorCache.reorder_cache` (inference/cache_utils.py:16-20) gathers the doubled cache with `beam_idx.repeat(2)` --
     indices into the FIRST half for both halves: from the first reorder on, the prompt half's self-attention cache holds copies of the
     negative half's rows.  Reproduced verbatim (golden `t5_tiny_beam.npz`, runs `b2g` / `b3g`).
+
+Long targets (opt-in, `cache="indexed"`): step (g) copies the whole cache after every token -- 4 x the cache's bytes up to the current
+position.  The indexed route keeps every cache row where its step wrote it and lets attention follow a uint8 (rows, tgt_len) table
+instead (`mh_t5_step_indexed`; a reorder is `mh_t5_reorder_index` from one table into the other, `beam_idx.repeat(2)` included):
+bit-identical logits, no scratch buffer.  `prefill=True` on top of it sends positions 0 .. P-2 of each chunk's prompt (all beams of a
+chunk carry the same one) through the batched prefill of mh_t5_generate once (`mh_t5_step_prefill`) and starts the table with
+origin = the chunk's row for those positions.
 """
 from __future__ import annotations
 
@@ -213,6 +220,58 @@ def _step_kv_fp8(engine, cross_kv: torch.Tensor, kv_fp8):
     return kv_fp8
 
 
+def _check_cache_mode(cache, prefill):
+    if cache not in ("copy", "indexed"):
+        raise ValueError(f"beam cache {cache!r}: expected 'copy' or 'indexed'")
+    if prefill and cache != "indexed":
+        raise ValueError("the batched prompt prefill of the beam search (prefill / beam_prefill) needs cache='indexed'")
+
+
+class _IndexedCache:
+    """cache="indexed": the self-attention cache rows stay where the steps wrote them; two uint8 (rows, tgt_len) tables say which
+    cache row holds each (row, position) (mh_t5_step_indexed), and a reorder permutes table rows (mh_t5_reorder_index) from one
+    table into the other.  `prefill` (n positions of the `groups` prompts, one mh_t5_step_prefill call) fills cache rows
+    0 .. groups-1 and starts the table with them."""
+
+    def __init__(self, lib, p, rows, kv_group, dev, stream):
+        self.lib, self.p, self.rows, self.kv_group, self.stream = lib, p, rows, kv_group, stream
+        n = int(lib.mh_t5_beam_index_bytes(C.byref(p.cfg), rows))
+        if n <= 0:
+            raise ValueError(f"the index table does not cover {rows} rows")
+        self.tables = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.cur = 0
+
+    def init(self, n_prefilled: int):
+        _lib.check(self.lib.mh_t5_beam_index_init(C.byref(self.p.cfg), self.rows, self.kv_group, int(n_prefilled),
+                                                  self.tables[self.cur].data_ptr(), self.stream), "mh_t5_beam_index_init")
+
+    def prefill(self, cross_kv, prompts, masks, n_pos, ws):
+        """prompts int32 (groups, P) on the device, masks uint8 (groups, P) or None: positions 0 .. n_pos-1 of every prompt"""
+        P = prompts.shape[1]
+        rc = self.lib.mh_t5_step_prefill(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), prompts.shape[0],
+                                         prompts.data_ptr(), _lib.ptr(masks), P, int(n_pos), ws.data_ptr(), ws.numel(), self.rows,
+                                         self.stream)
+        _lib.check(rc, "mh_t5_step_prefill")
+        self.init(n_pos)
+
+    def step(self, cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws):
+        rc = self.lib.mh_t5_step_indexed(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), _lib.ptr(kv_fp8), self.rows,
+                                         self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), self.tables[self.cur].data_ptr(), self.stream)
+        _lib.check(rc, "mh_t5_step_indexed")
+
+    def reorder(self, src, n_pos):
+        rc = self.lib.mh_t5_reorder_index(C.byref(self.p.cfg), self.rows, src.data_ptr(), int(n_pos), self.tables[self.cur].data_ptr(),
+                                          self.tables[self.cur ^ 1].data_ptr(), self.stream)
+        _lib.check(rc, "mh_t5_reorder_index")
+        self.cur ^= 1
+
+
+def _prefill_prompts(ids0e, mask, nb):
+    """the (group) prompts of the (group, beam) rows the engine is fed: every nb-th row (all beams of a group carry the same prompt)"""
+    return ids0e[::nb].to(torch.int32).contiguous(), None if mask is None else mask[::nb].contiguous()
+
+
 def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P, logits, ws, stream):
     """One decoder position for all (chunk, beam) rows: mh_t5_step, or mh_t5_step_fp8 over the e4m3 copy when there is one."""
     if kv_fp8 is None:
@@ -227,11 +286,13 @@ def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P
 
 @torch.no_grad()
 def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                        kv_fp8=None, sample_keep: Optional[int] = None) -> torch.Tensor:
+                        kv_fp8=None, sample_keep: Optional[int] = None, cache: str = "copy", prefill: bool = False) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
     D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs.  With the
     types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is.
-    `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep."""
+    `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep.
+    `cache` / `prefill`: see `beam_search`."""
+    _check_cache_mode(cache, prefill)
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = neg_mask = None
@@ -297,9 +358,13 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     flags_host = torch.zeros((G, 3), dtype=torch.int32).pin_memory()
     need = lib.mh_t5_decode_workspace_bytes(C.byref(p.cfg), RE)
     ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
-    scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     logits = torch.empty((RE, V), dtype=torch.float32, device=dev)
     stream = engine._s()
+    scratch = idx = None
+    if cache == "indexed":      # two index tables instead of the copy's scratch buffer
+        idx = _IndexedCache(lib, p, RE, nb, dev, stream)
+    else:
+        scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     bs = _lib.MhBeamStep()
     bs.logits, bs.eos_table = logits.data_ptr(), eos_table.data_ptr()
     bs.G, bs.num_beams, bs.V, bs.P, bs.max_length, bs.K = G, nb, V, P, max_length, K
@@ -311,11 +376,21 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     bs.heuristic_open, bs.src, bs.last, bs.flags = heuristic_open.data_ptr(), src.data_ptr(), feed.data_ptr(), flags.data_ptr()
 
     def step(tokens: torch.Tensor, pos: int):
-        _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
+        if idx is not None:
+            idx.step(cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws)
+        else:
+            _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
 
     engine._enter()
     with torch.cuda.stream(engine.stream):
-        for pos in range(P - 1):
+        first_pos = 0
+        if idx is not None:
+            if prefill and P > 1:      # the prompts' positions 0 .. P-2 in one batched pass, once per group
+                idx.prefill(cross_kv, *_prefill_prompts(ids0e, mask, nb), P - 1, ws)
+                first_pos = P - 1
+            else:
+                idx.init(0)
+        for pos in range(first_pos, P - 1):
             step(ids0e[:, pos].contiguous(), pos)
         feed.copy_(ids0e[:, P - 1])                    # the last prompt column (under guidance the first half has the negative prompt's)
         cur_len, par = P, 0
@@ -337,9 +412,12 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
             par ^= 1
             # (`src` / `feed` were written by the kernel for all RE rows: under guidance `beam_idx.repeat(2)`, cache_utils.py:18, and the
             # beam's token for both halves)
-            rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(),
-                                         scratch.data_ptr(), scratch.numel(), stream)
-            _lib.check(rc, "mh_t5_reorder_cache")
+            if idx is not None:
+                idx.reorder(src, cur_len)
+            else:
+                rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(),
+                                             scratch.data_ptr(), scratch.numel(), stream)
+                _lib.check(rc, "mh_t5_reorder_cache")
             cur_len += 1
             flags_host.copy_(flags, non_blocking=True)
             engine.stream.synchronize()
@@ -359,7 +437,8 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
 @torch.no_grad()
 def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids, sp,
                 num_beams: int, length_penalty: float = 1.0, early_stopping=False, sample_fn=None,
-                use_kernel: Optional[bool] = None, kv_fp8=None, device_draw: bool = False) -> torch.Tensor:
+                use_kernel: Optional[bool] = None, kv_fp8=None, device_draw: bool = False, cache: str = "copy",
+                prefill: bool = False) -> torch.Tensor:
     """cross_kv: the G chunks' cross K/V (engine.cross_kv); prompt int (G, P) left-padded, prompt_mask (G, P) or None.
     Under guidance (sp.cfg_scale > 1) `prompt` / `prompt_mask` carry 2G rows, [negative-prompt rows | prompt rows] (what
     T5Engine.generate and the scheduler build), and cross_kv still has G rows.
@@ -371,7 +450,14 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     the copy (mh_t5_step_fp8) instead of `cross_kv`.  bf16 storage only.
     `device_draw` (beam-sample only; ignored under greedy beams): the continuations are drawn by the library's rule (Gumbel top-K on
     its counter-based generator, seed sp.seed: module docstring) instead of torch.multinomial -- in the step kernel,
-    mh_beam_step_sample (`use_kernel` None / True), or by the same rule in torch ops (`use_kernel` False).  Not with `sample_fn`."""
+    mh_beam_step_sample (`use_kernel` None / True), or by the same rule in torch ops (`use_kernel` False).  Not with `sample_fn`.
+    `cache`: "copy" (the default) reorders the self-attention caches as HF does, row b <- row src[b] after every token
+    (mh_t5_reorder_cache).  "indexed" copies nothing: the steps read the cached rows through an index table (mh_t5_step_indexed) and a
+    reorder permutes table rows (mh_t5_reorder_index) -- the same logits bit for bit; tgt_len <= 2560.
+    `prefill` (with cache="indexed" only): positions 0 .. P-2 of the prompt go through the batched prefill once per chunk
+    (mh_t5_step_prefill) instead of one step per column and (chunk, beam) row.  The prefill's MFMA sums are ordered differently from
+    the token step's, as in mh_t5_generate: the same cache rows as that entry writes, not bit-identical to the token-by-token feed."""
+    _check_cache_mode(cache, prefill)
     if device_draw and sample_fn is not None:
         raise ValueError("device_draw draws inside the library: it cannot be combined with sample_fn")
     device_draw = bool(device_draw) and bool(sp.do_sample)
@@ -384,14 +470,14 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
                                       "beams > 8192)")
         if can_draw and use_kernel is not False:
             return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2)
+                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2, cache=cache, prefill=prefill)
     can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(eos_ids)) and sample_fn is None
     if use_kernel is True and not can:
         raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
                                   "K = max(2, 1 + #eos) x beams > 8192)")
     if can and use_kernel is not False:
         return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                   kv_fp8=kv_fp8)
+                                   kv_fp8=kv_fp8, cache=cache, prefill=prefill)
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = None
@@ -447,17 +533,32 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
 
     need = lib.mh_t5_decode_workspace_bytes(C.byref(p.cfg), RE)
     ws = torch.empty(int(need), dtype=torch.uint8, device=dev)                        # owned by this call: holds the caches
-    scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     logits = torch.empty((RE, V), dtype=torch.float32, device=dev)
     stream = engine._s()
+    scratch = idx = None
+    if cache == "indexed":      # two index tables instead of the copy's scratch buffer
+        idx = _IndexedCache(lib, p, RE, nb, dev, stream)
+    else:
+        scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     scale = float(sp.cfg_scale)
 
     def step(tokens: torch.Tensor, pos: int):
-        _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens.to(torch.int32).contiguous(), pos, mask, P, logits, ws, stream)
+        tokens = tokens.to(torch.int32).contiguous()
+        if idx is not None:
+            idx.step(cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws)
+        else:
+            _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
 
     engine._enter()
     with torch.cuda.stream(engine.stream):
-        for pos in range(P - 1):                                                      # the prompt, token by token
+        first_pos = 0
+        if idx is not None:
+            if prefill and P > 1:      # the prompts' positions 0 .. P-2 in one batched pass, once per group
+                idx.prefill(cross_kv, *_prefill_prompts(ids0e, mask, nb), P - 1, ws)
+                first_pos = P - 1
+            else:
+                idx.init(0)
+        for pos in range(first_pos, P - 1):                                           # the prompt, token by token
             step(ids0e[:, pos], pos)
         cur_len = P
         first = True
@@ -508,9 +609,12 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
             src = running_bidx[..., cur_len - P].reshape(R).to(torch.int32).contiguous()
             if cfg:      # `beam_idx.repeat(2)` (cache_utils.py:18): BOTH halves take their rows from the first half
                 src = torch.cat([src, src], 0).contiguous()
-            rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(), scratch.data_ptr(),
-                                         scratch.numel(), stream)
-            _lib.check(rc, "mh_t5_reorder_cache")
+            if idx is not None:
+                idx.reorder(src, cur_len)
+            else:
+                rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(), scratch.data_ptr(),
+                                             scratch.numel(), stream)
+                _lib.check(rc, "mh_t5_reorder_cache")
             cur_len += 1
             if early_stopping == "never" and length_penalty > 0.0:
                 hyp_len = max_length - P

@@ -877,28 +877,43 @@ __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key g
 // SC (the e4m3 self-attention cache): every key row carries its own fp32 scale pair, kscale_row[j] / vscale_row[j], fetched the
 // way the bias is (one value per key per 8-lane group, clamped index, unconditional load); the key scale multiplies the score
 // before bias and mask, the value scale multiplies the probability before the accumulate
-template <typename T, int U, typename E = T, bool SC = false>
+// IDX (beam search over an index table, mh_t5_step_indexed): key / value row j of this head comes from cache row origin[j] -- kbase /
+// vbase are then head h of cache row 0, `origin` the decode row's table entries in LDS and `row_stride` the elements between two
+// cache rows (H * tgt_len * 64).  An 8-lane group still reads one whole row; only the row's base differs from key to key.
+template <typename T, int U, typename E = T, bool SC = false, bool IDX = false>
 __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kbase, const E* vbase, int j0,
                                    int jend, int jstride, const float* bias_row, int pos, const uint8_t* mask_row,
                                    int P, float scale, int jmin = 0,   // keys below jmin are masked (sliding window)
-                                   const float* kscale_row = nullptr, const float* vscale_row = nullptr) {
+                                   const float* kscale_row = nullptr, const float* vscale_row = nullptr,
+                                   const uint8_t* origin = nullptr, long row_stride = 0) {
   // processes keys j0, j0+jstride, ... < jend for this lane's key group, U at a time
   const int c8 = (threadIdx.x & 7) * 8;
   for (int j = j0; j < jend; j += jstride * U) {
     float s[U];
     float kv[U][8];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int jj = j + u * jstride;
-      const int jc = jj < jend ? jj : j;
-      load8_stream<E>(kbase + (long)jc * 64 + c8, kv[u]);
-    }
     float vv[U][8];
+    if constexpr (IDX) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int jj = j + u * jstride;
-      const int jc = jj < jend ? jj : j;
-      load8_stream<E>(vbase + (long)jc * 64 + c8, vv[u]);
+      for (int u = 0; u < U; ++u) {
+        const int jj = j + u * jstride;
+        const int jc = jj < jend ? jj : j;
+        const long row = (long)origin[jc] * row_stride + (long)jc * 64 + c8;   // the cache row that holds key jc
+        load8_stream<E>(kbase + row, kv[u]);
+        load8_stream<E>(vbase + row, vv[u]);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int jj = j + u * jstride;
+        const int jc = jj < jend ? jj : j;
+        load8_stream<E>(kbase + (long)jc * 64 + c8, kv[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int jj = j + u * jstride;
+        const int jc = jj < jend ? jj : j;
+        load8_stream<E>(vbase + (long)jc * 64 + c8, vv[u]);
+      }
     }
     // bias / mask values: wave-uniform branch on the pointers, unconditional loads from clamped indices
     float bv[U];
@@ -1001,6 +1016,12 @@ struct SelfKv8P {
   float* ks; float* vs;          // fp32 scales [B][H][tgt_len]
 };
 struct NoSelfKv8P {};
+// ... or the index table of a beam search (IDX instantiations, mh_t5_step_indexed): uint8 [B][tgt_len], entry [b][j] = the cache row
+// that holds key / value j of decode row b
+struct SelfIdxP {
+  const uint8_t* origin;
+};
+constexpr int kSelfIdxMaxTgt = 2560;   // table entries of one row staged in LDS (the released tgt_seq_len)
 
 // merge the NW waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
 template <typename T, int NW = 4>
@@ -1254,13 +1275,18 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
 // F8 (bf16 storage only; mh_t5_generate_skv8): keys 0 .. pos-1 come from the e4m3 shadow cache `f8` with their per-row scales (64-byte
 // rows, 8 bytes per lane); the new key / value are attended at storage precision from LDS as ever, written to the bf16 cache as ever
 // (256 bytes per workgroup: the bf16 cache stays valid for everything that reads it) and appended to the shadow by waves 1 / 2
-template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false>
+// IDX (mh_t5_step_indexed: beam search without cache copies): cached key / value j < pos of decode row b is read from cache row
+// origin[b][j]; the new row is still written to cache row b at pos.  The row's table entries are requested with the first round trip
+// and staged in LDS, so that the key loop has no dependent global load in front of its K / V loads.  Everything else -- bias, masks,
+// window, the order of every sum -- is per decode row b as in the plain form: same bits as a cache whose rows were copied.
+template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false, bool IDX = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))   // 16 waves = 4 per SIMD: the whole 128-register budget
 void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_, const int* pos_,
                                                                  const void* kc_, const void* vc_, int H_, int d_, SelfAttnP p,
                                                                  HeadProjP hp,   // leading scalars: preloaded kernel arguments
-                                                                 typename std::conditional<F8, SelfKv8P, NoSelfKv8P>::type f8) {
+                                                                 typename std::conditional<F8, SelfKv8P, typename std::conditional<IDX, SelfIdxP, NoSelfKv8P>::type>::type f8) {
   static_assert(!F8 || sizeof(T) == 2, "the e4m3 shadow cache is made of bf16 rows");
+  static_assert(!(F8 && IDX), "the e4m3 shadow cache has no indexed form");
   hp.h = h_; hp.ln_w = lnw_; hp.W = W_; hp.ldh = d_; hp.ldw = d_; hp.d = d_;
   p.pos = pos_; p.kc = kc_; p.vc = vc_; p.H = H_;
   const int inner = H_ * 64;
@@ -1278,6 +1304,26 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   // they used to be two serial round trips at the END of the kernel)
   NormRow<T, LN> nrow;
   nrow.issue(hp, b);
+  uint8_t* org = nullptr;
+  if constexpr (IDX) {
+    __shared__ uint8_t org_lds[kSelfIdxMaxTgt];
+    org = org_lds;
+    // this row's table entries, all tgt_len of them (the position is itself a load: nothing here waits for it), clamped to the
+    // batch so that no table content can send a K / V load outside the cache; visible to every wave after the barriers of
+    // nrow.finish
+    const uint8_t* orow = f8.origin + (long)b * p.tgt_len;
+    uint8_t o3[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int i = (int)threadIdx.x + u * 1024;
+      o3[u] = orow[i < p.tgt_len ? i : 0];
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int i = (int)threadIdx.x + u * 1024;
+      if (i < p.tgt_len && i < kSelfIdxMaxTgt) org[i] = (int)o3[u] < p.B ? o3[u] : (uint8_t)(p.B - 1);
+    }
+  }
   const int pos = *p.pos;
   // (F8, the Whisper family at d = 896: the scale pairs of the key loop on top of the 21 weight vectors spill; one projection at a
   // time, as d = 1024 -- the same sums in the same order)
@@ -1347,6 +1393,11 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
                                    reinterpret_cast<const fp8_t*>(f8.v8) + bh * p.tgt_len * 64, j_first + wid * 8 + g, pos, 8 * NW,
                                    bias_row, pos, mask_row, p.P, sc, (WH && p.window > 0) ? pos - p.window : 0,
                                    f8.ks + bh * p.tgt_len, f8.vs + bh * p.tgt_len);
+  } else if constexpr (IDX) {   // head h of cache row 0; every key adds its own row's offset
+    const long row_stride = (long)p.H * p.tgt_len * 64;
+    attend_keys<T, 2, T, false, true>(st, q, kcache - (long)b * row_stride, vcache - (long)b * row_stride, j_first + wid * 8 + g, pos,
+                                      8 * NW, bias_row, pos, mask_row, p.P, sc, (WH && p.window > 0) ? pos - p.window : 0, nullptr,
+                                      nullptr, org, row_stride);
   } else {
     attend_keys<T, 2>(st, q, kcache, vcache, j_first + wid * 8 + g, pos, 8 * NW, bias_row, pos, mask_row, p.P, sc,
                       (WH && p.window > 0) ? pos - p.window : 0);

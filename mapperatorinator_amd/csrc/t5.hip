@@ -1146,11 +1146,24 @@ DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
 #define MH_SELF_LEAD_ARGS hp.h, hp.ln_w, hp.W, sa.pos, sa.kc, sa.vc, sa.H, hp.d
 #define MH_CROSS_LEAD_ARGS hp.h, hp.ln_w, hp.W, ca.k, ca.v, ca.H, ca.L, hp.d, ca.kv_B
 // f8 != NULL: the F8 instantiation over this layer's rows of the e4m3 shadow cache (bf16 storage only)
+// origin != NULL: the IDX instantiation, cached rows read through the beam search's index table (mh_t5_step_indexed; never with f8)
 template <typename T, int KC>
-int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8) {
+int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8,
+                    const uint8_t* origin = nullptr) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d && inner == sa.H * 64, "decode: dense residual rows / projection weights expected");
   const dec::NoSelfKv8P no8{};
-  if (f8) {
+  if (origin) {
+    MH_REQUIRE(!f8, "decode: the e4m3 self-attention cache has no indexed form");
+    MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
+               dec::kSelfIdxMaxTgt, sa.tgt_len);
+    const dec::SelfIdxP ix{origin};
+    if (sa.rope && hp.ln_b)
+      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
+    else if (sa.rope)
+      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
+    else
+      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
+  } else if (f8) {
     if constexpr (sizeof(T) == 2) {
       if (sa.rope && hp.ln_b)
         hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
@@ -1213,6 +1226,7 @@ struct StepCall {
   int kv_group;                          // > 1: rows are (chunk, beam) pairs and row b reads cross K/V row b / kv_group
   int has_rows; RowSetP rows;            // has_rows: the sampler reads its settings per returned row (mh_t5_generate_rows)
   unsigned long long* timing_buf; int timing_ring;   // the timing hook as it stood when the call was built
+  const uint8_t* origin;                 // beam search by index (mh_t5_step_indexed): uint8 [Bfull][tgt_len], else NULL
 };
 static_assert(std::is_trivially_copyable<StepCall>::value, "StepCall is keyed by its bytes");
 void step_call_init(StepCall* k, const MhT5Config* c, const MhT5Weights* w) {
@@ -1287,7 +1301,7 @@ int enqueue_step(const StepCall& k, hipStream_t s) {
       f8.ks = bf.self8_scales + self8.scale(l, 0); f8.vs = bf.self8_scales + self8.scale(l, 1);
     }
     const dec::HeadProjP qkv = head_proj(c, bf.h, w->dec_ln1[l], hf ? w->dec_ln1_b[l] : nullptr, w->dec_qkv[l]);
-    MH_TRY(dispatch_kc(qkv.d, [&](auto kc) { return launch_self_qkv<T, decltype(kc)::value>(sa, qkv, inner, s, bf.self8 ? &f8 : nullptr); }));
+    MH_TRY(dispatch_kc(qkv.d, [&](auto kc) { return launch_self_qkv<T, decltype(kc)::value>(sa, qkv, inner, s, bf.self8 ? &f8 : nullptr, k.origin); }));
     MH_TRY(skinny_resid<T>(o_gemv(k, w->dec_o[l], w->dec_o_b[l]), s));
     // cross attention (+ query projection)
     dec::CrossAttnP ca = cross_attn(c, k.cross_kv, kvB, l, bf.attn, B);
@@ -1424,8 +1438,12 @@ int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64
 // (HF prefill: SURVEY.md appendix A.1).  Position P-1 is left to the per-token loop, which also produces the
 // first sampled token.  Left-pad keys are masked, left-pad query rows produce unused garbage, as in HF.
 int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kvB, const int32_t* prompt,
-                   const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s) {
+                   const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s,
+                   int cache_rows = 0) {
   // P = row stride of `prompt` / `prompt_mask`, np <= P = positions that go through the stack
+  // cache_rows: rows of the caches self_k / self_v point into (their layer stride); 0 = B.  More than B (mh_t5_step_prefill): the
+  // B prompts fill cache rows 0 .. B-1 of every layer
+  if (cache_rows <= 0) cache_rows = B;
   const int rows = B * np;
   const int d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff, L = c->src_len, tgt = c->tgt_len;
   const int es = es_of(c->dtype);
@@ -1453,8 +1471,8 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
                        (char*)pb.cross_vt + (long)l * kvB * inner * pb.Lpad * es, pb.Lpad, kvB, H, c->dtype, s));
   MhGemm g;
   for (int l = 0; l < c->n_dec_layers; ++l) {
-    char* kc = (char*)self_k + (long)l * B * H * tgt * 64 * es;
-    char* vc = (char*)self_v + (long)l * B * H * tgt * 64 * es;
+    char* kc = (char*)self_k + (long)l * cache_rows * H * tgt * 64 * es;
+    char* vc = (char*)self_v + (long)l * cache_rows * H * tgt * 64 * es;
     // self attention over the prompt
     MH_TRY(pre_norm(c, pb.h, w->dec_ln1[l], w->dec_ln1_b[l], pb.n, rows, c->dtype, s));
     g = MhGemm{};
@@ -2294,10 +2312,13 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
 // mh_t5_step (fp8 = false) and mh_t5_step_fp8
 static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, bool fp8, const void* cross_kv_fp8, int B,
                      int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
-                     int64_t workspace_bytes, void* stream, const char* who) {   // who: the entry the caller used (error messages)
+                     int64_t workspace_bytes, void* stream, const char* who,   // who: the entry the caller used (error messages)
+                     bool indexed = false, const uint8_t* origin = nullptr) {
   MH_TRY(check_cfg(c, who));
   MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace, "%s: null argument", who);
+  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace && (origin || !indexed), "%s: null argument", who);
+  MH_REQUIRE(!indexed || c->tgt_len <= dec::kSelfIdxMaxTgt, "%s: the index table covers tgt_len <= %d (got %d)", who,
+             dec::kSelfIdxMaxTgt, c->tgt_len);
   MH_REQUIRE(!fp8 || c->dtype == MH_BF16, "%s: the fp8 cross K/V copy needs bf16 storage", who);
   MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64]", who, B);
   MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "%s: %d rows are not whole groups of %d", who, B, kv_group);
@@ -2310,6 +2331,7 @@ static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cros
   k.cross_kv = cross_kv; k.Bc = k.Bfull = B; k.kvB = B / kv_group; k.prompt_mask = prompt_mask; k.P = P; k.kv_group = kv_group;
   k.bf = decode_layout(c, B, workspace).bf;
   k.bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
+  k.origin = origin;
   if (fp8) { k.kv8 = cross_kv_fp8; k.kv8_scales = (const float*)((const char*)cross_kv_fp8 + cross_kv8_layout(c, k.kvB).scales_offset); }
   const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
   const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
@@ -2365,4 +2387,87 @@ extern "C" int mh_t5_reorder_cache(const MhT5Config* c, int B, const int32_t* sr
     hipLaunchKernelGGL(cache_scatter_kernel<T>, grid, dim3(256), 0, s, (T*)self_k, (T*)self_v, (const T*)scratch, B, H, c->tgt_len, n_pos, layer_stride);
     return check_launch("cache reorder");
   });
+}
+
+// ---- beam search by index: the self-attention cache stays where it was written ---------------------------------------------
+// The caches of a (chunk, beam) batch are never copied.  A table origin uint8 [B][tgt_len] says, per decode row b and position j, which
+// cache row holds that key / value; the step reads through it (dec_self_attn_qkv_kernel, IDX) and a reorder permutes table rows.  A
+// step writes position `pos` of cache row b and nothing else, so every (cache row, position) is written once and an entry never goes
+// stale.
+namespace mh {
+namespace {
+__global__ __launch_bounds__(256) void beam_index_init_kernel(uint8_t* origin, int tgt, int kv_group, int n_prefilled) {
+  const int b = blockIdx.x;
+  for (int j = threadIdx.x; j < tgt; j += 256) origin[(long)b * tgt + j] = (uint8_t)(j < n_prefilled ? b / kv_group : b);
+}
+// out[b][j] = in[src[b]][j] for j < n_pos, b beyond (src clamped to the batch: a table entry is always a cache row)
+__global__ __launch_bounds__(256) void beam_index_reorder_kernel(const uint8_t* in, uint8_t* out, const int32_t* src, int B, int tgt,
+                                                                int n_pos) {
+  const int b = blockIdx.x;
+  int sb = src[b];
+  sb = sb < 0 ? 0 : (sb >= B ? B - 1 : sb);
+  for (int j = threadIdx.x; j < tgt; j += 256) out[(long)b * tgt + j] = j < n_pos ? in[(long)sb * tgt + j] : (uint8_t)b;
+}
+}  // namespace
+}  // namespace mh
+
+extern "C" int64_t mh_t5_beam_index_bytes(const MhT5Config* c, int B) {
+  if (!c || B <= 0 || B > 64 || c->tgt_len <= 0) return -1;
+  return (int64_t)B * c->tgt_len;
+}
+
+extern "C" int mh_t5_beam_index_init(const MhT5Config* c, int B, int kv_group, int n_prefilled, void* origin, void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_beam_index_init"));
+  MH_REQUIRE(origin, "mh_t5_beam_index_init: null argument");
+  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_beam_index_init: batch %d not in [1, 64]", B);
+  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_beam_index_init: %d rows are not whole groups of %d", B, kv_group);
+  MH_REQUIRE(n_prefilled >= 0 && n_prefilled < c->tgt_len, "mh_t5_beam_index_init: %d prefilled positions outside the cache (tgt_len %d)",
+             n_prefilled, c->tgt_len);
+  hipLaunchKernelGGL(mh::beam_index_init_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (uint8_t*)origin, c->tgt_len, kv_group,
+                     n_prefilled);
+  return check_launch("beam_index_init_kernel");
+}
+
+extern "C" int mh_t5_reorder_index(const MhT5Config* c, int B, const int32_t* src, int n_pos, const void* origin_in, void* origin_out,
+                                   void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_reorder_index"));
+  MH_REQUIRE(src && origin_in && origin_out, "mh_t5_reorder_index: null argument");
+  MH_REQUIRE(origin_in != origin_out, "mh_t5_reorder_index: origin_in and origin_out must be two tables (the caller ping-pongs)");
+  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_reorder_index: batch %d not in [1, 64]", B);
+  MH_REQUIRE(n_pos > 0 && n_pos <= c->tgt_len, "mh_t5_reorder_index: %d positions outside the cache (tgt_len %d)", n_pos, c->tgt_len);
+  hipLaunchKernelGGL(mh::beam_index_reorder_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)origin_in,
+                     (uint8_t*)origin_out, src, B, c->tgt_len, n_pos);
+  return check_launch("beam_index_reorder_kernel");
+}
+
+// mh_t5_step / mh_t5_step_fp8 (cross_kv_fp8 != NULL) reading the cached keys / values through `origin`
+extern "C" int mh_t5_step_indexed(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
+                                  int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
+                                  void* workspace, int64_t workspace_bytes, const void* origin, void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  return step_impl(c, w, cross_kv, cross_kv_fp8 != nullptr, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace,
+                   workspace_bytes, stream, "mh_t5_step_indexed", true, (const uint8_t*)origin);
+}
+
+// positions 0 .. n_pos-1 of Bp prompts through the batched prefill (prefill_prompt: HF's one forward over the prompt) into cache rows
+// 0 .. Bp-1 of a B-row step workspace
+extern "C" int mh_t5_step_prefill(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int Bp, const int32_t* prompt,
+                                  const uint8_t* prompt_mask, int P, int n_pos, void* workspace, int64_t workspace_bytes, int B,
+                                  void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_step_prefill"));
+  MH_TRY(check_decode_shape(c, "mh_t5_step_prefill"));
+  MH_REQUIRE(w && cross_kv && prompt && workspace, "mh_t5_step_prefill: null argument");
+  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step_prefill: batch %d not in [1, 64]", B);
+  MH_REQUIRE(Bp > 0 && B % Bp == 0, "mh_t5_step_prefill: %d rows are not whole groups over %d prompts", B, Bp);
+  MH_REQUIRE(n_pos >= 1 && n_pos <= P && n_pos < c->tgt_len, "mh_t5_step_prefill: %d positions outside the prompt (%d columns) or the cache (tgt_len %d)",
+             n_pos, P, c->tgt_len);
+  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step_prefill: workspace too small");
+  MH_TRY(check_arch2_weights(c, w, "mh_t5_step_prefill"));
+  const DecodeLayout ly = decode_layout(c, B, workspace);
+  PrefillBuf pb;
+  prefill_layout(c, Bp, n_pos, (char*)workspace + ly.end, workspace_bytes - ly.end, &pb);
+  return prefill_prompt(c, w, cross_kv, Bp, Bp, prompt, prompt_mask, P, n_pos, ly.bf.self_k, ly.bf.self_v, pb, (hipStream_t)stream, B);
 }

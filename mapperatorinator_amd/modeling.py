@@ -384,7 +384,7 @@ class MapperatorinatorHIP:
         reference's `model_generate` calls it (server.py:143-151): the processor OBJECTS are translated
         (server.sampling_from_processors), `past_key_values` / `use_cache` are accepted and unused (the engine owns
         its caches).  Returns int64 (B, prompt + new) on the model's device, pad_token_id after each row's EOS."""
-        from .server import sampling_from_processors
+        from .server import beam_cache_kwargs, sampling_from_processors
         audio = inputs if inputs is not None else frames
         if decoder_input_ids is None:
             raise ValueError("decoder_input_ids is required (the reference always passes the prompt)")
@@ -410,6 +410,7 @@ class MapperatorinatorHIP:
         kv_fp8 = bool(unused.get("cross_kv_fp8", False))
         if kv_fp8:
             require_bf16_for_cross_kv_fp8(self.dtype)
+        beam_cache = beam_cache_kwargs(unused)     # beam_cache / beam_prefill (beam.py): ValueError for a bad combination
         skv8 = {}
         if unused.get("self_kv_fp8", False):     # e4m3 shadow of the self-attention cache (T5Engine.decode): bf16 storage, no beams
             require_bf16_for_self_kv_fp8(self.dtype, int(num_beams))
@@ -419,6 +420,7 @@ class MapperatorinatorHIP:
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
                                             sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=kv_fp8,
                                             **(dict(device_draw=True) if unused.get("beam_sample_kernel", False) else {}),
+                                            **beam_cache,
                                             **({} if row_bias is None else dict(row_bias=row_bias)))
             return out["tokens"].to(self.device)
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,

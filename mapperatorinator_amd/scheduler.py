@@ -26,7 +26,7 @@ from typing import Callable, Optional
 
 import torch
 
-from .server import _build_generation_stats, build_row_sampling, build_sampling, row_call_key
+from .server import _build_generation_stats, beam_cache_kwargs, build_row_sampling, build_sampling, row_call_key
 from .t5_engine import HostStager, require_bf16_for_self_kv_fp8
 
 
@@ -272,7 +272,8 @@ class SequentialWindowScheduler:
             from .beam import beam_search
             result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn"),
                                  kv_fp8=True if gk.get("cross_kv_fp8") else None,
-                                 **(dict(device_draw=True) if gk.get("beam_sample_kernel") else {})).to(torch.int64).cpu()
+                                 **(dict(device_draw=True) if gk.get("beam_sample_kernel") else {}),
+                                 **{k[5:]: v for k, v in beam_cache_kwargs(gk).items()}).to(torch.int64).cpu()
         else:
             eng.synchronize()
             n_cols = int(n_out.item())

@@ -409,6 +409,16 @@ def sampling_from_processors(processors, vocab_size_out: int, *, do_sample=False
     return sp
 
 
+def beam_cache_kwargs(generate_kwargs: dict) -> dict:
+    """generate_kwargs["beam_cache"] ("copy", the default, or "indexed") and ["beam_prefill"] as the keyword arguments of
+    T5Engine.generate_beam; nothing when both are at their defaults.  An unknown value, or the prefill without the indexed cache,
+    is a ValueError (beam.py)."""
+    from .beam import _check_cache_mode
+    cache, prefill = generate_kwargs.get("beam_cache", "copy"), bool(generate_kwargs.get("beam_prefill", False))
+    _check_cache_mode(cache, prefill)
+    return {} if cache == "copy" else dict(beam_cache=cache, beam_prefill=prefill)
+
+
 def _conditioning_bias(model, model_kwargs):
     cond = getattr(model, "cond", None)
     if cond is None or not cond.active:
@@ -482,6 +492,7 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     kv_fp8 = bool(generate_kwargs.get("cross_kv_fp8", False))
     if kv_fp8:
         require_bf16_for_cross_kv_fp8(model.dtype)
+    beam_cache = beam_cache_kwargs(generate_kwargs)              # (refused here, before anything is encoded)
     start = time.perf_counter()
     extra = {} if row_bias is None else dict(row_bias=row_bias)
     if generate_kwargs.get("self_kv_fp8", False):
@@ -491,6 +502,7 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     if getattr(sp, "num_beams", 1) > 1:
         if generate_kwargs.get("beam_sample_kernel", False):      # opt-in: beam-sample draws inside the step kernel (beam.py `device_draw`)
             extra["device_draw"] = True
+        extra.update(beam_cache)                                 # opt-in: the self-attention cache by index, the prompt prefilled
         # HF beam search (processor.py:159 `num_beams`; the timing generator uses two beams): mapperatorinator_amd/beam.py
         out = model.engine.generate_beam(audio, prompt, mask, eos, sp, sp.num_beams, negative_prompt=neg,
                                          sample_fn=generate_kwargs.get("beam_sample_fn"),

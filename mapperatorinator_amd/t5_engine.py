@@ -531,15 +531,19 @@ class T5Engine:
     def generate_beam(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids,
                       sampling: _lib.MhSampling, num_beams: int, row_bias: Optional[torch.Tensor] = None,
                       length_penalty: float = 1.0, early_stopping=False, negative_prompt: Optional[torch.Tensor] = None,
-                      sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False, device_draw: bool = False):
+                      sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False, device_draw: bool = False,
+                      beam_cache: str = "copy", beam_prefill: bool = False):
         """mel -> encoder -> cross K/V, then HF-style beam search over the step-wise decode entry (beam.py).  Returns
         dict(tokens=int64 CPU (B, n_cols), n_cols, logits=None) like `generate`.  `negative_prompt` with sampling.cfg_scale > 1:
         classifier-free guidance under beams (the doubled batch of modeling_mapperatorinator.py:243-254; beam.py).  With
         `sampling.do_sample` the continuations are drawn (beam-sample): `sample_fn(probs, k)` or torch.multinomial on the device, or
         with `device_draw=True` inside the step kernel (mh_beam_step_sample; seed sampling.seed: beam.py).
         `cross_kv_fp8`: every step streams the e4m3 copy of the cross-attention K / V (see `cross_kv_fp8()`; under guidance the copy
-        is made of the doubled rows)."""
-        from .beam import beam_search
+        is made of the doubled rows).
+        `beam_cache` "copy" | "indexed" and `beam_prefill`: beam.py `cache` / `prefill` -- the self-attention cache followed by an
+        index table instead of copied after every token, and the prompt prefilled once per chunk (needs the indexed cache)."""
+        from .beam import beam_search, _check_cache_mode
+        _check_cache_mode(beam_cache, beam_prefill)
         if cross_kv_fp8:
             require_bf16_for_cross_kv_fp8(self.dtype)
         audio = audio.to(self.device, torch.float32)
@@ -559,7 +563,8 @@ class T5Engine:
             kv = self.cross_kv(self.encode_mel(self.mel(audio), row_bias=row_bias))
         self._leave()
         out = beam_search(self, kv, prompt, prompt_mask, eos_ids, sampling, num_beams, length_penalty, early_stopping,
-                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None, device_draw=device_draw)
+                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None, device_draw=device_draw,
+                          **({} if beam_cache == "copy" else dict(cache=beam_cache, prefill=bool(beam_prefill))))
         return dict(tokens=out.cpu(), n_cols=int(out.shape[1]), logits=None)
 
     def generate(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
