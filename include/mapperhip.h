@@ -540,8 +540,10 @@ int mh_t5_generate(const MhT5Config* cfg, const MhT5Weights* w, const void* cros
  *   own their cache rows), sampling, forced ids and logits_dump.  The shadow need not be initialised and is rewritten by every call.
  * mh_quantize_kv_rows: the bulk quantiser on plain buffers -- x_bf16 [n_rows][64] bf16 -> q [n_rows][64] e4m3 bytes, scales [n_rows].
  * mh_t5_decode_self_cache: the bf16 self-attention caches [n_dec][B][H][tgt_len][64] inside a decode workspace of B rows.
- * Not built here: mh_t5_step / mh_t5_step_fp8 / mh_t5_reorder_cache (beam search) have no shadow-cache form -- they take no shadow
- *   argument and always run over the bf16 cache; the hosts refuse self_kv_fp8 with num_beams > 1. */
+ * Not built here: mh_t5_step / mh_t5_step_fp8 / mh_t5_reorder_cache (beam search over a copied cache) have no shadow-cache form --
+ *   they take no shadow argument and always run over the bf16 cache; the hosts refuse self_kv_fp8 with num_beams > 1 over the copy
+ *   cache.  Beam search over the INDEXED cache has one: mh_t5_step_indexed_skv8 and mh_t5_self_kv_fp8_fill, further down beside
+ *   mh_t5_step_indexed. */
 int64_t mh_t5_self_kv_fp8_bytes(const MhT5Config* cfg, int B);
 int mh_t5_generate_skv8(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int B,
                         const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
@@ -718,7 +720,7 @@ int mh_t5_reorder_cache(const MhT5Config* cfg, int B, const int32_t* src, int n_
  *   mh_t5_step_indexed: mh_t5_step (cross_kv_fp8 NULL) or mh_t5_step_fp8 (cross_kv_fp8 = the packed copy) whose self-attention
  *     reads cached row j < pos of decode row b from cache row origin[b][j] and writes its new row to cache row b.  Bias, masks,
  *     window and the order of every sum are those of row b: with tables kept by mh_t5_reorder_index the logits are bit-identical to
- *     mh_t5_step + mh_t5_reorder_cache.  Entries are clamped to [0, B).  No e4m3 self-cache form.
+ *     mh_t5_step + mh_t5_reorder_cache.  Entries are clamped to [0, B).  Its e4m3 self-cache form is mh_t5_step_indexed_skv8 (below).
  *   mh_t5_beam_index_init: origin[b][j] = b / kv_group for j < n_prefilled (the prompt rows of mh_t5_step_prefill), b beyond;
  *     n_prefilled = 0 is the identity table.
  *   mh_t5_reorder_index: origin_out[b][j] = origin_in[src[b]][j] for j < n_pos, b beyond -- `reorder_cache(beam_idx)` on the table;
@@ -740,6 +742,35 @@ int mh_t5_step_indexed(const MhT5Config* cfg, const MhT5Weights* w, const void* 
                        int64_t workspace_bytes, const void* origin, void* stream);
 int mh_t5_step_prefill(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, int Bp, const int32_t* prompt,
                        const uint8_t* prompt_mask, int P, int n_pos, void* workspace, int64_t workspace_bytes, int B, void* stream);
+
+/* The e4m3 self-attention cache under the index table ("self_kv_fp8" with beam_cache = "indexed"; additive at ABI 11: two symbols,
+ * no struct changes layout).  `self_kv_fp8` is the caller-owned shadow of mh_t5_self_kv_fp8_bytes(cfg, B) bytes in the layout written
+ * there (e4m3 [n_dec][2][B][H][tgt_len][64], then 256-byte aligned fp32 scales [n_dec][2][B][H][tgt_len]): 0.53 x the bf16 cache, on
+ * top of it.  Nothing is ever copied, so the shadow rows and their scales stay where their step wrote them and are read through the
+ * same table as the bf16 rows would be.  bf16 storage only, tgt_len <= 2560, B <= 64.
+ * Contract:
+ *   - mh_t5_step_indexed_skv8: mh_t5_step_indexed's arguments with the shadow between `origin` and `stream` (cross_kv_fp8 NULL or
+ *     the packed copy).  The step at `pos` of decode row b attends, for j < pos, the 64 e4m3 bytes of shadow row origin[b][j] (head,
+ *     position j) with THAT row's two scales -- the key scale multiplies the score before bias and mask, the value scale the
+ *     probability before the accumulate -- attends its own new key / value at storage precision, writes the bf16 row to bf16 cache
+ *     row b at `pos` and appends the quantised row and its scale to shadow row b at `pos`, never to an origin row: every (shadow row,
+ *     position) is written exactly once and an entry never goes stale.  Bias, prompt mask, window, RoPE and the order of every sum
+ *     are those of decode row b.  With the identity table the caches, the shadow and the logits are those of mh_t5_generate_skv8's
+ *     token steps.
+ *   - mh_t5_self_kv_fp8_fill: after mh_t5_step_prefill (n_rows = Bp, the same n_pos): positions 0 .. n_pos-1 of cache rows
+ *     0 .. n_rows-1 of the bf16 self-attention caches inside the B-row step workspace, every layer, k and v, are quantised into the
+ *     same places of the B-row shadow by the rule the step's append uses.  Nothing else of the shadow is written.  The prompt
+ *     positions attended each other through the bf16 cache, as in mh_t5_generate_skv8.
+ *   - rows stay batch-invariant: a row's logits do not depend on which rows share its call (a scale belongs to one cached row).
+ *   - mh_t5_step, mh_t5_step_fp8 and mh_t5_reorder_cache still have no shadow form; the shadow need not be initialised.
+ * Both return MH_ERR_ARG with a message naming the entry, before any launch, for a null pointer, fp32 storage, tgt_len > 2560, B
+ * outside [1, 64], rows that are not whole groups, pos / n_pos outside the cache, n_rows outside [1, B] and a workspace that is too
+ * small. */
+int mh_t5_step_indexed_skv8(const MhT5Config* cfg, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
+                            int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
+                            void* workspace, int64_t workspace_bytes, const void* origin, void* self_kv_fp8, void* stream);
+int mh_t5_self_kv_fp8_fill(const MhT5Config* cfg, int B, int n_rows, int n_pos, void* workspace, int64_t workspace_bytes,
+                           void* self_kv_fp8, void* stream);
 
 /* Teacher-forced decoder forward over whole sequences: `Mapperatorinator.forward` with `encoder_outputs` given
  * (seam B2, osuT5/osuT5/model/modeling_mapperatorinator.py:174-228; used by server.py:160-181 `model_forward`).

@@ -209,6 +209,8 @@ SYMBOLS = {
     "mh_t5_reorder_index": (I, [C.POINTER(MhT5Config), I, VP, I, VP, VP, VP]),
     "mh_t5_step_indexed": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, VP, I, I, VP, I, VP, I, VP, VP, I64, VP, VP]),
     "mh_t5_step_prefill": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, I, VP, I64, I, VP]),
+    "mh_t5_step_indexed_skv8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, VP, I, I, VP, I, VP, I, VP, VP, I64, VP, VP, VP]),
+    "mh_t5_self_kv_fp8_fill": (I, [C.POINTER(MhT5Config), I, I, I, VP, I64, VP, VP]),
     "mh_t5_forward_workspace_bytes": (I64, [C.POINTER(MhT5Config), I, I]),
     "mh_t5_decoder_forward": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP, VP, I64, VP]),
     "mh_score_rows": (I, [VP, I64, I, I, VP, VP, VP, VP, VP, VP, VP]),

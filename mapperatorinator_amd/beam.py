@@ -55,7 +55,9 @@ position.  The indexed route keeps every cache row where its step wrote it and l
 instead (`mh_t5_step_indexed`; a reorder is `mh_t5_reorder_index` from one table into the other, `beam_idx.repeat(2)` included):
 bit-identical logits, no scratch buffer.  `prefill=True` on top of it sends positions 0 .. P-2 of each chunk's prompt (all beams of a
 chunk carry the same one) through the batched prefill of mh_t5_generate once (`mh_t5_step_prefill`) and starts the table with
-origin = the chunk's row for those positions.
+origin = the chunk's row for those positions.  `self_kv_fp8=True` on top of the indexed route: the steps attend an e4m3 shadow of the
+cache (`mh_t5_step_indexed_skv8`) whose rows and scales also stay where their step wrote them and are read through the same table;
+after a prefill the prompt rows are quantised in place (`mh_t5_self_kv_fp8_fill`).  The copy route has no such form.
 """
 from __future__ import annotations
 
@@ -65,7 +67,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .t5_engine import require_bf16_for_cross_kv_fp8
+from .t5_engine import require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
 
 
 def _gather(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -227,14 +229,33 @@ def _check_cache_mode(cache, prefill):
         raise ValueError("the batched prompt prefill of the beam search (prefill / beam_prefill) needs cache='indexed'")
 
 
+def _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8):
+    """self_kv_fp8 under beams: the indexed cache and bf16 storage, else ValueError (t5_engine.require_bf16_for_self_kv_fp8)"""
+    if self_kv_fp8:
+        require_bf16_for_self_kv_fp8(engine.dtype, max(2, int(num_beams)), cache)
+
+
+def _self_kv_shadow(engine, rows, self_kv_fp8):
+    """The e4m3 shadow of the self-attention cache for the `rows` rows the decoder runs (guidance doubling included), from the
+    engine's workspace "skv8" -- the one T5Engine.decode uses; or None."""
+    if not self_kv_fp8:
+        return None
+    n = int(engine.lib.mh_t5_self_kv_fp8_bytes(C.byref(engine.packed.cfg), rows))
+    if n <= 0:
+        raise ValueError(f"the e4m3 self-attention cache does not cover {rows} rows")
+    return engine._workspace("skv8", n)
+
+
 class _IndexedCache:
     """cache="indexed": the self-attention cache rows stay where the steps wrote them; two uint8 (rows, tgt_len) tables say which
     cache row holds each (row, position) (mh_t5_step_indexed), and a reorder permutes table rows (mh_t5_reorder_index) from one
     table into the other.  `prefill` (n positions of the `groups` prompts, one mh_t5_step_prefill call) fills cache rows
-    0 .. groups-1 and starts the table with them."""
+    0 .. groups-1 and starts the table with them.
+    `skv8` (self_kv_fp8): the e4m3 shadow of the self-attention cache for `rows` rows; the steps then go through
+    mh_t5_step_indexed_skv8, which reads the shadow through the same table, and a prefill is followed by mh_t5_self_kv_fp8_fill."""
 
-    def __init__(self, lib, p, rows, kv_group, dev, stream):
-        self.lib, self.p, self.rows, self.kv_group, self.stream = lib, p, rows, kv_group, stream
+    def __init__(self, lib, p, rows, kv_group, dev, stream, skv8=None):
+        self.lib, self.p, self.rows, self.kv_group, self.stream, self.skv8 = lib, p, rows, kv_group, stream, skv8
         n = int(lib.mh_t5_beam_index_bytes(C.byref(p.cfg), rows))
         if n <= 0:
             raise ValueError(f"the index table does not cover {rows} rows")
@@ -252,9 +273,20 @@ class _IndexedCache:
                                          prompts.data_ptr(), _lib.ptr(masks), P, int(n_pos), ws.data_ptr(), ws.numel(), self.rows,
                                          self.stream)
         _lib.check(rc, "mh_t5_step_prefill")
+        if self.skv8 is not None:      # the prompt rows the prefill wrote, quantised where they are
+            rc = self.lib.mh_t5_self_kv_fp8_fill(C.byref(self.p.cfg), self.rows, prompts.shape[0], int(n_pos), ws.data_ptr(), ws.numel(),
+                                                 self.skv8.data_ptr(), self.stream)
+            _lib.check(rc, "mh_t5_self_kv_fp8_fill")
         self.init(n_pos)
 
     def step(self, cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws):
+        if self.skv8 is not None:
+            rc = self.lib.mh_t5_step_indexed_skv8(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), _lib.ptr(kv_fp8), self.rows,
+                                                  self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P, logits.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), self.tables[self.cur].data_ptr(), self.skv8.data_ptr(),
+                                                  self.stream)
+            _lib.check(rc, "mh_t5_step_indexed_skv8")
+            return
         rc = self.lib.mh_t5_step_indexed(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), _lib.ptr(kv_fp8), self.rows,
                                          self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(),
                                          ws.numel(), self.tables[self.cur].data_ptr(), self.stream)
@@ -286,13 +318,15 @@ def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P
 
 @torch.no_grad()
 def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                        kv_fp8=None, sample_keep: Optional[int] = None, cache: str = "copy", prefill: bool = False) -> torch.Tensor:
+                        kv_fp8=None, sample_keep: Optional[int] = None, cache: str = "copy", prefill: bool = False,
+                        self_kv_fp8: bool = False) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
     D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs.  With the
     types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is.
     `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep.
-    `cache` / `prefill`: see `beam_search`."""
+    `cache` / `prefill` / `self_kv_fp8`: see `beam_search`."""
     _check_cache_mode(cache, prefill)
+    _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8)
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = neg_mask = None
@@ -362,7 +396,7 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     stream = engine._s()
     scratch = idx = None
     if cache == "indexed":      # two index tables instead of the copy's scratch buffer
-        idx = _IndexedCache(lib, p, RE, nb, dev, stream)
+        idx = _IndexedCache(lib, p, RE, nb, dev, stream, skv8=_self_kv_shadow(engine, RE, self_kv_fp8))
     else:
         scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     bs = _lib.MhBeamStep()
@@ -438,7 +472,7 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
 def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor], eos_ids, sp,
                 num_beams: int, length_penalty: float = 1.0, early_stopping=False, sample_fn=None,
                 use_kernel: Optional[bool] = None, kv_fp8=None, device_draw: bool = False, cache: str = "copy",
-                prefill: bool = False) -> torch.Tensor:
+                prefill: bool = False, self_kv_fp8: bool = False) -> torch.Tensor:
     """cross_kv: the G chunks' cross K/V (engine.cross_kv); prompt int (G, P) left-padded, prompt_mask (G, P) or None.
     Under guidance (sp.cfg_scale > 1) `prompt` / `prompt_mask` carry 2G rows, [negative-prompt rows | prompt rows] (what
     T5Engine.generate and the scheduler build), and cross_kv still has G rows.
@@ -456,8 +490,13 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     reorder permutes table rows (mh_t5_reorder_index) -- the same logits bit for bit; tgt_len <= 2560.
     `prefill` (with cache="indexed" only): positions 0 .. P-2 of the prompt go through the batched prefill once per chunk
     (mh_t5_step_prefill) instead of one step per column and (chunk, beam) row.  The prefill's MFMA sums are ordered differently from
-    the token step's, as in mh_t5_generate: the same cache rows as that entry writes, not bit-identical to the token-by-token feed."""
+    the token step's, as in mh_t5_generate: the same cache rows as that entry writes, not bit-identical to the token-by-token feed.
+    `self_kv_fp8` (with cache="indexed" and bf16 storage only, else ValueError): the steps attend an e4m3 shadow of the self-attention
+    cache, one fp32 scale per cached row, through the same table (mh_t5_step_indexed_skv8); a prefill is followed by
+    mh_t5_self_kv_fp8_fill.  The shadow is the engine's workspace "skv8", 0.53 x the bf16 cache on top of it; tgt_len <= 2560, at most
+    64 rows.  Not a parity mode: the logits are those of cached K / V rounded to e4m3.  The search itself never sees the cache."""
     _check_cache_mode(cache, prefill)
+    _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8)
     if device_draw and sample_fn is not None:
         raise ValueError("device_draw draws inside the library: it cannot be combined with sample_fn")
     device_draw = bool(device_draw) and bool(sp.do_sample)
@@ -470,14 +509,15 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
                                       "beams > 8192)")
         if can_draw and use_kernel is not False:
             return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2, cache=cache, prefill=prefill)
+                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2, cache=cache, prefill=prefill,
+                                       self_kv_fp8=self_kv_fp8)
     can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(eos_ids)) and sample_fn is None
     if use_kernel is True and not can:
         raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
                                   "K = max(2, 1 + #eos) x beams > 8192)")
     if can and use_kernel is not False:
         return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                   kv_fp8=kv_fp8, cache=cache, prefill=prefill)
+                                   kv_fp8=kv_fp8, cache=cache, prefill=prefill, self_kv_fp8=self_kv_fp8)
     dev, lib, p = engine.device, engine.lib, engine.packed
     cfg = sp.cfg_scale > 1.0
     neg_prompt = None
@@ -537,7 +577,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     stream = engine._s()
     scratch = idx = None
     if cache == "indexed":      # two index tables instead of the copy's scratch buffer
-        idx = _IndexedCache(lib, p, RE, nb, dev, stream)
+        idx = _IndexedCache(lib, p, RE, nb, dev, stream, skv8=_self_kv_shadow(engine, RE, self_kv_fp8))
     else:
         scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     scale = float(sp.cfg_scale)

@@ -880,6 +880,8 @@ __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key g
 // IDX (beam search over an index table, mh_t5_step_indexed): key / value row j of this head comes from cache row origin[j] -- kbase /
 // vbase are then head h of cache row 0, `origin` the decode row's table entries in LDS and `row_stride` the elements between two
 // cache rows (H * tgt_len * 64).  An 8-lane group still reads one whole row; only the row's base differs from key to key.
+// SC with IDX (mh_t5_step_indexed_skv8): kscale_row / vscale_row are head h of shadow row 0 and key j's pair sits at
+// origin[j] * (row_stride / 64) + j -- the scales of the row that holds the key, never those of the decode row.
 template <typename T, int U, typename E = T, bool SC = false, bool IDX = false>
 __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kbase, const E* vbase, int j0,
                                    int jend, int jstride, const float* bias_row, int pos, const uint8_t* mask_row,
@@ -892,12 +894,14 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
     float s[U];
     float kv[U][8];
     float vv[U][8];
+    int org_u[U];   // (IDX) the table value of key u: its scale pair below is addressed from the same LDS read as its K / V
     if constexpr (IDX) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int jj = j + u * jstride;
         const int jc = jj < jend ? jj : j;
-        const long row = (long)origin[jc] * row_stride + (long)jc * 64 + c8;   // the cache row that holds key jc
+        org_u[u] = origin[jc];
+        const long row = (long)org_u[u] * row_stride + (long)jc * 64 + c8;   // the cache row that holds key jc
         load8_stream<E>(kbase + row, kv[u]);
         load8_stream<E>(vbase + row, vv[u]);
       }
@@ -924,8 +928,14 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int jj = j + u * jstride;
-      ksv[u] = SC ? kscale_row[jj < jend ? jj : j] : 1.f;
-      vsv[u] = SC ? vscale_row[jj < jend ? jj : j] : 1.f;
+      if constexpr (SC && IDX) {   // requested with the K / V loads above still in flight: no dependent round trip is added
+        const long si = (long)org_u[u] * (row_stride >> 6) + (jj < jend ? jj : j);
+        ksv[u] = kscale_row[si];
+        vsv[u] = vscale_row[si];
+      } else {
+        ksv[u] = SC ? kscale_row[jj < jend ? jj : j] : 1.f;
+        vsv[u] = SC ? vscale_row[jj < jend ? jj : j] : 1.f;
+      }
     }
     if (bias_row) {
 #pragma unroll
@@ -1019,6 +1029,10 @@ struct NoSelfKv8P {};
 // ... or the index table of a beam search (IDX instantiations, mh_t5_step_indexed): uint8 [B][tgt_len], entry [b][j] = the cache row
 // that holds key / value j of decode row b
 struct SelfIdxP {
+  const uint8_t* origin;
+};
+// ... or both (F8 with IDX, mh_t5_step_indexed_skv8): the shadow rows and their scales are read through the table as well
+struct SelfKv8IdxP : SelfKv8P {
   const uint8_t* origin;
 };
 constexpr int kSelfIdxMaxTgt = 2560;   // table entries of one row staged in LDS (the released tgt_seq_len)
@@ -1279,14 +1293,17 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
 // origin[b][j]; the new row is still written to cache row b at pos.  The row's table entries are requested with the first round trip
 // and staged in LDS, so that the key loop has no dependent global load in front of its K / V loads.  Everything else -- bias, masks,
 // window, the order of every sum -- is per decode row b as in the plain form: same bits as a cache whose rows were copied.
+// F8 with IDX (mh_t5_step_indexed_skv8): cached key / value j < pos is the e4m3 row of shadow row origin[b][j] with THAT row's scale
+// pair; the new row goes to bf16 cache row b and, quantised, to shadow row b at pos -- never to an origin row, so the shadow keeps
+// the table's invariant (every (row, position) written once, no entry goes stale).
 template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false, bool IDX = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))   // 16 waves = 4 per SIMD: the whole 128-register budget
 void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_, const int* pos_,
                                                                  const void* kc_, const void* vc_, int H_, int d_, SelfAttnP p,
                                                                  HeadProjP hp,   // leading scalars: preloaded kernel arguments
-                                                                 typename std::conditional<F8, SelfKv8P, typename std::conditional<IDX, SelfIdxP, NoSelfKv8P>::type>::type f8) {
+                                                                 typename std::conditional<F8, typename std::conditional<IDX, SelfKv8IdxP, SelfKv8P>::type,
+                                                                                           typename std::conditional<IDX, SelfIdxP, NoSelfKv8P>::type>::type f8) {
   static_assert(!F8 || sizeof(T) == 2, "the e4m3 shadow cache is made of bf16 rows");
-  static_assert(!(F8 && IDX), "the e4m3 shadow cache has no indexed form");
   hp.h = h_; hp.ln_w = lnw_; hp.W = W_; hp.ldh = d_; hp.ldw = d_; hp.d = d_;
   p.pos = pos_; p.kc = kc_; p.vc = vc_; p.H = H_;
   const int inner = H_ * 64;
@@ -1387,7 +1404,12 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   const float sc = WH ? p.scale : 1.0f;
   int j_first = 0;
   if (WH && p.window > 0 && pos - p.window > 0) j_first = (pos - p.window) & ~(8 * NW - 1);   // whole key iterations below the window are skipped
-  if constexpr (F8) {
+  if constexpr (F8 && IDX) {   // head h of shadow row 0 (bytes and scales); every key adds the offsets of the row that holds it
+    const long row_stride = (long)p.H * p.tgt_len * 64, hh = (long)h * p.tgt_len;
+    attend_keys<T, 2, fp8_t, true, true>(st, q, reinterpret_cast<const fp8_t*>(f8.k8) + hh * 64, reinterpret_cast<const fp8_t*>(f8.v8) + hh * 64,
+                                         j_first + wid * 8 + g, pos, 8 * NW, bias_row, pos, mask_row, p.P, sc,
+                                         (WH && p.window > 0) ? pos - p.window : 0, f8.ks + hh, f8.vs + hh, org, row_stride);
+  } else if constexpr (F8) {
     const long bh = (long)b * p.H + h;
     attend_keys<T, 2, fp8_t, true>(st, q, reinterpret_cast<const fp8_t*>(f8.k8) + bh * p.tgt_len * 64,
                                    reinterpret_cast<const fp8_t*>(f8.v8) + bh * p.tgt_len * 64, j_first + wid * 8 + g, pos, 8 * NW,

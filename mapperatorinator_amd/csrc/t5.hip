@@ -1146,14 +1146,27 @@ DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
 #define MH_SELF_LEAD_ARGS hp.h, hp.ln_w, hp.W, sa.pos, sa.kc, sa.vc, sa.H, hp.d
 #define MH_CROSS_LEAD_ARGS hp.h, hp.ln_w, hp.W, ca.k, ca.v, ca.H, ca.L, hp.d, ca.kv_B
 // f8 != NULL: the F8 instantiation over this layer's rows of the e4m3 shadow cache (bf16 storage only)
-// origin != NULL: the IDX instantiation, cached rows read through the beam search's index table (mh_t5_step_indexed; never with f8)
+// origin != NULL: the IDX instantiation, cached rows read through the beam search's index table (mh_t5_step_indexed); with f8 as well,
+// the F8 + IDX one: the shadow rows and their scales through the same table (mh_t5_step_indexed_skv8)
 template <typename T, int KC>
 int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8,
                     const uint8_t* origin = nullptr) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d && inner == sa.H * 64, "decode: dense residual rows / projection weights expected");
   const dec::NoSelfKv8P no8{};
-  if (origin) {
-    MH_REQUIRE(!f8, "decode: the e4m3 self-attention cache has no indexed form");
+  if (origin && f8) {   // both: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
+    MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
+               dec::kSelfIdxMaxTgt, sa.tgt_len);
+    if constexpr (sizeof(T) == 2) {
+      dec::SelfKv8IdxP ix8{};
+      ix8.k8 = f8->k8; ix8.v8 = f8->v8; ix8.ks = f8->ks; ix8.vs = f8->vs; ix8.origin = origin;
+      if (sa.rope && hp.ln_b)
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
+      else if (sa.rope)
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
+      else
+        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
+    } else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
+  } else if (origin) {
     MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
                dec::kSelfIdxMaxTgt, sa.tgt_len);
     const dec::SelfIdxP ix{origin};
@@ -1659,12 +1672,14 @@ extern "C" int mh_t5_quantize_cross_kv(const MhT5Config* c, const void* cross_kv
 // One wave per 64-element bf16 row (dec::quant_row64: the token step's append is the same function).  Rows are addressed as
 // (plane y, slab, position): plane y = (layer, k|v) reads src_k / src_v at layer * n_slabs * stride rows and writes plane y of q /
 // scales; within a plane, row (slab, i) for i < n_pos sits at row slab * stride + i of both.  Plain buffers: one plane, one slab.
+// plane_rows: the rows of a whole plane, n_slabs * stride when every slab is visited -- more when only the first n_slabs of a plane
+// are (mh_t5_self_kv_fp8_fill: the prompts' rows of a (chunk, beam) batch).
 __global__ __launch_bounds__(256) void self_kv_quant_rows_kernel(const bf16_t* src_k, const bf16_t* src_v, uint8_t* q, float* scales,
-                                                                long n_slabs, long n_pos, long stride) {
+                                                                long n_slabs, long n_pos, long stride, long plane_rows) {
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);   // (wave-uniform)
   if (r >= n_slabs * n_pos) return;
   const long slab = r / n_pos, i = r - slab * n_pos;
-  const long plane_rows = n_slabs * stride, y = blockIdx.y;
+  const long y = blockIdx.y;
   const bf16_t* src = ((y & 1) ? src_v : src_k) + (y >> 1) * plane_rows * 64;
   const long row = slab * stride + i;
   const float x = mh::Elem<bf16_t>::to_f32(src[row * 64 + (threadIdx.x & 63)]);
@@ -1680,7 +1695,7 @@ extern "C" int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, 
     const int64_t n = n_rows - r0 < kChunk ? n_rows - r0 : kChunk;
     const bf16_t* x = (const bf16_t*)x_bf16 + r0 * 64;
     hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n + 3) / 4), 1), dim3(256), 0, (hipStream_t)stream, x, x,
-                       (uint8_t*)q + r0 * 64, scales + r0, 1L, (long)n, (long)n);
+                       (uint8_t*)q + r0 * 64, scales + r0, 1L, (long)n, (long)n, (long)n);
     MH_TRY(check_launch("self_kv_quant_rows_kernel"));
   }
   return MH_OK;
@@ -2013,7 +2028,7 @@ static int generate_impl(const GenerateArgs& a) {
     const long n_slabs = (long)B * c->n_heads;
     hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
                        (const bf16_t*)ly.bf.self_k, (const bf16_t*)ly.bf.self_v, self8,
-                       reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)start_pos, (long)c->tgt_len);
+                       reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)start_pos, (long)c->tgt_len, n_slabs * c->tgt_len);
     MH_TRY(check_launch("self_kv_quant_rows_kernel"));
   }
   if (hipEventRecord(g_pool.fork, s) != hipSuccess) return check_launch("fork record");
@@ -2313,10 +2328,13 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
 static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, bool fp8, const void* cross_kv_fp8, int B,
                      int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
                      int64_t workspace_bytes, void* stream, const char* who,   // who: the entry the caller used (error messages)
-                     bool indexed = false, const uint8_t* origin = nullptr) {
+                     bool indexed = false, const uint8_t* origin = nullptr,
+                     bool shadow = false, void* self_kv_fp8 = nullptr) {   // shadow: mh_t5_step_indexed_skv8 (the caller's e4m3 self cache)
   MH_TRY(check_cfg(c, who));
   MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace && (origin || !indexed), "%s: null argument", who);
+  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace && (origin || !indexed) && (self_kv_fp8 || !shadow),
+             "%s: null argument", who);
+  MH_REQUIRE(!shadow || c->dtype == MH_BF16, "%s: the e4m3 self-attention cache needs bf16 storage", who);
   MH_REQUIRE(!indexed || c->tgt_len <= dec::kSelfIdxMaxTgt, "%s: the index table covers tgt_len <= %d (got %d)", who,
              dec::kSelfIdxMaxTgt, c->tgt_len);
   MH_REQUIRE(!fp8 || c->dtype == MH_BF16, "%s: the fp8 cross K/V copy needs bf16 storage", who);
@@ -2332,6 +2350,10 @@ static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cros
   k.bf = decode_layout(c, B, workspace).bf;
   k.bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
   k.origin = origin;
+  if (shadow) {   // the whole batch is one chain: the shadow's first row and its scales (chain_call's derivation at b0 = 0)
+    k.bf.self8 = (uint8_t*)self_kv_fp8;
+    k.bf.self8_scales = reinterpret_cast<float*>((uint8_t*)self_kv_fp8 + self_kv8_layout(c, B).scales_offset);
+  }
   if (fp8) { k.kv8 = cross_kv_fp8; k.kv8_scales = (const float*)((const char*)cross_kv_fp8 + cross_kv8_layout(c, k.kvB).scales_offset); }
   const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
   const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
@@ -2449,6 +2471,40 @@ extern "C" int mh_t5_step_indexed(const MhT5Config* c, const MhT5Weights* w, con
   mh::OptionScope option_scope(c ? c->options : nullptr);
   return step_impl(c, w, cross_kv, cross_kv_fp8 != nullptr, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace,
                    workspace_bytes, stream, "mh_t5_step_indexed", true, (const uint8_t*)origin);
+}
+
+// mh_t5_step_indexed over the caller's e4m3 shadow of the self-attention cache (mh_t5_self_kv_fp8_bytes(cfg, B) bytes): cached rows
+// j < pos are the e4m3 rows of shadow row origin[b][j] with that row's scales; the new row is appended to shadow row b
+extern "C" int mh_t5_step_indexed_skv8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
+                                       int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
+                                       void* workspace, int64_t workspace_bytes, const void* origin, void* self_kv_fp8, void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  return step_impl(c, w, cross_kv, cross_kv_fp8 != nullptr, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace,
+                   workspace_bytes, stream, "mh_t5_step_indexed_skv8", true, (const uint8_t*)origin, true, self_kv_fp8);
+}
+
+// positions 0 .. n_pos-1 of cache rows 0 .. n_rows-1 (what mh_t5_step_prefill wrote, n_rows = Bp) of the bf16 self-attention caches of
+// a B-row step workspace -> the B-row shadow, every layer, k and v; nothing else of the shadow is written
+extern "C" int mh_t5_self_kv_fp8_fill(const MhT5Config* c, int B, int n_rows, int n_pos, void* workspace, int64_t workspace_bytes,
+                                      void* self_kv_fp8, void* stream) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  MH_TRY(check_cfg(c, "mh_t5_self_kv_fp8_fill"));
+  MH_REQUIRE(workspace && self_kv_fp8, "mh_t5_self_kv_fp8_fill: null argument");
+  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_self_kv_fp8_fill: the e4m3 self-attention cache needs bf16 storage");
+  MH_REQUIRE(c->tgt_len <= dec::kSelfIdxMaxTgt, "mh_t5_self_kv_fp8_fill: the index table covers tgt_len <= %d (got %d)",
+             dec::kSelfIdxMaxTgt, c->tgt_len);
+  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_self_kv_fp8_fill: batch %d not in [1, 64]", B);
+  MH_REQUIRE(n_rows >= 1 && n_rows <= B, "mh_t5_self_kv_fp8_fill: %d rows not in [1, %d]", n_rows, B);
+  MH_REQUIRE(B % n_rows == 0, "mh_t5_self_kv_fp8_fill: %d rows are not whole groups over %d prompts", B, n_rows);
+  MH_REQUIRE(n_pos >= 1 && n_pos < c->tgt_len, "mh_t5_self_kv_fp8_fill: %d positions outside the cache (tgt_len %d)", n_pos, c->tgt_len);
+  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_self_kv_fp8_fill: workspace too small");
+  const DecodeLayout ly = decode_layout(c, B, workspace);
+  const long n_slabs = (long)n_rows * c->n_heads, plane_rows = (long)B * c->n_heads * c->tgt_len;
+  uint8_t* self8 = (uint8_t*)self_kv_fp8;
+  hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * n_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)ly.bf.self_k, (const bf16_t*)ly.bf.self_v, self8,
+                     reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)n_pos, (long)c->tgt_len, plane_rows);
+  return check_launch("self_kv_quant_rows_kernel");
 }
 
 // positions 0 .. n_pos-1 of Bp prompts through the batched prefill (prefill_prompt: HF's one forward over the prompt) into cache rows

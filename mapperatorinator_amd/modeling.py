@@ -412,15 +412,16 @@ class MapperatorinatorHIP:
             require_bf16_for_cross_kv_fp8(self.dtype)
         beam_cache = beam_cache_kwargs(unused)     # beam_cache / beam_prefill (beam.py): ValueError for a bad combination
         skv8 = {}
-        if unused.get("self_kv_fp8", False):     # e4m3 shadow of the self-attention cache (T5Engine.decode): bf16 storage, no beams
-            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams))
-            skv8 = dict(self_kv_fp8=True)
+        if unused.get("self_kv_fp8", False):     # e4m3 shadow of the self-attention cache (T5Engine.decode): bf16 storage; under beams
+            # only over the indexed cache, where the engine's keyword is `beam_self_kv_fp8`
+            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams), unused.get("beam_cache", "copy"))
+            skv8 = dict(self_kv_fp8=True) if num_beams == 1 else dict(beam_self_kv_fp8=True)
         if num_beams != 1:
             out = self.engine.generate_beam(audio, decoder_input_ids, decoder_attention_mask, eos, sp, int(num_beams),
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
                                             sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=kv_fp8,
                                             **(dict(device_draw=True) if unused.get("beam_sample_kernel", False) else {}),
-                                            **beam_cache,
+                                            **beam_cache, **skv8,
                                             **({} if row_bias is None else dict(row_bias=row_bias)))
             return out["tokens"].to(self.device)
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,

@@ -135,9 +135,10 @@ class SequentialWindowScheduler:
     @torch.no_grad()
     def run(self, jobs: list[SongJob]):
         eng, tok = self.engine, self.tokenizer
-        for j in jobs:   # self_kv_fp8 where it is not built (fp32 storage, beams): refused before anything is encoded
+        for j in jobs:   # self_kv_fp8 where it is not built (fp32 storage, beams over the copied cache): refused before anything is encoded
             if j.generate_kwargs.get("self_kv_fp8"):
-                require_bf16_for_self_kv_fp8(eng.dtype, int(j.generate_kwargs.get("num_beams", 1) or 1))
+                require_bf16_for_self_kv_fp8(eng.dtype, int(j.generate_kwargs.get("num_beams", 1) or 1),
+                                             j.generate_kwargs.get("beam_cache", "copy"))
         start = time.perf_counter()
         kvs = self.encode_all(jobs)
         n_waves = max(j.frames.shape[0] for j in jobs)
@@ -219,7 +220,7 @@ class SequentialWindowScheduler:
         cfg = sp.cfg_scale > 1.0
         nb = int(getattr(sp, "num_beams", 1) or 1)
         if gk.get("self_kv_fp8"):   # (a window's own generate_kwargs may switch the mode on: the same refusals)
-            require_bf16_for_self_kv_fp8(eng.dtype, nb)
+            require_bf16_for_self_kv_fp8(eng.dtype, nb, gk.get("beam_cache", "copy"))
         if len(group) * (2 if cfg else 1) * nb > 64:
             raise ValueError(f"{len(group)} windows{' x 2 (guidance)' if cfg else ''}{f' x {nb} beams' if nb > 1 else ''} exceed "
                              f"the engine's 64-row decode batch")
@@ -256,7 +257,8 @@ class SequentialWindowScheduler:
             # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search
             # makes it itself: with guidance it is a copy of the doubled rows)
             kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") and nb == 1 else None
-            # generate_kwargs["self_kv_fp8"]: the token steps attend the engine's e4m3 shadow of the self-attention cache (no beams)
+            # generate_kwargs["self_kv_fp8"]: the token steps attend the engine's e4m3 shadow of the self-attention cache (under beams
+            # the search takes it, over the indexed cache only)
             skv8 = dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {}
             if merged:   # every row under its own settings (mh_t5_generate_rows); eos_table is ignored there
                 skv8["row_sampling"] = row_sampling
@@ -273,7 +275,8 @@ class SequentialWindowScheduler:
             result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn"),
                                  kv_fp8=True if gk.get("cross_kv_fp8") else None,
                                  **(dict(device_draw=True) if gk.get("beam_sample_kernel") else {}),
-                                 **{k[5:]: v for k, v in beam_cache_kwargs(gk).items()}).to(torch.int64).cpu()
+                                 **{k[5:]: v for k, v in beam_cache_kwargs(gk).items()},
+                                 **(dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {})).to(torch.int64).cpu()
         else:
             eng.synchronize()
             n_cols = int(n_out.item())

@@ -496,9 +496,11 @@ def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     start = time.perf_counter()
     extra = {} if row_bias is None else dict(row_bias=row_bias)
     if generate_kwargs.get("self_kv_fp8", False):
-        # the token steps attend an e4m3 shadow of the self-attention cache (T5Engine.decode); bf16 storage, no beams
-        require_bf16_for_self_kv_fp8(model.dtype, int(getattr(sp, "num_beams", 1) or 1))
-        extra["self_kv_fp8"] = True
+        # the token steps attend an e4m3 shadow of the self-attention cache (T5Engine.decode); bf16 storage; under beams only with
+        # beam_cache="indexed" (beam.py `self_kv_fp8`), where the engine's keyword is `beam_self_kv_fp8`
+        n_beams = int(getattr(sp, "num_beams", 1) or 1)
+        require_bf16_for_self_kv_fp8(model.dtype, n_beams, generate_kwargs.get("beam_cache", "copy"))
+        extra["beam_self_kv_fp8" if n_beams > 1 else "self_kv_fp8"] = True
     if getattr(sp, "num_beams", 1) > 1:
         if generate_kwargs.get("beam_sample_kernel", False):      # opt-in: beam-sample draws inside the step kernel (beam.py `device_draw`)
             extra["device_draw"] = True

@@ -202,16 +202,17 @@ def require_bf16_for_cross_kv_fp8(dtype) -> None:
                          "is made of bf16 rows")
 
 
-def require_bf16_for_self_kv_fp8(dtype, num_beams: int = 1) -> None:
+def require_bf16_for_self_kv_fp8(dtype, num_beams: int = 1, beam_cache: str = "copy") -> None:
     """`self_kv_fp8` where it is not built: refused on the host, before anything is encoded.  The shadow cache is made of bf16 rows
-    (fp32 storage has no e4m3 self-attention kernel), and the step-wise entries of beam search (`mh_t5_step`, `mh_t5_step_fp8`,
-    `mh_t5_reorder_cache`) have no shadow-cache form."""
+    (fp32 storage has no e4m3 self-attention kernel), and the step-wise entries of beam search over the copied cache (`mh_t5_step`,
+    `mh_t5_step_fp8`, `mh_t5_reorder_cache`) have no shadow-cache form.  Beams over the indexed cache have one
+    (`mh_t5_step_indexed_skv8`) and pass."""
     if dtype != torch.bfloat16:
         raise ValueError(f"self_kv_fp8 needs bf16 storage (this model stores {dtype}): the e4m3 self-attention cache is made of "
                          "bf16 rows")
-    if num_beams > 1:
-        raise ValueError(f"self_kv_fp8 is not built for beam search (num_beams={num_beams}): the step-wise decode entries and the "
-                         "cache reorder have no e4m3 shadow-cache form; use num_beams=1 or drop the flag")
+    if num_beams > 1 and beam_cache != "indexed":
+        raise ValueError(f"self_kv_fp8 is not built for beam search over the copied cache (num_beams={num_beams}): mh_t5_step and the "
+                         "cache reorder have no e4m3 shadow-cache form; pass beam_cache='indexed', use num_beams=1 or drop the flag")
 
 
 def next_token_targets(ids: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -532,7 +533,7 @@ class T5Engine:
                       sampling: _lib.MhSampling, num_beams: int, row_bias: Optional[torch.Tensor] = None,
                       length_penalty: float = 1.0, early_stopping=False, negative_prompt: Optional[torch.Tensor] = None,
                       sample_fn=None, use_kernel: Optional[bool] = None, cross_kv_fp8: bool = False, device_draw: bool = False,
-                      beam_cache: str = "copy", beam_prefill: bool = False):
+                      beam_cache: str = "copy", beam_prefill: bool = False, beam_self_kv_fp8: bool = False):
         """mel -> encoder -> cross K/V, then HF-style beam search over the step-wise decode entry (beam.py).  Returns
         dict(tokens=int64 CPU (B, n_cols), n_cols, logits=None) like `generate`.  `negative_prompt` with sampling.cfg_scale > 1:
         classifier-free guidance under beams (the doubled batch of modeling_mapperatorinator.py:243-254; beam.py).  With
@@ -541,9 +542,13 @@ class T5Engine:
         `cross_kv_fp8`: every step streams the e4m3 copy of the cross-attention K / V (see `cross_kv_fp8()`; under guidance the copy
         is made of the doubled rows).
         `beam_cache` "copy" | "indexed" and `beam_prefill`: beam.py `cache` / `prefill` -- the self-attention cache followed by an
-        index table instead of copied after every token, and the prompt prefilled once per chunk (needs the indexed cache)."""
+        index table instead of copied after every token, and the prompt prefilled once per chunk (needs the indexed cache).
+        `beam_self_kv_fp8` (beam.py `self_kv_fp8`; needs the indexed cache and bf16 storage): the steps attend the e4m3 shadow of
+        the self-attention cache through the same table (`mh_t5_step_indexed_skv8`)."""
         from .beam import beam_search, _check_cache_mode
         _check_cache_mode(beam_cache, beam_prefill)
+        if beam_self_kv_fp8:
+            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams), beam_cache)
         if cross_kv_fp8:
             require_bf16_for_cross_kv_fp8(self.dtype)
         audio = audio.to(self.device, torch.float32)
@@ -564,7 +569,8 @@ class T5Engine:
         self._leave()
         out = beam_search(self, kv, prompt, prompt_mask, eos_ids, sampling, num_beams, length_penalty, early_stopping,
                           sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None, device_draw=device_draw,
-                          **({} if beam_cache == "copy" else dict(cache=beam_cache, prefill=bool(beam_prefill))))
+                          **({} if beam_cache == "copy" else dict(cache=beam_cache, prefill=bool(beam_prefill))),
+                          **(dict(self_kv_fp8=True) if beam_self_kv_fp8 else {}))
         return dict(tokens=out.cpu(), n_cols=int(out.shape[1]), logits=None)
 
     def generate(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],

@@ -6,8 +6,9 @@
 
 varwhisper-small dims, bf16, at 1 window x 2 beams and 8 windows x 4 beams.  Per position p three legs alternate in one process,
 `--rounds` times each, `--iters` tokens per timing (host clock around a stream synchronise): the plain step at p, step + cache copy of
-p + 1 positions, indexed step + table reorder.  The index table is filled with a random beam of the row's window per position -- the
-most scattered table a search can produce.  One JSON line per (shape, position): median ms per token and the min .. max span of the
+p + 1 positions, indexed step + table reorder, and indexed step + table reorder over the e4m3 self cache (`self_kv_fp8=True`:
+mh_t5_step_indexed_skv8, column `indexed_skv8_ms`; its baseline is the `indexed_ms` column of the same run).  The index table is filled
+with a random beam of the row's window per position -- the most scattered table a search can produce.  One JSON line per (shape, position): median ms per token and the min .. max span of the
 rounds, beside the bytes each reorder moves, derived from the shapes:
     copy   4 x (2 n_dec rows H 64 (p + 1) element size)   gather read + write, scatter read + write
     index  rows (p + 1) read + rows tgt_len written
@@ -72,7 +73,18 @@ def per_token(eng, kv, G, nb, positions, iters, rounds):
                                               ws.data_ptr(), ws.numel(), a.data_ptr(), s), "mh_t5_step_indexed")
             _lib.check(lib.mh_t5_reorder_index(cfg, R, src.data_ptr(), pos + 1, a.data_ptr(), b.data_ptr(), s), "mh_t5_reorder_index")
             state[0] ^= 1
-        legs = (("plain_step", plain), ("copy", copy), ("indexed", indexed))
+        # indexed step + table reorder, e4m3 self cache: the same tables, the cached rows read from a shadow (bf16 storage only)
+        sh = None
+        if eng.dtype == torch.bfloat16:
+            sh = torch.zeros(int(lib.mh_t5_self_kv_fp8_bytes(cfg, R)), dtype=torch.uint8, device=dev)
+
+        def indexed_skv8(pos, state=[0]):
+            a, b = tabs[state[0]], tabs[state[0] ^ 1]
+            _lib.check(lib.mh_t5_step_indexed_skv8(cfg, w, kv.data_ptr(), None, R, nb, ids.data_ptr(), pos, None, 1, logits.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), a.data_ptr(), sh.data_ptr(), s), "mh_t5_step_indexed_skv8")
+            _lib.check(lib.mh_t5_reorder_index(cfg, R, src.data_ptr(), pos + 1, a.data_ptr(), b.data_ptr(), s), "mh_t5_reorder_index")
+            state[0] ^= 1
+        legs = (("plain_step", plain), ("copy", copy), ("indexed", indexed)) + ((("indexed_skv8", indexed_skv8),) if sh is not None else ())
         for pos in positions:
             times = {name: [] for name, _ in legs}
             for r in range(rounds + 1):                        # round 0 warms up

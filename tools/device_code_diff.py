@@ -5,7 +5,11 @@ the set of kernel symbols.  A host-only change must leave all of them as they we
 `__hip_cuid_<hash>` symbol, which hashes the source file.  This is how "compiles to the same instructions" is checked.
 
 usage: device_code_diff.py OLD.so NEW.so      exit status 0: only __hip_cuid_* symbols differ, 1: anything else differs,
-                                              3: a tool (llvm-objcopy / -readelf, PyYAML) is missing or failed"""
+                                              3: a tool (llvm-objcopy / -readelf, PyYAML) is missing or failed
+       device_code_diff.py --kernel FRAGMENT OLD.so NEW.so
+                                              for a change that adds kernels: the function bytes of every kernel of OLD whose mangled
+                                              name contains FRAGMENT against the same kernel of NEW (0: all equal, 1: one differs or
+                                              is gone)"""
 from __future__ import annotations
 
 import hashlib
@@ -15,7 +19,7 @@ import sys
 import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from check_kernel_resources import LLVM, code_objects, kernels_of  # noqa: E402
+from check_kernel_resources import LLVM, code_objects, demangle, kernels_of  # noqa: E402
 
 SECTIONS = (".text", ".rodata", ".note")
 
@@ -37,7 +41,60 @@ def describe(elf: bytes):
     return secs, {k[".symbol"] for k in kernels_of(elf)}, {s for s in syms if s.startswith("__hip_cuid_")}
 
 
+def kernel_texts(lib_path: str, fragment: str):
+    """-> {kernel symbol: the bytes of its function in .text} for every kernel of the library whose mangled name contains `fragment`"""
+    out = {}
+    for elf in code_objects(lib_path):
+        wanted = {k[".symbol"].removesuffix(".kd") for k in kernels_of(elf) if fragment in k[".symbol"]}
+        if not wanted:
+            continue
+        with tempfile.TemporaryDirectory() as td:
+            co, sec = os.path.join(td, "a.co"), os.path.join(td, "text.bin")
+            open(co, "wb").write(elf)
+            subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.text", co, sec], check=True)
+            text = open(sec, "rb").read()
+            run = lambda *a: subprocess.run([os.path.join(LLVM, "llvm-readelf"), *a, "--wide", co], check=True, capture_output=True,
+                                            text=True).stdout
+            base = next(int(f[f.index(".text") + 2], 16) for f in (ln.replace("[", " ").replace("]", " ").split()
+                                                                    for ln in run("--sections").splitlines()) if ".text" in f)
+            for ln in run("--symbols").splitlines():
+                f = ln.split()
+                if len(f) >= 8 and f[3] == "FUNC" and f[7] in wanted:
+                    addr, size = int(f[1], 16), int(f[2], 0)
+                    out[f[7]] = text[addr - base: addr - base + size]
+    # keyed by the instantiation -- name and template arguments, without the parameter list: a dependent parameter type that is
+    # spelled differently in the new source mangles differently although every old instantiation receives the same type
+    def instantiation(nm: str) -> str:   # the demangled name up to the "(" that opens the (last, top-level) parameter list
+        end, depth = nm.rfind(")"), 0
+        for i in range(end, -1, -1):
+            depth += (nm[i] == ")") - (nm[i] == "(")
+            if depth == 0:
+                return nm[:i]
+        return nm
+    syms = sorted(out)
+    return {instantiation(nm): out[s] for s, nm in zip(syms, demangle(syms))}
+
+
+def main_kernels(old_lib: str, new_lib: str, fragment: str) -> int:
+    """--kernel FRAGMENT: a change that ADDS instantiations moves the code object as a whole; what must hold then is that every
+    kernel the old build has comes out with the same instructions (branches are pc-relative, so equal code has equal bytes)"""
+    old, new = kernel_texts(old_lib, fragment), kernel_texts(new_lib, fragment)
+    if not old:
+        raise RuntimeError(f"no kernel matching {fragment!r} in {old_lib}")
+    changed = [s for s in sorted(old) if s in new and old[s] != new[s]]
+    gone = [s for s in sorted(old) if s not in new]
+    for s in changed:
+        print(f"!! {s}: {len(old[s])} bytes {hashlib.sha1(old[s]).hexdigest()[:12]} -> {len(new[s])} bytes {hashlib.sha1(new[s]).hexdigest()[:12]}")
+    for s in gone:
+        print(f"!! removed: {s}")
+    print(f"{len(old)} kernels matching {fragment!r} in the old build: {len(old) - len(changed) - len(gone)} with identical bytes, "
+          f"{len(changed)} changed, {len(gone)} removed; {len(set(new) - set(old))} added by the new build")
+    return 1 if changed or gone else 0
+
+
 def main(argv):
+    if len(argv) == 4 and argv[0] == "--kernel":
+        return main_kernels(argv[2], argv[3], argv[1])
     if len(argv) != 2:
         print(__doc__, file=sys.stderr)
         return 3
