@@ -839,6 +839,12 @@ int mh_t5_decode_chains_cfg(const MhT5Config* cfg, int B);   /* ABI 8: ... under
  * weights struct agree byte for byte).  Counters of graphs replayed from / captured into the cache since the last reset. */
 int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset);
 int mh_wall_clock_khz(void);
+/* Test aid: the kernels' cross-lane reductions run on the VALU (DPP row exchanges and the gfx950 row / half swaps, csrc/common.hpp)
+ * instead of through the LDS crossbar; this applies each of those helpers and the shuffle form it replaced to the same input in one
+ * kernel.  in: n_waves * 64 raw 32-bit patterns, one wave per 64; out_new / out_ref: [16][n_waves * 64] -- cases 0 wave sum, 1 wave
+ * max, 2-4 sums over groups of 8 / 16 / 64 lanes, 5-7 their maxima, 8 / 9 sum / max over lanes 8, 16, 32 apart (the attention merge),
+ * 10-15 the bare exchange with lane ^ 1, 2, 4, 8, 16, 32.  The two outputs must agree bit for bit. */
+int mh_debug_lane_reduce(const uint32_t* in, int64_t n_waves, uint32_t* out_new, uint32_t* out_ref, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K7/K8/K9  osu_diffusion DiT + DDPM.  Replaces DiT.forward_with_cfg

@@ -224,6 +224,7 @@ SYMBOLS = {
     "mh_t5_decode_chains_cfg": (I, [C.POINTER(MhT5Config), I]),
     "mh_t5_step_graph_cache_stats": (I, [C.POINTER(C.c_long), C.POINTER(C.c_long), I]),
     "mh_wall_clock_khz": (I, []),
+    "mh_debug_lane_reduce": (I, [VP, I64, VP, VP, VP]),
     "mh_dit_workspace_bytes": (I64, [C.POINTER(MhDiTConfig), I, I]),
     "mh_dit_forward_cfg": (I, [C.POINTER(MhDiTConfig), C.POINTER(MhDiTWeights), VP, VP, VP, VP, F, I, I, I, I,
                                VP, VP, I64, VP]),

@@ -103,19 +103,109 @@ template <> struct Atom<float> {
   }
 };
 
+// ---- lane exchanges on the VALU ----------------------------------------------------------------
+// `__shfl_xor(v, constant, 64)` compiles here to v_xor + ds_bpermute_b32 + s_waitcnt lgkmcnt(0): a round trip through the LDS
+// crossbar per butterfly level, whose wait also drains every other LDS read in flight.  The same exchange with the partner
+// lane ^ O as DPP modifiers (O < 16: within a row of 16 lanes) or a gfx950 row / half swap (O = 16 / 32) is one or two VALU
+// instructions and no wait.
+// EXEC: a DPP / swap read from an INACTIVE lane gives 0 or a stale register where ds_bpermute gave 0 -- every use must run with
+// the partner lanes active, i.e. whole groups of 2 O lanes (wave-uniform branches are fine; all call sites in the tree do).
+constexpr int kDppQuadXor1 = 0xB1, kDppQuadXor2 = 0x4E;                        // quad_perm:[1,0,3,2] / [2,3,0,1]
+constexpr int kDppRowShl4 = 0x104, kDppRowShr4 = 0x114, kDppRowRor8 = 0x128;   // lane i reads i + 4 / i - 4 / (i + 8) % 16 of its row
+// the 32-bit value of lane ^ O, O in {1, 2, 4, 8}
+template <int O> __device__ inline uint32_t lane_xor_u32(uint32_t x) {
+  static_assert(O == 1 || O == 2 || O == 4 || O == 8, "row-local exchange");
+  const int v = (int)x;
+  if constexpr (O == 1) return (uint32_t)__builtin_amdgcn_update_dpp(v, v, kDppQuadXor1, 0xF, 0xF, true);
+  else if constexpr (O == 2) return (uint32_t)__builtin_amdgcn_update_dpp(v, v, kDppQuadXor2, 0xF, 0xF, true);
+  else if constexpr (O == 8) return (uint32_t)__builtin_amdgcn_update_dpp(v, v, kDppRowRor8, 0xF, 0xF, true);
+  else {   // banks 0 / 2 (lanes 0-3, 8-11 of the row) take i + 4, banks 1 / 3 take i - 4: every enabled lane reads inside its row
+    const int t = __builtin_amdgcn_update_dpp(v, v, kDppRowShl4, 0xF, 0x5, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp(t, v, kDppRowShr4, 0xF, 0xA, false);
+  }
+}
+// {own, partner} of lane ^ 16 / lane ^ 32 in UNSPECIFIED order (v_permlane16_swap / v_permlane32_swap of {x, x}: the lanes whose
+// bit O is clear hold {own, partner}, the others {partner, own}) -- all a commutative operation needs
+template <int O> __device__ inline void lane_swap_pair(uint32_t x, uint32_t& a, uint32_t& b) {
+  static_assert(O == 16 || O == 32, "row / half exchange");
+  if constexpr (O == 16) { auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false); a = r[0]; b = r[1]; }
+  else { auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false); a = r[0]; b = r[1]; }
+}
+// the value lane ^ O holds, any O in {1, .., 32} (the swaps pay one select for the order: lane = threadIdx.x & 63, workgroups are
+// one-dimensional everywhere here)
+template <int O> __device__ inline uint32_t lane_xor(uint32_t x) {
+  if constexpr (O >= 16) {
+    uint32_t a, b;
+    lane_swap_pair<O>(x, a, b);
+    return (threadIdx.x & O) ? a : b;
+  } else {
+    return lane_xor_u32<O>(x);
+  }
+}
+template <int O> __device__ inline float lane_xor(float v) { return __uint_as_float(lane_xor<O>(__float_as_uint(v))); }
+template <int O> __device__ inline int lane_xor(int v) { return (int)lane_xor<O>((uint32_t)v); }
+// one butterfly level: v (+) the value of lane ^ O, in every lane the bits of `v + __shfl_xor(v, O, 64)` / `fmaxf(v, __shfl_xor(..))`.
+// xor_add keeps the form `v + partner`: where v is a bare product x * y, hipcc contracts it into fma(x, y, partner) -- the UNROUNDED
+// own product plus the partner's rounded one, as it did with the shuffle -- and only that form lets it (the row / half swaps pay a
+// select for it).  xor_add_of_sum is for a v that is itself the result of an addition (every level after the first; accumulated
+// statistics): nothing to contract, a + b commutes exactly, the swap's two halves are added as they come.  fmaxf commutes exactly too.
+template <int O> __device__ inline float xor_add(float v) { return v + lane_xor<O>(v); }
+template <int O> __device__ inline float xor_add_of_sum(float v) {
+  if constexpr (O >= 16) {
+    uint32_t a, b;
+    lane_swap_pair<O>(__float_as_uint(v), a, b);
+    return __uint_as_float(a) + __uint_as_float(b);
+  } else {
+    return v + lane_xor<O>(v);
+  }
+}
+template <int O> __device__ inline float xor_max(float v) {
+  if constexpr (O >= 16) {
+    uint32_t a, b;
+    lane_swap_pair<O>(__float_as_uint(v), a, b);
+    return fmaxf(__uint_as_float(a), __uint_as_float(b));
+  } else {
+    return fmaxf(v, lane_xor<O>(v));
+  }
+}
+
 // ---- wave / block reductions -----------------------------------------------------------------
-__device__ inline float wave_sum(float v) {
+// levels from the widest partner down, as the __shfl_xor loops ran them (kept below as *_ref: the test's reference only)
+template <int G> __device__ inline float group_sum(float v) {   // over groups of G consecutive lanes (G power of two <= 64)
+  if constexpr (G > 32) v = xor_add<32>(v);                                     // (v may be a product: see xor_add)
+  if constexpr (G > 16) v = G == 32 ? xor_add<16>(v) : xor_add_of_sum<16>(v);
+  if constexpr (G > 8) v = xor_add<8>(v);
+  if constexpr (G > 4) v = xor_add<4>(v);
+  if constexpr (G > 2) v = xor_add<2>(v);
+  if constexpr (G > 1) v = xor_add<1>(v);
+  return v;
+}
+template <int G> __device__ inline float group_max(float v) {
+  if constexpr (G > 32) v = xor_max<32>(v);
+  if constexpr (G > 16) v = xor_max<16>(v);
+  if constexpr (G > 8) v = xor_max<8>(v);
+  if constexpr (G > 4) v = xor_max<4>(v);
+  if constexpr (G > 2) v = xor_max<2>(v);
+  if constexpr (G > 1) v = xor_max<1>(v);
+  return v;
+}
+__device__ inline float wave_sum(float v) { return group_sum<64>(v); }
+__device__ inline float wave_max(float v) { return group_max<64>(v); }
+// across the 8-lane groups of a wave (partners 8, 16, 32 in that order): lanes with equal lane & 7
+__device__ inline float across_groups8_sum(float v) { return xor_add_of_sum<32>(xor_add_of_sum<16>(xor_add<8>(v))); }
+__device__ inline float across_groups8_max(float v) { return xor_max<32>(xor_max<16>(xor_max<8>(v))); }
+
+__device__ inline float wave_sum_ref(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ inline float wave_max(float v) {
+__device__ inline float wave_max_ref(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-// reduce over groups of G consecutive lanes (G power of two <= 64)
-template <int G> __device__ inline float group_sum(float v) {
+template <int G> __device__ inline float group_sum_ref(float v) {
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

@@ -575,8 +575,7 @@ __device__ __forceinline__ void gemv_tile(const SkinnyP& p, const int tile, cons
         float q = 0.f;
 #pragma unroll
         for (int c = 0; c < CH; ++c) q += (kb0 + NWV * c < nkb) ? VecOps<T>::sum(hraw[c][f]) : 0.f;
-        q += __shfl_xor(q, 16, 64);
-        q += __shfl_xor(q, 32, 64);
+        q = xor_add_of_sum<32>(xor_add_of_sum<16>(q));   // the 4 lane groups, VALU row / half swaps (q is an accumulated sum)
         if (lg == 0) ssw[wid][f * 16 + l15] = q;
       }
       if (tid * 4 < p.K) { *reinterpret_cast<float4*>(lnw + tid * 4) = lnraw; *reinterpret_cast<float4*>(lnb + tid * 4) = lnbraw; }
@@ -593,8 +592,7 @@ __device__ __forceinline__ void gemv_tile(const SkinnyP& p, const int tile, cons
           hraw[c][f] = VecOps<T>::centred(hraw[c][f], mu);
           q += (kb0 + NWV * c < nkb) ? VecOps<T>::sumsq(hraw[c][f]) : 0.f;
         }
-        q += __shfl_xor(q, 16, 64);
-        q += __shfl_xor(q, 32, 64);
+        q = xor_add_of_sum<32>(xor_add_of_sum<16>(q));   // the 4 lane groups, VALU row / half swaps (q is an accumulated sum)
         if (lg == 0) ssw2[wid][f * 16 + l15] = q;
       }
       __syncthreads();
@@ -612,8 +610,7 @@ __device__ __forceinline__ void gemv_tile(const SkinnyP& p, const int tile, cons
         float q = 0.f;
 #pragma unroll
         for (int c = 0; c < CH; ++c) q += (kb0 + NWV * c < nkb) ? VecOps<T>::sumsq(hraw[c][f]) : 0.f;
-        q += __shfl_xor(q, 16, 64);
-        q += __shfl_xor(q, 32, 64);
+        q = xor_add_of_sum<32>(xor_add_of_sum<16>(q));   // the 4 lane groups, VALU row / half swaps (q is an accumulated sum)
         if (lg == 0) ssw[wid][f * 16 + l15] = q;
       }
       if (tid * 4 < p.K) *reinterpret_cast<float4*>(lnw + tid * 4) = lnraw;
@@ -671,7 +668,9 @@ __device__ __forceinline__ void gemv_tile(const SkinnyP& p, const int tile, cons
     if (EPI == SK_GELU_ERF) {
       if (ok) store_wt(reinterpret_cast<T*>(p.out) + (long)row * p.ldo + ocol, Elem<T>::from_f32(0.5f * v * (1.0f + erff(v * 0.70710678118654752f))));
     } else if (EPI == SK_GEGLU) {
-      const float lin = __shfl_down(v, 8, 16);   // the linear half of the pair sits 8 tile columns to the right
+      // the linear half of the pair sits 8 tile columns to the right: row_ror:8 (columns >= 8 get the gate back and are never
+      // stored, col_ok; whole waves reach this line -- the `unit` break above is wave-uniform)
+      const float lin = lane_xor<8>(v);
       if (ok) store_wt(reinterpret_cast<T*>(p.out) + (long)row * p.ldo + ocol, Elem<T>::from_f32(gelu_tanh(v) * lin));
     } else if (EPI == SK_LOGITS) {
       if (ok) store_wt(reinterpret_cast<float*>(p.out) + (long)row * p.ldo + ocol, v);
@@ -858,19 +857,15 @@ template <typename T>
 __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key groups of a wave
   // rescale to the wave-wide maximum first (ONE exponential per lane), then plain shuffle sums: no exponential sits in
   // the 3-level reduction chain
-  float mw = s.m;
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) mw = fmaxf(mw, __shfl_xor(mw, o, 64));
+  // (partners 8, 16, 32 on the VALU -- row_ror:8, then the row and half swaps; the whole wave calls this)
+  const float mw = across_groups8_max(s.m);
   const float f = fexp<T>(s.m - mw);
   s.l *= f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) s.acc[i] *= f;
+  s.l = across_groups8_sum(s.l);
 #pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    s.l += __shfl_xor(s.l, o, 64);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s.acc[i] += __shfl_xor(s.acc[i], o, 64);
-  }
+  for (int i = 0; i < 8; ++i) s.acc[i] = across_groups8_sum(s.acc[i]);
   s.m = mw;
 }
 
@@ -960,6 +955,7 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
       float d = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) d += q[i] * kv[u][i];
+      // (DPP partners 4, 2, 1 stay inside the 8-lane group, and the loop's trip count depends on the group alone: whole groups run)
       if (SC) d = group_sum<8>(d) * ksv[u] * scale + bv[u];
       else d = group_sum<8>(d) * scale + bv[u];
       const bool ok = (jj < jend) && (jj >= jmin) && (mv[u] != 0);
@@ -1007,9 +1003,7 @@ struct SelfAttnP {
 // and lane 0 the scale, with ordinary vector stores (the next launch reads them).
 __device__ inline void quant_row64(float x, uint8_t* q_row, float* scale_slot) {
   const int lane = threadIdx.x & 63;
-  float mx = fabsf(x);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  const float mx = wave_max(fabsf(x));
   const float scale = mx > 0.f ? mx / 448.0f : 1.0f;   // 448 = largest finite e4m3 value
   const float inv = 1.0f / scale;
   const float y = x * inv;
@@ -1171,7 +1165,9 @@ struct NormRow {
 // 128-byte lines (lane-contiguous chunks -- 96-byte strides at d = 768 -- touch 12 lines per output row and instruction;
 // the CU's load path is charged per line and lane).  The weight slice does not depend on the activations: `load` is
 // called at kernel entry, `apply` after the normalised row is in LDS.
-template <typename T, int KC, int NP>
+// FENCE: nothing is scheduled across the end of a projection (the shuffle reductions' LDS waits used to keep the projections apart;
+// without them hipcc overlaps them and the Whisper-family self-attention instantiations, at the 128-register limit, spill)
+template <typename T, int KC, int NP, bool FENCE = false>
 struct HeadProj {
   Raw8<T> raw[NP][KC];
   __device__ inline void load(const HeadProjP& hp, const int (&row0)[NP]) {
@@ -1210,6 +1206,7 @@ struct HeadProj {
       acc = group_sum<16>(acc);
       if (bias) acc += bias[row0[q] + o];
       if (ks == 0) out[q][o] = Elem<T>::to_f32(Elem<T>::from_f32(acc));
+      if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
     }
   }
 };
@@ -1345,7 +1342,7 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
   // (F8, the Whisper family at d = 896: the scale pairs of the key loop on top of the 21 weight vectors spill; one projection at a
   // time, as d = 1024 -- the same sums in the same order)
   constexpr bool kAllAtOnce = sizeof(T) == 2 && KC <= ((F8 && WH) ? 6 : 7);
-  HeadProj<T, KC, kAllAtOnce ? 3 : 1> proj;
+  HeadProj<T, KC, kAllAtOnce ? 3 : 1, WH> proj;
   const int row03[3] = {h * 64, inner + h * 64, 2 * inner + h * 64};
   const float* bias_row = WH ? nullptr : p.bias + (long)h * p.tgt_len;       // (the Whisper family has no additive bias)
   const uint8_t* mask_row = p.prompt_mask ? p.prompt_mask + (long)b * p.P : nullptr;
@@ -1365,7 +1362,7 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
 #pragma unroll
     for (int q3 = 0; q3 < 3; ++q3) {
       const int row0[1] = {q3 * inner + h * 64};
-      HeadProj<T, KC, 1> proj1;
+      HeadProj<T, KC, 1, WH> proj1;
       proj1.load(hp, row0);
       proj1.apply(xn, qkv + q3, qb, row0);
     }

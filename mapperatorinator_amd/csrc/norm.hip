@@ -133,7 +133,44 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
   }
 }
 
+// ---- test aid: the VALU lane exchanges of common.hpp against the __shfl_xor forms they replaced (mh_debug_lane_reduce) ----------
+// one wave per 64 inputs (raw bit patterns); out_new / out_ref [kLaneReduceCases][n_waves * 64].  Cases: 0 wave_sum, 1 wave_max,
+// 2-4 group_sum<8 / 16 / 64>, 5-7 group_max<8 / 16 / 64>, 8 / 9 sum / max across the 8-lane groups (partners 8, 16, 32: the
+// attention merge), 10-15 the bare exchange lane ^ 1, 2, 4, 8, 16, 32
+constexpr int kLaneReduceCases = 16;
+template <int G> __device__ inline float group_max_ref(float v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__global__ __launch_bounds__(256) void lane_reduce_debug_kernel(const uint32_t* __restrict__ in, long n_waves, uint32_t* __restrict__ out_new,
+                                                                uint32_t* __restrict__ out_ref) {
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wave >= n_waves) return;   // wave-uniform: whole waves run the exchanges
+  const long i = wave * 64 + (threadIdx.x & 63), n = n_waves * 64;
+  const uint32_t xu = in[i];
+  const float x = __uint_as_float(xu);
+  float ms = x, mm = x;          // the merge pattern as partial_merge_groups ran it
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) { ms += __shfl_xor(ms, o, 64); mm = fmaxf(mm, __shfl_xor(mm, o, 64)); }
+  const float fn[10] = {wave_sum(x), wave_max(x), group_sum<8>(x), group_sum<16>(x), group_sum<64>(x),
+                        group_max<8>(x), group_max<16>(x), group_max<64>(x), across_groups8_sum(x), across_groups8_max(x)};
+  const float fr[10] = {wave_sum_ref(x), wave_max_ref(x), group_sum_ref<8>(x), group_sum_ref<16>(x), group_sum_ref<64>(x),
+                        group_max_ref<8>(x), group_max_ref<16>(x), group_max_ref<64>(x), ms, mm};
+#pragma unroll
+  for (int c = 0; c < 10; ++c) { out_new[c * n + i] = __float_as_uint(fn[c]); out_ref[c * n + i] = __float_as_uint(fr[c]); }
+  const uint32_t un[6] = {lane_xor<1>(xu), lane_xor<2>(xu), lane_xor<4>(xu), lane_xor<8>(xu), lane_xor<16>(xu), lane_xor<32>(xu)};
+#pragma unroll
+  for (int c = 0; c < 6; ++c) { out_new[(10 + c) * n + i] = un[c]; out_ref[(10 + c) * n + i] = (uint32_t)__shfl_xor((int)xu, 1 << c, 64); }
+}
+
 }  // namespace
+
+int debug_lane_reduce(const uint32_t* in, long n_waves, uint32_t* out_new, uint32_t* out_ref, hipStream_t s) {
+  MH_REQUIRE(in && out_new && out_ref && n_waves > 0 && n_waves <= (1 << 20), "mh_debug_lane_reduce: bad arguments");
+  hipLaunchKernelGGL(lane_reduce_debug_kernel, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, s, in, n_waves, out_new, out_ref);
+  return check_launch("lane_reduce_debug_kernel");
+}
 
 int rmsnorm(const float* x, int ldx, const float* w, void* y, int ldy, int rows, int d, float eps, int out_dtype,
             hipStream_t s) {
@@ -190,4 +227,7 @@ extern "C" int mh_rmsnorm(const float* x, int ldx, const float* w, void* y, int 
 extern "C" int mh_layernorm(const float* x, int ldx, const float* w, const float* b, void* y, int ldy, int rows, int d, float eps,
                             int out_dtype, void* stream) {
   return mh::layernorm(x, ldx, w, b, y, ldy, rows, d, eps, out_dtype, (hipStream_t)stream);
+}
+extern "C" int mh_debug_lane_reduce(const uint32_t* in, int64_t n_waves, uint32_t* out_new, uint32_t* out_ref, void* stream) {
+  return mh::debug_lane_reduce(in, (long)n_waves, out_new, out_ref, (hipStream_t)stream);
 }

@@ -716,12 +716,15 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
       }
     }
     // argmax with first-index tie-break (torch.argmax semantics on ties = first maximal index)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(besti, o, 64);
-      if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+    // (lane exchanges on the VALU, common.hpp; the whole workgroup is here)
+#define MH_ARGMAX_LEVEL(O)                                                        \
+    {                                                                             \
+      const float ob = lane_xor<O>(best);                                         \
+      const int oi = lane_xor<O>(besti);                                          \
+      if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }     \
     }
+    MH_ARGMAX_LEVEL(32) MH_ARGMAX_LEVEL(16) MH_ARGMAX_LEVEL(8) MH_ARGMAX_LEVEL(4) MH_ARGMAX_LEVEL(2) MH_ARGMAX_LEVEL(1)
+#undef MH_ARGMAX_LEVEL
     __syncthreads();   // the reductions above may still be reading sf
     if (lane == 0) { sf[wid] = best; si[wid] = besti; }
     __syncthreads();
@@ -1627,8 +1630,7 @@ __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(const bf16_t* src, ui
       mx = fmaxf(mx, fabsf(__uint_as_float(w[j] & 0xffff0000u)));
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
