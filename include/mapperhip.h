@@ -140,8 +140,23 @@ int mh_mel(const float* audio, int B, int n_samples, int n_fft, int hop, int n_m
  * (modeling_mapperatorinator.py:195-196; HF T5Attention q/k/v/o, T5DenseGatedActDense;
  *  osu_diffusion/utils/models.py:111-116,145-155).  C = A[M,K] * W[N,K]^T with a fused epilogue.
  * A, W have element type `dtype`; lda/ldw/ldc in elements; K % 8 == 0 (bf16) or % 4 (f32),
- * row starts 16-byte aligned.  bias fp32[N] or NULL.  gate fp32 [.., gate_ld].
- * For MH_EPI_KV_SCATTER: kv_B, kv_H, kv_L describe the scatter (rows m = b*kv_L + key). */
+ * row starts of A and W 16-byte aligned; lda, ldw >= K (the columns [K, ld) are never read).  bias fp32[N] or NULL.
+ * gate fp32 [.., gate_ld]: MH_EPI_GATE_RESID reads gate[m / rows_per_batch], MH_EPI_BIAS_GELU_ERF (gate optional: the position
+ * table) adds gate[m % rows_per_batch].
+ * C may be ANY pointer aligned to its element (2 bytes bf16, 4 bytes fp32 and the pre-split form), ldc >= the columns written.
+ * This is a contract shown on the device, not one of the C++: the register-staged tiles store element by element, but the LDS-DMA,
+ * three-stage and MX-fp8 kernels access C in vectors whatever its alignment -- fp32 outputs (STORE_F32, RESID, GATE_RESID, the
+ * q | k block of the fp32 QKV_VT) are stored, and the old C loaded, as 16 bytes; bf16 outputs as 8 bytes, or as 16 bytes when C is
+ * 16-byte aligned, ldc % 8 == 0 and N % 16 == 0 (pre-split output: 16 bytes when C is 16-byte aligned, ldc % 32 == 0 and
+ * N % 32 == 0, else 8) -- and rely on gfx950 serving unaligned global accesses.
+ * Only the documented positions are written: rows >= M and columns >= N (>= N / 2 for MH_EPI_GEGLU) of C, the V^T pad columns
+ * [kv_L, kv_Lpad) of MH_EPI_QKV_VT / MH_EPI_QKV_CACHE and the cache positions [kv_L, cache_len) of MH_EPI_QKV_CACHE are left
+ * untouched (tests/test_gpu_gemm.py runs every kernel and epilogue with sentinels around each output, C also at an 8-byte and at a
+ * one-element offset).
+ * For MH_EPI_KV_SCATTER: kv_B, kv_H, kv_L describe the scatter (rows m = b*kv_L + key) into [(layer, kv)][b][h][key][64].
+ * MH_EPI_QKV_VT: columns < n_split to C; the rest, kv_H heads of v, transposed per head to C2 [b][h][64][kv_Lpad].
+ * MH_EPI_QKV_CACHE (N = 3 * kv_H * 64, n_split = kv_H * 64): q to C; k to C2 and v to C3 as [b][h][cache_len][64] at position
+ * i = m % kv_L; v also transposed to C4 [b][h][64][kv_Lpad]. */
 typedef struct MhGemm {
   const void* A; int lda;
   const void* W; int ldw;
@@ -185,6 +200,23 @@ typedef struct MhGemm {
   uint8_t* mx_out; uint8_t* mx_out_scales;
 } MhGemm;
 int mh_gemm(const MhGemm* g, void* stream);
+/* Test-facing (additive at ABI 11: one symbol and one enum; a library without it is an older 11): the kernel the calling thread's
+ * last mh_gemm launch ran, as family * 1024 + tile rows (host-only bookkeeping, no device work; MH_GEMM_NONE before the first
+ * launch).  Together with dtype and epilogue, which the caller knows, that names one compiled kernel: e.g. MH_GEMM_TN * 1024 + 16
+ * is the 16 x 16 split-K tile, MH_GEMM_GLDS3 * 1024 + 128 the 128-row form of the three-stage kernel (tests/test_gpu_gemm.py). */
+typedef enum MhGemmKernel {
+  MH_GEMM_NONE = 0,
+  MH_GEMM_TN = 1,        /* register-staged tile: 128, 64, 32 or 16 (split-K) rows                   */
+  MH_GEMM_TN_S3 = 2,     /* ... its bf16 x 3 form (w_split3 = 1): 64 rows                             */
+  MH_GEMM_TN_GLDS = 3,   /* ... its LDS-DMA form (bf16): 128 rows                                     */
+  MH_GEMM_GLDS3 = 4,     /* three-stage LDS-DMA kernel (bf16): 256 x 128 or 128 x 128 tile            */
+  MH_GEMM_GLDS2S = 5,    /* two-stage short-K kernel (bf16): 128 x 128                                */
+  MH_GEMM_GLDS4 = 6,     /* two-stage 256 x 256 kernel (bf16)                                         */
+  MH_GEMM_S3G = 7,       /* three-stage bf16 x 3 kernel, A pre-split (w_split3 & 2): 128 rows         */
+  MH_GEMM_MX8 = 8,       /* MX-fp8 operands: 128 or 256 rows                                          */
+  MH_GEMM_MX8_MXO = 9    /* ... with the MX-fp8 image as output (mx_out)                              */
+} MhGemmKernel;
+int mh_gemm_last_kernel(void);
 
 /* MX-fp8 quantisation of a row-major matrix (the A / W operands of mh_gemm with dtype = MH_MX8).
  * x [rows][ldx] of in_dtype (MH_F32 / MH_BF16), K % 128 == 0 columns used.  Per (row, block of 32 consecutive k):

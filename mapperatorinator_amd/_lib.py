@@ -148,6 +148,9 @@ class MhAttnProblem(C.Structure):
 (ATTN_NONE, ATTN_FLASH_F32, ATTN_FLASH_BF16, ATTN_SMALL_K2, ATTN_SMALL_K4) = range(5)
 ATTN_FLASH2, ATTN_FLASH2_BIAS, ATTN_FLASH2_SIMPLE = 8, 1, 2
 
+# mh_gemm_last_kernel (MhGemmKernel): family * 1024 + tile rows
+(GEMM_NONE, GEMM_TN, GEMM_TN_S3, GEMM_TN_GLDS, GEMM_GLDS3, GEMM_GLDS2S, GEMM_GLDS4, GEMM_S3G, GEMM_MX8, GEMM_MX8_MXO) = range(10)
+
 ABI_VERSION = 11  # MH_ABI_VERSION of include/mapperhip.h
 
 # every symbol include/mapperhip.h declares: (name, restype, argtypes)
@@ -165,6 +168,7 @@ SYMBOLS = {
     "mh_options_get": (C.c_long, [VP, C.c_char_p]),
     "mh_mel": (I, [VP, I, I, I, I, I, VP, VP, VP, VP, VP, VP, I, VP, I, I, VP]),
     "mh_gemm": (I, [C.POINTER(MhGemm), VP]),
+    "mh_gemm_last_kernel": (I, []),
     "mh_rmsnorm": (I, [VP, I, VP, VP, I, I, I, F, I, VP]),
     "mh_layernorm": (I, [VP, I, VP, VP, VP, I, I, I, F, I, VP]),
     "mh_mx8_scale_row_bytes": (I64, [I]),

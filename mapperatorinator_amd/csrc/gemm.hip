@@ -1746,6 +1746,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_mx8_kernel(GemmP p) {
   g3_epilogue<EPI, MI, MXO>(p, acc, m0, n0, wr, wc, lane);
 }
 
+// which member of tile_kernels / mx8_kernels the calling thread's last GEMM launch was (mh_gemm_last_kernel: host-only, for tests)
+thread_local int tl_last_gemm_kernel = MH_GEMM_NONE;
+
 // ---- host side: ONE description per kernel family -----------------------------------------------------------------------------
 // Tile rows / columns, threads, dynamic LDS bytes, grid rule and the kernel itself.  Both the launch and the attribute set-up of
 // gemm_prepare() are generated from it (KernelList below), so a family's LDS size is written once.
@@ -1758,30 +1761,35 @@ struct Tn : GridPerTile {
   static constexpr int kLds = 2 * (BM + BN) * (RowBytes<BM>::v + 16) + BM * 8 + 2048;   // two padded stages + LayerNorm statistics
   static constexpr auto kernel() { return &gemm_tn_kernel<T, BM, BN, EPI, S3, GL>; }
   static constexpr const char* kName = "gemm_tn_kernel";
+  static constexpr int kFamily = S3 ? MH_GEMM_TN_S3 : GL ? MH_GEMM_TN_GLDS : MH_GEMM_TN;
 };
 template <int EPI, int MI>
 struct Glds3 : GridPerTile {
   static constexpr int BM = 64 * MI, BN = 128, kThreads = 512, kLds = 3 * dma_stage_bytes(BM, BN);
   static constexpr auto kernel() { return &gemm_glds3_kernel<EPI, MI>; }
   static constexpr const char* kName = "gemm_glds3_kernel";
+  static constexpr int kFamily = MH_GEMM_GLDS3;
 };
 template <int EPI>
 struct Glds2s : GridPerTile {
   static constexpr int BM = 128, BN = 128, kThreads = 512, kLds = 2 * dma_stage_bytes(BM, BN);
   static constexpr auto kernel() { return &gemm_glds2s_kernel<EPI>; }
   static constexpr const char* kName = "gemm_glds2s_kernel";
+  static constexpr int kFamily = MH_GEMM_GLDS2S;
 };
 template <int EPI>
 struct Glds4 : GridPerTile {
   static constexpr int BM = 256, BN = 256, kThreads = 512, kLds = 2 * dma_stage_bytes(BM, BN);
   static constexpr auto kernel() { return &gemm_glds4_kernel<EPI>; }
   static constexpr const char* kName = "gemm_glds4_kernel";
+  static constexpr int kFamily = MH_GEMM_GLDS4;
 };
 template <int EPI, int MI>
 struct S3g {
   static constexpr int BM = 64 * MI, BN = 128, kThreads = 512, kLds = 3 * dma_stage_bytes(BM, BN);
   static constexpr auto kernel() { return &gemm_s3g_kernel<EPI, MI>; }
   static constexpr const char* kName = "gemm_s3g_kernel";
+  static constexpr int kFamily = MH_GEMM_S3G;
   static int grid(int tiles) { return tiles < 256 ? tiles : 256; }   // persistent: one workgroup per CU walks the work list
 };
 template <int EPI, int MI, int NW, bool MXO = false>
@@ -1789,6 +1797,7 @@ struct Mx8 : GridPerTile {
   static constexpr int BM = 16 * MI * (NW / 2), BN = 128, kThreads = NW * 64, kLds = 3 * dma_stage_bytes(BM, BN);
   static constexpr auto kernel() { return &gemm_mx8_kernel<EPI, MI, NW, MXO>; }
   static constexpr const char* kName = "gemm_mx8_kernel";
+  static constexpr int kFamily = MXO ? MH_GEMM_MX8_MXO : MH_GEMM_MX8;
 };
 
 // The kernels of one (operand class, epilogue).  A kernel is launched THROUGH its list, and gemm_prepare() walks the same lists:
@@ -1803,6 +1812,7 @@ struct KernelList {
   static int launch(Q, const GemmP& p, hipStream_t s) {
     static_assert((... || std::is_same<Q, K>::value), "kernel is not in the list that gemm_prepare() walks");
     const int tiles = ((p.M + Q::BM - 1) / Q::BM) * ((p.N + Q::BN - 1) / Q::BN);
+    tl_last_gemm_kernel = Q::kFamily * 1024 + Q::BM;
     hipLaunchKernelGGL(Q::kernel(), dim3(Q::grid(tiles)), dim3(Q::kThreads), Q::kLds, s, p);
     return check_launch(Q::kName);
   }
@@ -2007,7 +2017,6 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
     MH_REQUIRE(g.C2 && g.C3 && g.C4 && g.kv_H > 0 && g.kv_L > 0 && g.kv_Lpad >= g.kv_L && g.cache_len >= g.kv_L &&
                    g.n_split == g.kv_H * 64 && g.N == 3 * g.kv_H * 64 && g.M % g.kv_L == 0,
                "mh_gemm: bad QKV_CACHE geometry");
-  { int rc = gemm_prepare(); if (rc != MH_OK) return rc; }
   const GemmP p = make_params(g, es, ascending_k);
   if (mx) {
     if (g.mx_out) {
@@ -2016,6 +2025,7 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
       MH_REQUIRE(g.mx_out_scales && width % 128 == 0 && g.ldc >= width && ((uintptr_t)g.mx_out % 4) == 0,
                  "mh_gemm: mx_out needs mx_out_scales, an output width that is a multiple of 128 and ldc >= width (width=%d ldc=%d)", width, g.ldc);
     }
+    { int rc = gemm_prepare(); if (rc != MH_OK) return rc; }
     return dispatch_mx8_epi(p, g.epilogue, s);
   }
   if (g.stats_out)
@@ -2038,11 +2048,15 @@ int gemm(const MhGemm& g, hipStream_t s, bool ascending_k, int plan_M) {
   // workgroups, the cause was never isolated in the ISA, and a later unrelated edit of this file brought the failure back.  A path
   // nothing uses and nobody can vouch for is refused, not shipped.
   MH_REQUIRE(!(g.ln_stats && g.w_split3), "mh_gemm: the fused LayerNorm-modulate prologue is not available with w_split3 (run mh_ln_modulate first)");
+  // (every argument check above comes before the first call that needs a device)
+  { int rc = gemm_prepare(); if (rc != MH_OK) return rc; }
   if (g.dtype == MH_BF16) return dispatch_epi<bf16_t>(p, g.epilogue, s, plan_M);
   return dispatch_epi<float>(p, g.epilogue, s, plan_M);
 }
 
 }  // namespace mh
+
+extern "C" int mh_gemm_last_kernel(void) { return mh::tl_last_gemm_kernel; }
 
 extern "C" int mh_gemm(const MhGemm* g, void* stream) {
   if (!g) { mh::set_error("mh_gemm: null descriptor"); return MH_ERR_ARG; }

@@ -33,6 +33,9 @@ def split3_pack(W):
     return torch.stack([hi.reshape(n, k // 32, 32), lo.reshape(n, k // 32, 32)], dim=2).reshape(n, 2 * k).contiguous()
 
 
+VT_SENTINEL = -768.0      # exact in bf16 and fp32: what the V^T buffer of MH_EPI_QKV_VT holds before the launch
+
+
 def run_gemm(A, W, epi, dtype, bias=None, C0=None, gate=None, rows_per_batch=0, kv=None, n_split=0, Lpad=0, out_cols=None,
              split3=False):
     L, lib = _lib()
@@ -68,7 +71,7 @@ def run_gemm(A, W, epi, dtype, bias=None, C0=None, gate=None, rows_per_batch=0, 
     elif epi == L.EPI_QKV_VT:
         B_, H_, L_ = kv
         out = torch.zeros((M, n_split), dtype=td, device=dev)
-        vt = torch.zeros((B_, H_, 64, Lpad), dtype=td, device=dev); keep.append(vt)
+        vt = torch.full((B_, H_, 64, Lpad), VT_SENTINEL, dtype=td, device=dev); keep.append(vt)   # pad columns must be left untouched
         g.C, g.ldc, g.C2, g.n_split, g.kv_B, g.kv_H, g.kv_L, g.kv_Lpad = out.data_ptr(), n_split, vt.data_ptr(), n_split, B_, H_, L_, Lpad
     L.check(lib.mh_gemm(C.byref(g), _stream()), "mh_gemm")
     torch.cuda.synchronize()
@@ -340,7 +343,7 @@ def test_gemm_kv_scatter_and_qkv_vt(dtype_name):
     assert torch.allclose(qk, full[:, :2 * H_ * 64], atol=tol, rtol=1e-2)
     v = full[:, 2 * H_ * 64:].view(B_, L_, H_, 64).permute(0, 2, 3, 1)   # [B,H,64,L]
     assert torch.allclose(vt[..., :L_], v, atol=tol, rtol=1e-2)
-    assert (vt[..., L_:] == 0).all()
+    assert (vt[..., L_:] == VT_SENTINEL).all()              # the pad columns [kv_L, kv_Lpad) were not written
 
 
 @pytest.mark.parametrize("dtype_name", ["f32", "bf16"])
