@@ -7,7 +7,7 @@ vectorised `GenerationMixin._beam_search` -- transformers >= 4.50; line referenc
 `generation/utils.py`): per step
 
     log_probs = processors(sequences, log_softmax(logits))            (b: processors act on LOG-PROBABILITIES here)
-    accumulated = log_probs + running_beam_scores                      -> top K = max(2, 1 + #eos) * num_beams continuations
+    accumulated = log_probs + running_beam_scores                      -> top K continuations (`_n_candidates`)
     candidates that hit an EOS id / max_length leave the running set   (e), the next `num_beams` others keep running
     finished hypotheses among the TOP num_beams candidates are merged into the finished set by score / length ** penalty   (f)
     the cache rows follow the surviving beams                           (g)
@@ -19,7 +19,10 @@ logits out -- `mh_t5_step_fp8` when the search is handed the e4m3 copy of the cr
 selection, finished-set merge, the early-stopping heuristic; 2 .. 8 beams, K <= 8192, any vocabulary: the scores live in LDS where
 they fit 120 KB, else a streaming kernel recomputes them from the logits, same bits) -- `_beam_search_kernel` below; the host reads three flags per chunk and step.  The torch-op
 form (`beam_search` with use_kernel=False; ~40 ATen launches per token) stays for beam-SAMPLE as HF draws it (torch.multinomial / an
-injected sampler: the default), and as the cross-check of the kernel (tests run both against the reference goldens).  The logits processors of
+injected sampler: the default), and as the cross-check of the kernel (tests run both against the reference goldens).  The two forms
+differ only in how continuations are ranked: `beam_search` builds one `_BeamDecoder` -- guidance doubling, row counts and refusals,
+K, the prompt rows, the buffers, the prompt feed, `step` / `reorder` over the cache route (`_CopiedCache` or `_IndexedCache`, one
+surface), the returned slice -- and hands it to `_beam_search_kernel` or `_beam_search_torch_ops`.  The logits processors of
 server.py:106-134 are applied here with torch ops (the in-kernel sampler of the greedy / sampling path selects per row and
 cannot rank across beams): classifier-free guidance, MonotonicTimeShift, TimeshiftBias, (Conditional)Temperature and the lookback
 warper, both branches.  Its types_first branch (logit_processors.py:116-133) keeps `last_scores` from call to call and indexes them by
@@ -61,6 +64,7 @@ after a prefill the prompt rows are quantised in place (`mh_t5_self_kv_fp8_fill`
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -158,12 +162,26 @@ class BeamProcessors:
         return scores
 
 
+def _n_candidates(num_beams: int, vocab_out: int, n_eos: int) -> int:
+    """K, the continuations HF ranks per chunk and step (`_get_top_k_continuations`): num_beams of them keep running even when every
+    EOS id took a place among them; never more than there are (beam, id) pairs."""
+    return min(max(2, 1 + n_eos) * num_beams, num_beams * vocab_out)
+
+
+_KERNEL_LIMITS = "beams outside 2 .. 8 or K = max(2, 1 + #eos) x beams > 8192"      # (the refusals' words for _n_candidates)
+
+
+def _min_tokens_to_keep(n_eos: int) -> int:
+    """what HF hands its top-k / top-p warpers under beams (utils.py `_get_logits_processor`)"""
+    return n_eos + 1 if n_eos else 2
+
+
 def kernel_path_available(sp, num_beams: int, vocab_out: int, n_eos: int) -> bool:
     """mh_beam_step / mh_beam_step_tf cover greedy beams (no beam-sample: `do_sample` decides before anything else is read), 2 .. 8
     beams, K <= 8192 candidates and any vocabulary: the library says which of its two kernels a shape runs (mh_beam_step_path; 0 =
     refused)."""
-    K = min(max(2, 1 + n_eos) * num_beams, num_beams * vocab_out)
-    return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), int(K)) != 0
+    K = _n_candidates(int(num_beams), int(vocab_out), n_eos)
+    return (not sp.do_sample) and _lib.load().mh_beam_step_path(int(num_beams), int(vocab_out), K) != 0
 
 
 _GOLDEN = 0x9E3779B97F4A7C15
@@ -222,17 +240,13 @@ def _step_kv_fp8(engine, cross_kv: torch.Tensor, kv_fp8):
     return kv_fp8
 
 
-def _check_cache_mode(cache, prefill):
+def check_cache_mode(cache, prefill):
+    """`cache` / `prefill` of `beam_search`, else ValueError: the hosts above it (server, T5Engine.generate_beam) refuse with it before
+    they encode anything"""
     if cache not in ("copy", "indexed"):
         raise ValueError(f"beam cache {cache!r}: expected 'copy' or 'indexed'")
     if prefill and cache != "indexed":
         raise ValueError("the batched prompt prefill of the beam search (prefill / beam_prefill) needs cache='indexed'")
-
-
-def _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8):
-    """self_kv_fp8 under beams: the indexed cache and bf16 storage, else ValueError (t5_engine.require_bf16_for_self_kv_fp8)"""
-    if self_kv_fp8:
-        require_bf16_for_self_kv_fp8(engine.dtype, max(2, int(num_beams)), cache)
 
 
 def _self_kv_shadow(engine, rows, self_kv_fp8):
@@ -249,47 +263,46 @@ def _self_kv_shadow(engine, rows, self_kv_fp8):
 class _IndexedCache:
     """cache="indexed": the self-attention cache rows stay where the steps wrote them; two uint8 (rows, tgt_len) tables say which
     cache row holds each (row, position) (mh_t5_step_indexed), and a reorder permutes table rows (mh_t5_reorder_index) from one
-    table into the other.  `prefill` (n positions of the `groups` prompts, one mh_t5_step_prefill call) fills cache rows
-    0 .. groups-1 and starts the table with them.
+    table into the other.  `start` with n_pos > 0 (the prompt prefill: n_pos positions of the `groups` prompts, one mh_t5_step_prefill
+    call) fills cache rows 0 .. groups-1 and starts the table with them.
     `skv8` (self_kv_fp8): the e4m3 shadow of the self-attention cache for `rows` rows; the steps then go through
     mh_t5_step_indexed_skv8, which reads the shadow through the same table, and a prefill is followed by mh_t5_self_kv_fp8_fill."""
 
-    def __init__(self, lib, p, rows, kv_group, dev, stream, skv8=None):
-        self.lib, self.p, self.rows, self.kv_group, self.stream, self.skv8 = lib, p, rows, kv_group, stream, skv8
+    def __init__(self, lib, p, rows, kv_group, ws, stream, skv8=None):
+        self.lib, self.p, self.rows, self.kv_group, self.ws, self.stream, self.skv8 = lib, p, rows, kv_group, ws, stream, skv8
         n = int(lib.mh_t5_beam_index_bytes(C.byref(p.cfg), rows))
         if n <= 0:
             raise ValueError(f"the index table does not cover {rows} rows")
-        self.tables = [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.tables = [torch.empty(n, dtype=torch.uint8, device=ws.device) for _ in range(2)]
         self.cur = 0
 
-    def init(self, n_prefilled: int):
-        _lib.check(self.lib.mh_t5_beam_index_init(C.byref(self.p.cfg), self.rows, self.kv_group, int(n_prefilled),
-                                                  self.tables[self.cur].data_ptr(), self.stream), "mh_t5_beam_index_init")
+    def start(self, cross_kv, prompts, masks, n_pos):
+        """Before the first token step.  n_pos > 0: positions 0 .. n_pos-1 of every prompt are prefilled -- prompts int32 (groups, P)
+        on the device, masks uint8 (groups, P) or None"""
+        cfg, ws = C.byref(self.p.cfg), self.ws
+        if n_pos:
+            G, P = prompts.shape
+            rc = self.lib.mh_t5_step_prefill(cfg, C.byref(self.p.w), cross_kv.data_ptr(), G, prompts.data_ptr(), _lib.ptr(masks), P,
+                                             int(n_pos), ws.data_ptr(), ws.numel(), self.rows, self.stream)
+            _lib.check(rc, "mh_t5_step_prefill")
+            if self.skv8 is not None:      # the prompt rows the prefill wrote, quantised where they are
+                rc = self.lib.mh_t5_self_kv_fp8_fill(cfg, self.rows, G, int(n_pos), ws.data_ptr(), ws.numel(), self.skv8.data_ptr(),
+                                                     self.stream)
+                _lib.check(rc, "mh_t5_self_kv_fp8_fill")
+        rc = self.lib.mh_t5_beam_index_init(cfg, self.rows, self.kv_group, int(n_pos), self.tables[self.cur].data_ptr(), self.stream)
+        _lib.check(rc, "mh_t5_beam_index_init")
 
-    def prefill(self, cross_kv, prompts, masks, n_pos, ws):
-        """prompts int32 (groups, P) on the device, masks uint8 (groups, P) or None: positions 0 .. n_pos-1 of every prompt"""
-        P = prompts.shape[1]
-        rc = self.lib.mh_t5_step_prefill(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), prompts.shape[0],
-                                         prompts.data_ptr(), _lib.ptr(masks), P, int(n_pos), ws.data_ptr(), ws.numel(), self.rows,
-                                         self.stream)
-        _lib.check(rc, "mh_t5_step_prefill")
-        if self.skv8 is not None:      # the prompt rows the prefill wrote, quantised where they are
-            rc = self.lib.mh_t5_self_kv_fp8_fill(C.byref(self.p.cfg), self.rows, prompts.shape[0], int(n_pos), ws.data_ptr(), ws.numel(),
-                                                 self.skv8.data_ptr(), self.stream)
-            _lib.check(rc, "mh_t5_self_kv_fp8_fill")
-        self.init(n_pos)
-
-    def step(self, cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws):
+    def step(self, cross_kv, kv_fp8, tokens, pos, mask, P, logits):
+        ws, table = self.ws, self.tables[self.cur]
         if self.skv8 is not None:
             rc = self.lib.mh_t5_step_indexed_skv8(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), _lib.ptr(kv_fp8), self.rows,
                                                   self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P, logits.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), self.tables[self.cur].data_ptr(), self.skv8.data_ptr(),
-                                                  self.stream)
+                                                  ws.data_ptr(), ws.numel(), table.data_ptr(), self.skv8.data_ptr(), self.stream)
             _lib.check(rc, "mh_t5_step_indexed_skv8")
             return
         rc = self.lib.mh_t5_step_indexed(C.byref(self.p.cfg), C.byref(self.p.w), cross_kv.data_ptr(), _lib.ptr(kv_fp8), self.rows,
                                          self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), self.tables[self.cur].data_ptr(), self.stream)
+                                         ws.numel(), table.data_ptr(), self.stream)
         _lib.check(rc, "mh_t5_step_indexed")
 
     def reorder(self, src, n_pos):
@@ -299,62 +312,132 @@ class _IndexedCache:
         self.cur ^= 1
 
 
-def _prefill_prompts(ids0e, mask, nb):
-    """the (group) prompts of the (group, beam) rows the engine is fed: every nb-th row (all beams of a group carry the same prompt)"""
-    return ids0e[::nb].to(torch.int32).contiguous(), None if mask is None else mask[::nb].contiguous()
+class _CopiedCache:
+    """cache="copy", HF's route: after every token cache row b <- row src[b] over the positions so far (mh_t5_reorder_cache: a gather
+    into a scratch buffer and a scatter back).  The steps are mh_t5_step, or mh_t5_step_fp8 over the e4m3 copy of the cross K/V when
+    there is one.  No prefill and no e4m3 self cache (`check_cache_mode`, require_bf16_for_self_kv_fp8)."""
+
+    def __init__(self, lib, p, rows, kv_group, ws, stream, max_length):
+        self.lib, self.p, self.rows, self.kv_group, self.ws, self.stream = lib, p, rows, kv_group, ws, stream
+        n = int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), rows, max_length))
+        self.scratch = torch.empty(n, dtype=torch.uint8, device=ws.device)
+
+    def start(self, cross_kv, prompts, masks, n_pos):
+        assert n_pos == 0      # every prompt column is a token step
+
+    def step(self, cross_kv, kv_fp8, tokens, pos, mask, P, logits):
+        lib, cfg, w, ws = self.lib, C.byref(self.p.cfg), C.byref(self.p.w), self.ws
+        if kv_fp8 is None:
+            rc = lib.mh_t5_step(cfg, w, cross_kv.data_ptr(), self.rows, self.kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P,
+                                logits.data_ptr(), ws.data_ptr(), ws.numel(), self.stream)
+            _lib.check(rc, "mh_t5_step")
+        else:
+            rc = lib.mh_t5_step_fp8(cfg, w, cross_kv.data_ptr(), kv_fp8.data_ptr(), self.rows, self.kv_group, tokens.data_ptr(), pos,
+                                    _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(), ws.numel(), self.stream)
+            _lib.check(rc, "mh_t5_step_fp8")
+
+    def reorder(self, src, n_pos):
+        rc = self.lib.mh_t5_reorder_cache(C.byref(self.p.cfg), self.rows, src.data_ptr(), int(n_pos), self.ws.data_ptr(), self.ws.numel(),
+                                          self.scratch.data_ptr(), self.scratch.numel(), self.stream)
+        _lib.check(rc, "mh_t5_reorder_cache")
 
 
-def _decoder_step(lib, p, cross_kv, kv_fp8, rows, kv_group, tokens, pos, mask, P, logits, ws, stream):
-    """One decoder position for all (chunk, beam) rows: mh_t5_step, or mh_t5_step_fp8 over the e4m3 copy when there is one."""
-    if kv_fp8 is None:
-        rc = lib.mh_t5_step(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), rows, kv_group, tokens.data_ptr(), pos, _lib.ptr(mask), P,
-                            logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(rc, "mh_t5_step")
-    else:
-        rc = lib.mh_t5_step_fp8(C.byref(p.cfg), C.byref(p.w), cross_kv.data_ptr(), kv_fp8.data_ptr(), rows, kv_group, tokens.data_ptr(),
-                                pos, _lib.ptr(mask), P, logits.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-        _lib.check(rc, "mh_t5_step_fp8")
+class _BeamDecoder:
+    """The decoder side of a beam search, shared by its two bookkeeping forms, which differ only in how they rank continuations.
+    Built once per `beam_search` call: the row counts (G chunks x nb beams = R rows the bookkeeping ranks, RE rows the engine
+    decodes: 2 R under guidance, the negative prompt's rows in front), the refusals, K / `fill` / `n_new` / `min_tokens_to_keep`,
+    and the prompt rows as the engine is fed them (`ids0e` int32 (RE, P), `mask` uint8 (RE, P) or None).  Inside `running()` there
+    are also the buffers -- the cross K/V as the steps read it (doubled under guidance; its e4m3 copy `kv_fp8`), the workspace that
+    holds the caches, `logits` fp32 (RE, V), `stream` -- and the cache route (`_CopiedCache` / `_IndexedCache`) behind
+    `feed_prompt` / `step` / `reorder`; a call that is refused before it runs allocates none of them."""
+
+    def __init__(self, engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, kv_fp8, cache, prefill, self_kv_fp8):
+        self.engine, self.cross_kv, self.kv_fp8 = engine, cross_kv, kv_fp8
+        self.indexed, self.prefill, self.self_kv_fp8 = cache == "indexed", bool(prefill), self_kv_fp8
+        dev, p = engine.device, engine.packed
+        self.guided = sp.cfg_scale > 1.0
+        if self.guided and prompt.shape[0] % 2:
+            raise ValueError("guidance: the prompt batch must be [negative rows | prompt rows]")
+        self.G, self.P = prompt.shape[0] // (2 if self.guided else 1), prompt.shape[1]
+        self.nb = nb = int(num_beams)
+        self.R = self.G * nb
+        self.RE = 2 * self.R if self.guided else self.R
+        if self.RE > 64:
+            raise ValueError(f"{self.G} chunks x {nb} beams{' x 2 (guidance)' if self.guided else ''} exceed the engine's 64-row decode batch")
+        self.V = p.vocab_out
+        self.max_length = int(sp.max_length)
+        if not (1 <= self.P < self.max_length <= p.tgt_len):
+            raise ValueError("prompt / max_length do not fit the cache")
+        self.eos = [int(e) for e in eos_ids]
+        self.K = _n_candidates(nb, self.V, len(self.eos))
+        self.min_tokens_to_keep = _min_tokens_to_keep(len(self.eos))
+        self.fill = int(sp.pad_id) or (self.eos[0] if self.eos else -1)       # HF: `pad_token_id or eos_token_id[0]`
+        self.n_new = self.max_length - self.P
+        # rows (chunk, beam); under guidance the negative rows come first, as `prompt` / `prompt_mask` carry them
+        self.ids0e = prompt.to(dev, torch.int32).repeat_interleave(nb, 0)
+        self.mask = None if prompt_mask is None else prompt_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0).contiguous()
+
+    @contextlib.contextmanager
+    def running(self):
+        """Makes the buffers and the cache route; inside, the engine's stream is current, behind everything enqueued before."""
+        e = self.engine
+        lib, p, dev, RE = e.lib, e.packed, e.device, self.RE
+        if self.guided:      # [layer][k|v][chunk][H][L][64]: the negative rows read their chunk's K / V
+            self.cross_kv = torch.cat([self.cross_kv, self.cross_kv], dim=2)
+        self.kv_fp8 = _step_kv_fp8(e, self.cross_kv, self.kv_fp8)
+        ws = torch.empty(int(lib.mh_t5_decode_workspace_bytes(C.byref(p.cfg), RE)), dtype=torch.uint8, device=dev)
+        self.logits = torch.empty((RE, self.V), dtype=torch.float32, device=dev)
+        self.stream = e._s()
+        if self.indexed:     # two index tables instead of the copy's scratch buffer
+            self.cache = _IndexedCache(lib, p, RE, self.nb, ws, self.stream, skv8=_self_kv_shadow(e, RE, self.self_kv_fp8))
+        else:
+            self.cache = _CopiedCache(lib, p, RE, self.nb, ws, self.stream, self.max_length)
+        e._enter()
+        with torch.cuda.stream(e.stream):
+            yield
+        e._leave()
+        e.synchronize()
+
+    def feed_prompt(self):
+        """Prompt columns 0 .. P-2 into the caches (column P-1 is the search's first step): with `prefill` in one batched pass, once
+        per chunk (all beams of a chunk carry the same prompt: every nb-th row), else token by token."""
+        n = self.P - 1 if self.prefill else 0
+        prompts = masks = None
+        if n:
+            prompts = self.ids0e[::self.nb].contiguous()
+            masks = None if self.mask is None else self.mask[::self.nb].contiguous()
+        self.cache.start(self.cross_kv, prompts, masks, n)
+        for pos in range(n, self.P - 1):
+            self.step(self.ids0e[:, pos].contiguous(), pos)
+
+    def step(self, tokens: torch.Tensor, pos: int):
+        """One decoder position for all RE rows -> `logits`.  tokens (RE,): int32 as they are, int64 converted."""
+        if tokens.dtype != torch.int32:
+            tokens = tokens.to(torch.int32).contiguous()
+        self.cache.step(self.cross_kv, self.kv_fp8, tokens, pos, self.mask, self.P, self.logits)
+
+    def reorder(self, src: torch.Tensor, cur_len: int):
+        """The caches follow the beams: row b continues row src[b] (int32 (RE,)) over positions 0 .. cur_len-1."""
+        self.cache.reorder(src, cur_len)
+
+    def finish(self, sequences: torch.Tensor, beam_bidx: torch.Tensor) -> torch.Tensor:
+        """sequences (G, nb, max_length), beam_bidx (G, nb, n_new; -1 = not generated) of the finished set -> the best hypothesis
+        per chunk, int64 (G, P + the longest generated length)"""
+        best = sequences[:, 0, :].to(torch.int64)
+        n_gen = int(((beam_bidx[:, 0, :] + 1).bool()).sum(dim=1).max())
+        return best[:, :self.P + n_gen].clone()
 
 
 @torch.no_grad()
-def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                        kv_fp8=None, sample_keep: Optional[int] = None, cache: str = "copy", prefill: bool = False,
-                        self_kv_fp8: bool = False) -> torch.Tensor:
+def _beam_search_kernel(dec: _BeamDecoder, sp, length_penalty, early_stopping, sample_keep: Optional[int] = None) -> torch.Tensor:
     """`beam_search` with the per-token bookkeeping in mh_beam_step: per token mh_t5_step -> mh_beam_step -> mh_t5_reorder_cache and ONE
     D2H copy of 3 G flags (HF's loop condition); the hypotheses live in int32 device arrays that the kernel ping-pongs.  With the
     types_first lookback the step is mh_beam_step_tf over `lookback_prev`, one fp32 per row slot that stays where it is.
-    `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep.
-    `cache` / `prefill` / `self_kv_fp8`: see `beam_search`."""
-    _check_cache_mode(cache, prefill)
-    _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8)
-    dev, lib, p = engine.device, engine.lib, engine.packed
-    cfg = sp.cfg_scale > 1.0
-    neg_prompt = neg_mask = None
-    if cfg:
-        if prompt.shape[0] % 2:
-            raise ValueError("guidance: the prompt batch must be [negative rows | prompt rows]")
-        half = prompt.shape[0] // 2
-        neg_prompt, prompt = prompt[:half], prompt[half:]
-        neg_mask = None if prompt_mask is None else prompt_mask[:half]
-        prompt_mask = None if prompt_mask is None else prompt_mask[half:]
-        cross_kv = torch.cat([cross_kv, cross_kv], dim=2)
-    kv_fp8 = _step_kv_fp8(engine, cross_kv, kv_fp8)
-    G, P = prompt.shape
-    nb = int(num_beams)
-    R = G * nb
-    RE = 2 * R if cfg else R
-    if RE > 64:
-        raise ValueError(f"{G} chunks x {nb} beams{' x 2 (guidance)' if cfg else ''} exceed the engine's 64-row decode batch")
-    V = p.vocab_out
-    max_length = int(sp.max_length)
-    if not (1 <= P < max_length <= p.tgt_len):
-        raise ValueError("prompt / max_length do not fit the cache")
-    eos_list = [int(e) for e in eos_ids]
-    K = min(max(2, 1 + len(eos_list)) * nb, nb * V)
-    fill = int(sp.pad_id) or (eos_list[0] if eos_list else -1)
-    n_new = max_length - P
+    `sample_keep` (beam-sample with the draw in the kernel): the step is mh_beam_step_sample with min_tokens_to_keep = sample_keep."""
+    dev, lib = dec.engine.device, dec.engine.lib
+    G, nb, R, RE, V, P, max_length, n_new = dec.G, dec.nb, dec.R, dec.RE, dec.V, dec.P, dec.max_length, dec.n_new
     eos_table = torch.zeros(V, dtype=torch.uint8, device=dev)
-    good = [e for e in eos_list if 0 <= e < V]
+    good = [e for e in dec.eos if 0 <= e < V]
     if good:
         eos_table[torch.tensor(good, dtype=torch.long, device=dev)] = 1
     types_first = bool(sp.lookback_types_first) and sp.lookback_mask_end > sp.ts_start
@@ -367,17 +450,10 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
                          "server.build_sampling)")
     # LookbackBiasLogitsWarper types_first: prob_eos of what entered the processor one step earlier, per row SLOT; < 0 = no call yet
     lookback_prev = torch.full((R,), -1.0, dtype=torch.float32, device=dev) if types_first else None
-    ids0 = prompt.to(dev, torch.int32).repeat_interleave(nb, 0)
-    mask = None if prompt_mask is None else prompt_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0).contiguous()
-    ids0e = ids0
-    if cfg:
-        ids0e = torch.cat([neg_prompt.to(dev, torch.int32).repeat_interleave(nb, 0), ids0], 0)
-        if mask is not None:
-            mask = torch.cat([neg_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0), mask], 0).contiguous()
 
     def state():
-        run = torch.full((G, nb, max_length), fill, dtype=torch.int32, device=dev)
-        run[:, :, :P] = ids0.view(G, nb, P)
+        run = torch.full((G, nb, max_length), dec.fill, dtype=torch.int32, device=dev)
+        run[:, :, :P] = dec.ids0e[-R:].view(G, nb, P)
         rs = torch.zeros((G, nb), dtype=torch.float32, device=dev)
         rs[:, 1:] = -1e9
         return dict(run=run, rs=rs, rb=torch.full((G, nb, n_new), -1, dtype=torch.int32, device=dev), seq=run.clone(),
@@ -390,46 +466,22 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
     feed = torch.zeros(RE, dtype=torch.int32, device=dev)      # ... and the token every row is fed next
     flags = torch.zeros((G, 3), dtype=torch.int32, device=dev)
     flags_host = torch.zeros((G, 3), dtype=torch.int32).pin_memory()
-    need = lib.mh_t5_decode_workspace_bytes(C.byref(p.cfg), RE)
-    ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
-    logits = torch.empty((RE, V), dtype=torch.float32, device=dev)
-    stream = engine._s()
-    scratch = idx = None
-    if cache == "indexed":      # two index tables instead of the copy's scratch buffer
-        idx = _IndexedCache(lib, p, RE, nb, dev, stream, skv8=_self_kv_shadow(engine, RE, self_kv_fp8))
-    else:
-        scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     bs = _lib.MhBeamStep()
-    bs.logits, bs.eos_table = logits.data_ptr(), eos_table.data_ptr()
-    bs.G, bs.num_beams, bs.V, bs.P, bs.max_length, bs.K = G, nb, V, P, max_length, K
-    bs.cfg, bs.cfg_scale, bs.length_penalty = int(cfg), float(sp.cfg_scale), float(length_penalty)
+    bs.eos_table = eos_table.data_ptr()
+    bs.G, bs.num_beams, bs.V, bs.P, bs.max_length, bs.K = G, nb, V, P, max_length, dec.K
+    bs.cfg, bs.cfg_scale, bs.length_penalty = int(dec.guided), float(sp.cfg_scale), float(length_penalty)
     bs.early_stopping = 2 if early_stopping == "never" else (1 if early_stopping is True else 0)
     bs.sp = sp                                       # (a copy: the caller's struct keeps its tok_flags)
     if flags_d is not None:
         bs.sp.tok_flags = flags_d.data_ptr()
     bs.heuristic_open, bs.src, bs.last, bs.flags = heuristic_open.data_ptr(), src.data_ptr(), feed.data_ptr(), flags.data_ptr()
-
-    def step(tokens: torch.Tensor, pos: int):
-        if idx is not None:
-            idx.step(cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws)
-        else:
-            _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
-
-    engine._enter()
-    with torch.cuda.stream(engine.stream):
-        first_pos = 0
-        if idx is not None:
-            if prefill and P > 1:      # the prompts' positions 0 .. P-2 in one batched pass, once per group
-                idx.prefill(cross_kv, *_prefill_prompts(ids0e, mask, nb), P - 1, ws)
-                first_pos = P - 1
-            else:
-                idx.init(0)
-        for pos in range(first_pos, P - 1):
-            step(ids0e[:, pos].contiguous(), pos)
-        feed.copy_(ids0e[:, P - 1])                    # the last prompt column (under guidance the first half has the negative prompt's)
+    with dec.running():
+        bs.logits, stream = dec.logits.data_ptr(), dec.stream
+        dec.feed_prompt()
+        feed.copy_(dec.ids0e[:, P - 1])                # the last prompt column (under guidance the first half has the negative prompt's)
         cur_len, par = P, 0
         while True:
-            step(feed, cur_len - 1)
+            dec.step(feed, cur_len - 1)
             a, b = st[par], st[par ^ 1]
             bs.cur_len = cur_len
             bs.run_in, bs.rs_in, bs.rb_in = a["run"].data_ptr(), a["rs"].data_ptr(), a["rb"].data_ptr()
@@ -446,25 +498,15 @@ def _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_
             par ^= 1
             # (`src` / `feed` were written by the kernel for all RE rows: under guidance `beam_idx.repeat(2)`, cache_utils.py:18, and the
             # beam's token for both halves)
-            if idx is not None:
-                idx.reorder(src, cur_len)
-            else:
-                rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(),
-                                             scratch.data_ptr(), scratch.numel(), stream)
-                _lib.check(rc, "mh_t5_reorder_cache")
+            dec.reorder(src, cur_len)
             cur_len += 1
             flags_host.copy_(flags, non_blocking=True)
-            engine.stream.synchronize()
+            dec.engine.stream.synchronize()
             f = flags_host.numpy()
             go_on = bool(f[:, 0].any()) and not (bool(f[:, 2].all()) and early_stopping is True) and not bool(f[:, 1].all())
             if not go_on:
                 break
-        fin = st[par]
-        best = fin["seq"][:, 0, :].to(torch.int64)
-        n_gen = int(((fin["bb"][:, 0, :] + 1).bool()).sum(dim=1).max())
-        out = best[:, :P + n_gen].clone()
-    engine._leave()
-    engine.synchronize()
+        out = dec.finish(st[par]["seq"], st[par]["bb"])
     return out
 
 
@@ -495,120 +537,60 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
     cache, one fp32 scale per cached row, through the same table (mh_t5_step_indexed_skv8); a prefill is followed by
     mh_t5_self_kv_fp8_fill.  The shadow is the engine's workspace "skv8", 0.53 x the bf16 cache on top of it; tgt_len <= 2560, at most
     64 rows.  Not a parity mode: the logits are those of cached K / V rounded to e4m3.  The search itself never sees the cache."""
-    _check_cache_mode(cache, prefill)
-    _check_self_kv_fp8(engine, num_beams, cache, self_kv_fp8)
+    check_cache_mode(cache, prefill)
+    if self_kv_fp8:
+        require_bf16_for_self_kv_fp8(engine.dtype, max(2, int(num_beams)), cache)
     if device_draw and sample_fn is not None:
         raise ValueError("device_draw draws inside the library: it cannot be combined with sample_fn")
     device_draw = bool(device_draw) and bool(sp.do_sample)
-    eos_ids = list(eos_ids)
+    dec = _BeamDecoder(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, kv_fp8, cache, prefill, self_kv_fp8)
     if device_draw:
-        nb_, V_ = int(num_beams), engine.packed.vocab_out
-        can_draw = _lib.load().mh_beam_step_path(nb_, V_, min(max(2, 1 + len(eos_ids)) * nb_, nb_ * V_)) != 0
+        can_draw = _lib.load().mh_beam_step_path(dec.nb, dec.V, dec.K) != 0
         if use_kernel is True and not can_draw:
-            raise NotImplementedError("mh_beam_step_sample does not cover this call (beams outside 2 .. 8 or K = max(2, 1 + #eos) x "
-                                      "beams > 8192)")
+            raise NotImplementedError(f"mh_beam_step_sample does not cover this call ({_KERNEL_LIMITS})")
         if can_draw and use_kernel is not False:
-            return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                       kv_fp8=kv_fp8, sample_keep=len(eos_ids) + 1 if eos_ids else 2, cache=cache, prefill=prefill,
-                                       self_kv_fp8=self_kv_fp8)
-    can = kernel_path_available(sp, int(num_beams), engine.packed.vocab_out, len(eos_ids)) and sample_fn is None
+            return _beam_search_kernel(dec, sp, length_penalty, early_stopping, sample_keep=dec.min_tokens_to_keep)
+    can = kernel_path_available(sp, dec.nb, dec.V, len(dec.eos)) and sample_fn is None
     if use_kernel is True and not can:
-        raise NotImplementedError("mh_beam_step does not cover this call (beam-sample, an injected sampler, beams outside 2 .. 8 or "
-                                  "K = max(2, 1 + #eos) x beams > 8192)")
+        raise NotImplementedError(f"mh_beam_step does not cover this call (beam-sample, an injected sampler, {_KERNEL_LIMITS})")
     if can and use_kernel is not False:
-        return _beam_search_kernel(engine, cross_kv, prompt, prompt_mask, eos_ids, sp, num_beams, length_penalty, early_stopping,
-                                   kv_fp8=kv_fp8, cache=cache, prefill=prefill, self_kv_fp8=self_kv_fp8)
-    dev, lib, p = engine.device, engine.lib, engine.packed
-    cfg = sp.cfg_scale > 1.0
-    neg_prompt = None
-    if cfg:
-        if prompt.shape[0] % 2:
-            raise ValueError("guidance: the prompt batch must be [negative rows | prompt rows]")
-        half = prompt.shape[0] // 2
-        neg_prompt, prompt = prompt[:half], prompt[half:]
-        neg_mask = None if prompt_mask is None else prompt_mask[:half]
-        prompt_mask = None if prompt_mask is None else prompt_mask[half:]
-        cross_kv = torch.cat([cross_kv, cross_kv], dim=2)          # [layer][k|v][chunk][H][L][64]: the negative rows read their chunk's K / V
-    kv_fp8 = _step_kv_fp8(engine, cross_kv, kv_fp8)
-    G, P = prompt.shape
-    nb = int(num_beams)
-    R = G * nb                                                     # rows the beam bookkeeping ranks
-    RE = 2 * R if cfg else R                                       # rows the engine decodes
-    if RE > 64:
-        raise ValueError(f"{G} chunks x {nb} beams{' x 2 (guidance)' if cfg else ''} exceed the engine's 64-row decode batch")
-    V = p.vocab_out
-    max_length = int(sp.max_length)
-    if not (1 <= P < max_length <= p.tgt_len):
-        raise ValueError("prompt / max_length do not fit the cache")
-    eos_list = [int(e) for e in eos_ids]
-    procs = BeamProcessors(sp, dev, min_tokens_to_keep=len(eos_list) + 1 if eos_list else 2)
+        return _beam_search_kernel(dec, sp, length_penalty, early_stopping)
+    return _beam_search_torch_ops(dec, sp, length_penalty, early_stopping, sample_fn, device_draw)
+
+
+def _beam_search_torch_ops(dec: _BeamDecoder, sp, length_penalty, early_stopping, sample_fn, device_draw: bool) -> torch.Tensor:
+    """`beam_search` with HF's bookkeeping restated in torch ops (module docstring, steps b .. g): beam-sample as HF draws it, and the
+    cross-check of `_beam_search_kernel`."""
+    dev = dec.engine.device
+    G, nb, R, V, P, max_length, K, cfg = dec.G, dec.nb, dec.R, dec.V, dec.P, dec.max_length, dec.K, dec.guided
+    procs = BeamProcessors(sp, dev, min_tokens_to_keep=dec.min_tokens_to_keep)
     do_sample = bool(sp.do_sample)
     if do_sample and sample_fn is None and not device_draw:
         sample_fn = torch.multinomial
-    eos_t = torch.tensor(sorted(set(eos_list)), dtype=torch.long, device=dev)
-    n_eos = len(eos_list)
-    K = max(2, 1 + n_eos) * nb
-    K = min(K, nb * V)
+    eos_t = torch.tensor(sorted(set(dec.eos)), dtype=torch.long, device=dev)
     top_mask = torch.zeros(K, dtype=torch.bool, device=dev)
     top_mask[:nb] = True
-    fill = int(sp.pad_id) or (eos_list[0] if eos_list else -1)
-    ids0 = prompt.to(dev, torch.int64).repeat_interleave(nb, 0)                       # (R, P): rows (chunk, beam)
-    mask = None if prompt_mask is None else prompt_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0).contiguous()
-    ids0e = ids0                                                                      # what the engine is fed over the prompt columns
-    if cfg:
-        ids0e = torch.cat([neg_prompt.to(dev, torch.int64).repeat_interleave(nb, 0), ids0], 0)
-        if mask is not None:
-            mask = torch.cat([neg_mask.to(dev).to(torch.uint8).repeat_interleave(nb, 0), mask], 0).contiguous()
-    running = torch.full((G, nb, max_length), fill, dtype=torch.int64, device=dev)
-    running[:, :, :P] = ids0.view(G, nb, P)
+    running = torch.full((G, nb, max_length), dec.fill, dtype=torch.int64, device=dev)
+    running[:, :, :P] = dec.ids0e[-R:].view(G, nb, P)
     sequences = running.clone()
     running_scores = torch.zeros((G, nb), dtype=torch.float32, device=dev)
     running_scores[:, 1:] = -1e9
     beam_scores = torch.full((G, nb), -1e9, dtype=torch.float32, device=dev)
     finished = torch.zeros((G, nb), dtype=torch.bool, device=dev)
     heuristic_open = torch.ones((G, 1), dtype=torch.bool, device=dev)
-    n_new = max_length - P
-    running_bidx = torch.full((G, nb, n_new), -1, dtype=torch.int32, device=dev)
+    running_bidx = torch.full((G, nb, dec.n_new), -1, dtype=torch.int32, device=dev)
     beam_bidx = running_bidx.clone()
-
-    need = lib.mh_t5_decode_workspace_bytes(C.byref(p.cfg), RE)
-    ws = torch.empty(int(need), dtype=torch.uint8, device=dev)                        # owned by this call: holds the caches
-    logits = torch.empty((RE, V), dtype=torch.float32, device=dev)
-    stream = engine._s()
-    scratch = idx = None
-    if cache == "indexed":      # two index tables instead of the copy's scratch buffer
-        idx = _IndexedCache(lib, p, RE, nb, dev, stream, skv8=_self_kv_shadow(engine, RE, self_kv_fp8))
-    else:
-        scratch = torch.empty(int(lib.mh_t5_reorder_cache_scratch_bytes(C.byref(p.cfg), RE, max_length)), dtype=torch.uint8, device=dev)
     scale = float(sp.cfg_scale)
-
-    def step(tokens: torch.Tensor, pos: int):
-        tokens = tokens.to(torch.int32).contiguous()
-        if idx is not None:
-            idx.step(cross_kv, kv_fp8, tokens, pos, mask, P, logits, ws)
-        else:
-            _decoder_step(lib, p, cross_kv, kv_fp8, RE, nb, tokens, pos, mask, P, logits, ws, stream)
-
-    engine._enter()
-    with torch.cuda.stream(engine.stream):
-        first_pos = 0
-        if idx is not None:
-            if prefill and P > 1:      # the prompts' positions 0 .. P-2 in one batched pass, once per group
-                idx.prefill(cross_kv, *_prefill_prompts(ids0e, mask, nb), P - 1, ws)
-                first_pos = P - 1
-            else:
-                idx.init(0)
-        for pos in range(first_pos, P - 1):                                           # the prompt, token by token
-            step(ids0e[:, pos], pos)
+    with dec.running():
+        dec.feed_prompt()
         cur_len = P
-        first = True
         while True:
             flat = running[:, :, :cur_len].reshape(R, cur_len)
             last = flat[:, cur_len - 1]
             if cfg:      # both halves are fed the beam's last token; over the prompt columns the first half has the negative prompt's
-                last = torch.cat([last if cur_len > P else ids0e[:R, P - 1], last], 0)
-            step(last, cur_len - 1)
-            lsm = torch.log_softmax(logits, dim=-1)
+                last = torch.cat([last if cur_len > P else dec.ids0e[:R, P - 1], last], 0)
+            dec.step(last, cur_len - 1)
+            lsm = torch.log_softmax(dec.logits, dim=-1)
             if cfg:      # HF's processor, first in the list: `cond, uncond = scores.split(R); uncond + (cond - uncond) * scale`
                 lsm = lsm[R:] + (lsm[:R] - lsm[R:]) * scale
             log_probs = procs(flat, lsm)
@@ -649,12 +631,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
             src = running_bidx[..., cur_len - P].reshape(R).to(torch.int32).contiguous()
             if cfg:      # `beam_idx.repeat(2)` (cache_utils.py:18): BOTH halves take their rows from the first half
                 src = torch.cat([src, src], 0).contiguous()
-            if idx is not None:
-                idx.reorder(src, cur_len)
-            else:
-                rc = lib.mh_t5_reorder_cache(C.byref(p.cfg), RE, src.data_ptr(), cur_len, ws.data_ptr(), ws.numel(), scratch.data_ptr(),
-                                             scratch.numel(), stream)
-                _lib.check(rc, "mh_t5_reorder_cache")
+            dec.reorder(src, cur_len)
             cur_len += 1
             if early_stopping == "never" and length_penalty > 0.0:
                 hyp_len = max_length - P
@@ -664,12 +641,7 @@ def beam_search(engine, cross_kv: torch.Tensor, prompt: torch.Tensor, prompt_mas
             worst_fin = torch.where(finished, torch.min(beam_scores, dim=1, keepdim=True)[0], -1.0e9)
             heuristic_open = heuristic_open & torch.any(best_running > worst_fin, dim=-1, keepdim=True)
             go_on = torch.any(heuristic_open) & ~(torch.all(finished) & (early_stopping is True)) & ~torch.all(hits)
-            first = False
             if not bool(go_on):
                 break
-        best = sequences[:, 0, :]
-        n_gen = int(((beam_bidx[:, 0, :] + 1).bool()).sum(dim=1).max())
-        out = best[:, :P + n_gen].clone()
-    engine._leave()
-    engine.synchronize()
+        out = dec.finish(sequences, beam_bidx)
     return out

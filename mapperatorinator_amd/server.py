@@ -413,9 +413,9 @@ def beam_cache_kwargs(generate_kwargs: dict) -> dict:
     """generate_kwargs["beam_cache"] ("copy", the default, or "indexed") and ["beam_prefill"] as the keyword arguments of
     T5Engine.generate_beam; nothing when both are at their defaults.  An unknown value, or the prefill without the indexed cache,
     is a ValueError (beam.py)."""
-    from .beam import _check_cache_mode
+    from .beam import check_cache_mode
     cache, prefill = generate_kwargs.get("beam_cache", "copy"), bool(generate_kwargs.get("beam_prefill", False))
-    _check_cache_mode(cache, prefill)
+    check_cache_mode(cache, prefill)
     return {} if cache == "copy" else dict(beam_cache=cache, beam_prefill=prefill)
 
 

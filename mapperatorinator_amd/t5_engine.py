@@ -545,8 +545,8 @@ class T5Engine:
         index table instead of copied after every token, and the prompt prefilled once per chunk (needs the indexed cache).
         `beam_self_kv_fp8` (beam.py `self_kv_fp8`; needs the indexed cache and bf16 storage): the steps attend the e4m3 shadow of
         the self-attention cache through the same table (`mh_t5_step_indexed_skv8`)."""
-        from .beam import beam_search, _check_cache_mode
-        _check_cache_mode(beam_cache, beam_prefill)
+        from .beam import beam_search, check_cache_mode
+        check_cache_mode(beam_cache, beam_prefill)
         if beam_self_kv_fp8:
             require_bf16_for_self_kv_fp8(self.dtype, int(num_beams), beam_cache)
         if cross_kv_fp8:
