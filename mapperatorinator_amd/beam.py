@@ -61,6 +61,9 @@ chunk carry the same one) through the batched prefill of mh_t5_generate once (`m
 origin = the chunk's row for those positions.  `self_kv_fp8=True` on top of the indexed route: the steps attend an e4m3 shadow of the
 cache (`mh_t5_step_indexed_skv8`) whose rows and scales also stay where their step wrote them and are read through the same table;
 after a prefill the prompt rows are quantised in place (`mh_t5_self_kv_fp8_fill`).  The copy route has no such form.
+
+How the generate kwargs of the hosts above (`beam_cache`, `beam_prefill`, `beam_sample_kernel`, the two fp8 switches) become this
+module's keywords, and where they are refused: decode_modes.py.
 """
 from __future__ import annotations
 
@@ -71,7 +74,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .t5_engine import require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
+from .decode_modes import check_cache_mode, require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8  # noqa: F401
 
 
 def _gather(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -238,15 +241,6 @@ def _step_kv_fp8(engine, cross_kv: torch.Tensor, kv_fp8):
             kv_fp8 = engine.cross_kv_fp8(cross_kv.contiguous())
         engine._leave()
     return kv_fp8
-
-
-def check_cache_mode(cache, prefill):
-    """`cache` / `prefill` of `beam_search`, else ValueError: the hosts above it (server, T5Engine.generate_beam) refuse with it before
-    they encode anything"""
-    if cache not in ("copy", "indexed"):
-        raise ValueError(f"beam cache {cache!r}: expected 'copy' or 'indexed'")
-    if prefill and cache != "indexed":
-        raise ValueError("the batched prompt prefill of the beam search (prefill / beam_prefill) needs cache='indexed'")
 
 
 def _self_kv_shadow(engine, rows, self_kv_fp8):

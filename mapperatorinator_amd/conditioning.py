@@ -37,6 +37,7 @@ def _mlp(x, sd, prefix):
 
 class ConditioningEmbedders:
     """Built from the wrapper's state_dict; which embedders exist is read off the keys present."""
+    INPUTS = ("beatmap_idx", "difficulty", "mapper_idx", "song_position")      # the keyword arguments of `vectors`
 
     def __init__(self, state_dict: dict, n_mels: int, max_difficulty: float = 10.0):
         sd = {k: v.detach().to(torch.float32).cpu() for k, v in state_dict.items()
@@ -103,6 +104,11 @@ class ConditioningEmbedders:
         if out.shape[1] != self.cond_size:
             raise ValueError(f"conditioning vectors have {out.shape[1]} columns, encoder_embedder expects {self.cond_size}")
         return out
+
+    def encoder_bias(self, cond: torch.Tensor, storage_dtype: torch.dtype) -> torch.Tensor:
+        """What the engines take as `row_bias=`: conv1 `channels()` with project_encoder_input = false ('Tiger14n/ropewhisper-*'),
+        else the `row_bias()` of the encoder input projection."""
+        return self.channels(cond, storage_dtype) if self.as_channels else self.row_bias(cond, storage_dtype)
 
     def channels(self, cond: torch.Tensor, storage_dtype: torch.dtype) -> torch.Tensor:
         """(B, cond_size) fp32, rounded to the storage dtype (the reference's embedder modules run in the model's dtype and the

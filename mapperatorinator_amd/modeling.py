@@ -21,7 +21,9 @@ import torch
 
 from . import _lib
 from .conditioning import ConditioningEmbedders
-from .t5_engine import T5Dims, T5Engine, T5_PRESETS, require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
+from .decode_modes import DecodeModes
+from .server import sampling_from_processors
+from .t5_engine import T5Dims, T5Engine, T5_PRESETS
 from .whisper_engine import VARWHISPER_PRESETS, VarWhisperDims, VarWhisperEngine
 
 
@@ -291,10 +293,7 @@ class MapperatorinatorHIP:
         carry beatmap_idx / difficulty / mapper_idx / song_position as the reference's forward takes them."""
         if not self.cond.active:
             return None
-        vec = self.cond.vectors(batch, beatmap_idx=kw.get("beatmap_idx"), difficulty=kw.get("difficulty"),
-                                mapper_idx=kw.get("mapper_idx"), song_position=kw.get("song_position"))
-        # project_encoder_input = false ('Tiger14n/ropewhisper-*'): the vectors are conv1 input channels, else a row bias of the projection
-        return self.cond.channels(vec, self.dtype) if self.cond.as_channels else self.cond.row_bias(vec, self.dtype)
+        return self.cond.encoder_bias(self.cond.vectors(batch, **{k: kw.get(k) for k in self.cond.INPUTS}), self.dtype)
 
     # ---- B2: the two calls the reference makes on the model object -----------------------------------------
     def _cross_kv(self, frames, encoder_outputs, row_bias=None):
@@ -384,7 +383,6 @@ class MapperatorinatorHIP:
         reference's `model_generate` calls it (server.py:143-151): the processor OBJECTS are translated
         (server.sampling_from_processors), `past_key_values` / `use_cache` are accepted and unused (the engine owns
         its caches).  Returns int64 (B, prompt + new) on the model's device, pad_token_id after each row's EOS."""
-        from .server import beam_cache_kwargs, sampling_from_processors
         audio = inputs if inputs is not None else frames
         if decoder_input_ids is None:
             raise ValueError("decoder_input_ids is required (the reference always passes the prompt)")
@@ -407,26 +405,16 @@ class MapperatorinatorHIP:
         if sp.cfg_scale > 1.0 and negative_prompt is None:
             raise ValueError("guidance needs negative_prompt (modeling_mapperatorinator.py:243-254)")
         row_bias = None if enc_states is not None else self._row_bias(decoder_input_ids.shape[0], unused)   # (the conditioning acts in the encoder)
-        kv_fp8 = bool(unused.get("cross_kv_fp8", False))
-        if kv_fp8:
-            require_bf16_for_cross_kv_fp8(self.dtype)
-        beam_cache = beam_cache_kwargs(unused)     # beam_cache / beam_prefill (beam.py): ValueError for a bad combination
-        skv8 = {}
-        if unused.get("self_kv_fp8", False):     # e4m3 shadow of the self-attention cache (T5Engine.decode): bf16 storage; under beams
-            # only over the indexed cache, where the engine's keyword is `beam_self_kv_fp8`
-            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams), unused.get("beam_cache", "copy"))
-            skv8 = dict(self_kv_fp8=True) if num_beams == 1 else dict(beam_self_kv_fp8=True)
+        modes = DecodeModes.of(unused, self.dtype, int(num_beams))    # the fp8 caches and the beam cache route: ValueError where not built
+        extra = {} if row_bias is None else dict(row_bias=row_bias)
         if num_beams != 1:
             out = self.engine.generate_beam(audio, decoder_input_ids, decoder_attention_mask, eos, sp, int(num_beams),
                                             negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
-                                            sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=kv_fp8,
-                                            **(dict(device_draw=True) if unused.get("beam_sample_kernel", False) else {}),
-                                            **beam_cache, **skv8,
-                                            **({} if row_bias is None else dict(row_bias=row_bias)))
+                                            sample_fn=unused.get("beam_sample_fn"), cross_kv_fp8=modes.cross_kv_fp8,
+                                            **modes.generate_beam_kwargs(), **extra)
             return out["tokens"].to(self.device)
         out = self.engine.generate(audio, decoder_input_ids, decoder_attention_mask, eos, sp,
                                    negative_prompt=negative_prompt if sp.cfg_scale > 1.0 else None,
-                                   negative_mask=negative_prompt_attention_mask, cross_kv_fp8=kv_fp8,
-                                   encoder_states=enc_states, **skv8,
-                                   **({} if row_bias is None else dict(row_bias=row_bias)))
+                                   negative_mask=negative_prompt_attention_mask, cross_kv_fp8=modes.cross_kv_fp8,
+                                   encoder_states=enc_states, **modes.decode_kwargs(), **extra)
         return out["tokens"].to(self.device)

@@ -26,8 +26,9 @@ from typing import Callable, Optional
 
 import torch
 
-from .server import _build_generation_stats, beam_cache_kwargs, build_row_sampling, build_sampling, row_call_key
-from .t5_engine import HostStager, require_bf16_for_self_kv_fp8
+from .decode_modes import DecodeModes
+from .server import _build_generation_stats, build_row_sampling, build_sampling, row_call_key
+from .t5_engine import HostStager, eos_id_table, guided_rows
 
 
 @dataclasses.dataclass
@@ -110,7 +111,7 @@ class SequentialWindowScheduler:
         cond = getattr(self.model, "cond", None)
         if cond is None or not cond.active:
             return None
-        keys = ("beatmap_idx", "difficulty", "mapper_idx", "song_position")
+        keys = cond.INPUTS
         rows = {k: [] for k in keys}
         for j in jobs:
             if j.conditioning_fn is None:
@@ -128,17 +129,14 @@ class SequentialWindowScheduler:
                 raise ValueError(f"conditioning input {k!r} is given for some windows only")
             kw[k] = torch.stack([torch.as_tensor(v, dtype=torch.float32 if k in ("difficulty", "song_position") else torch.long)
                                  for v in rows[k]])
-        vec = cond.vectors(n, **kw)
-        return cond.channels(vec, self.model.dtype) if cond.as_channels else cond.row_bias(vec, self.model.dtype)
+        return cond.encoder_bias(cond.vectors(n, **kw), self.model.dtype)
 
     # ---- stage 2: waves of dependent windows -----------------------------------------------------------------
     @torch.no_grad()
     def run(self, jobs: list[SongJob]):
         eng, tok = self.engine, self.tokenizer
-        for j in jobs:   # self_kv_fp8 where it is not built (fp32 storage, beams over the copied cache): refused before anything is encoded
-            if j.generate_kwargs.get("self_kv_fp8"):
-                require_bf16_for_self_kv_fp8(eng.dtype, int(j.generate_kwargs.get("num_beams", 1) or 1),
-                                             j.generate_kwargs.get("beam_cache", "copy"))
+        for j in jobs:   # a mode where it is not built: refused before anything is encoded
+            self._modes(j.generate_kwargs, int(j.generate_kwargs.get("num_beams", 1) or 1))
         start = time.perf_counter()
         kvs = self.encode_all(jobs)
         n_waves = max(j.frames.shape[0] for j in jobs)
@@ -192,6 +190,11 @@ class SequentialWindowScheduler:
             for a in range(0, len(rows), step):
                 self._decode_group(jobs, kvs, w, rows[a:a + step], pad_id, merged=True)
 
+    def _modes(self, gk: dict, nb: int) -> DecodeModes:
+        """The mode switches of one decode call, the scheduler's own way: the cache route is read under beams only (a greedy window
+        ignores it), self_kv_fp8 is refused first and cross_kv_fp8 last, the storage type is the engine's (None for a stand-in without)."""
+        return DecodeModes.of(gk, getattr(self.engine, "dtype", None), nb, beam_switches=nb > 1, order=("self", "cache", "cross"))
+
     def _call_kwargs(self, gk0: dict) -> dict:
         """the kwargs of one decode call of a group"""
         # rows of different songs share this batch where the reference runs one batch-1 call per window: the conditional
@@ -219,8 +222,7 @@ class SequentialWindowScheduler:
             sp, eos = build_sampling(tok, gk, self.model.config.max_target_positions)
         cfg = sp.cfg_scale > 1.0
         nb = int(getattr(sp, "num_beams", 1) or 1)
-        if gk.get("self_kv_fp8"):   # (a window's own generate_kwargs may switch the mode on: the same refusals)
-            require_bf16_for_self_kv_fp8(eng.dtype, nb, gk.get("beam_cache", "copy"))
+        modes = self._modes(gk, nb)   # (a window's own generate_kwargs may switch a mode on: the same refusals)
         if len(group) * (2 if cfg else 1) * nb > 64:
             raise ValueError(f"{len(group)} windows{' x 2 (guidance)' if cfg else ''}{f' x {nb} beams' if nb > 1 else ''} exceed "
                              f"the engine's 64-row decode batch")
@@ -233,39 +235,25 @@ class SequentialWindowScheduler:
             # ragged prompts: only the left padding added HERE must not be attended -- a pad_id inside a caller's own
             # prompt stays visible, exactly as in the batch-1 call without a mask
             masks = _left_pad([torch.ones_like(g[1]["decoder_input_ids"]) for g in group], 0, torch.uint8)
-        neg = None
-        if cfg:
+        p_all, m_all = prompts, masks
+        if cfg:      # [negative rows | prompt rows] of the left-padded prompts
             if any(g[1].get("negative_prompt") is None for g in group):
                 raise ValueError("cfg_scale > 1 needs a negative_prompt for every window")
-            neg_rows = _left_pad([g[1]["negative_prompt"] for g in group], pad_id, torch.int64)
-            if neg_rows.shape[1] > prompts.shape[1]:
-                raise ValueError("negative prompt longer than the prompt")
-            # as prepare_inputs_for_generation: the negative prompt overwrites the first columns of a copy of the prompt
-            neg = prompts.clone()
-            neg[:, :neg_rows.shape[1]] = neg_rows
+            p_all, m_all, _ = guided_rows(prompts, masks, _left_pad([g[1]["negative_prompt"] for g in group], pad_id, torch.int64))
         dev = eng.device
-        eos_table = torch.zeros(eng.packed.vocab_out, dtype=torch.uint8)
-        eos_table[torch.as_tensor(sorted(set(int(e) for e in eos if 0 <= int(e) < eng.packed.vocab_out)),
-                                  dtype=torch.long)] = 1
+        eos_table = eos_id_table(eos, eng.packed.vocab_out)
         eos_ids = torch.as_tensor(sorted(set(int(e) for e in eos)), dtype=torch.int64)
         t0 = time.perf_counter()
         eng._enter()
         with eng.on_stream():
             kv = torch.stack([kvs[g[0]][:, :, w] for g in group], 2).contiguous()   # rows of this wave, gathered
-            p_all = torch.cat([neg, prompts], 0) if cfg else prompts
-            m_all = None if masks is None else (torch.cat([masks, masks], 0) if cfg else masks)
-            # generate_kwargs["cross_kv_fp8"]: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search
-            # makes it itself: with guidance it is a copy of the doubled rows)
-            kv8 = eng.cross_kv_fp8(kv) if gk.get("cross_kv_fp8") and nb == 1 else None
-            # generate_kwargs["self_kv_fp8"]: the token steps attend the engine's e4m3 shadow of the self-attention cache (under beams
-            # the search takes it, over the indexed cache only)
-            skv8 = dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {}
-            if merged:   # every row under its own settings (mh_t5_generate_rows); eos_table is ignored there
-                skv8["row_sampling"] = row_sampling
-            if nb == 1:
+            # cross_kv_fp8: the token steps stream an e4m3 copy of this wave's cross K / V (under beams the search makes it itself:
+            # with guidance it is a copy of the doubled rows)
+            kv8 = eng.cross_kv_fp8(kv) if modes.cross_kv_fp8 and nb == 1 else None
+            if nb == 1:   # merged: every row under its own settings (mh_t5_generate_rows); eos_table is ignored there
                 tokens, n_out, _ = eng.decode(kv, p_all.to(dev, torch.int32).contiguous(),
-                                              None if m_all is None else m_all.to(dev).contiguous(),
-                                              eos_table.to(dev), sp, kv_fp8=kv8, **skv8)
+                                              None if m_all is None else m_all.to(dev).contiguous(), eos_table.to(dev), sp, kv_fp8=kv8,
+                                              **modes.decode_kwargs(), **(dict(row_sampling=row_sampling) if merged else {}))
         eng._leave()
         if nb > 1:
             # HF beam search over the step-wise decode entry (beam.py), the windows of this wave as its batch: every window's
@@ -273,10 +261,7 @@ class SequentialWindowScheduler:
             # end early carry HF's fill (the first EOS id) and are cut at their first EOS-set id below like any other row
             from .beam import beam_search
             result = beam_search(eng, kv, p_all, m_all, eos, sp, nb, sample_fn=gk.get("beam_sample_fn"),
-                                 kv_fp8=True if gk.get("cross_kv_fp8") else None,
-                                 **(dict(device_draw=True) if gk.get("beam_sample_kernel") else {}),
-                                 **{k[5:]: v for k, v in beam_cache_kwargs(gk).items()},
-                                 **(dict(self_kv_fp8=True) if gk.get("self_kv_fp8") else {})).to(torch.int64).cpu()
+                                 **modes.beam_search_kwargs()).to(torch.int64).cpu()
         else:
             eng.synchronize()
             n_cols = int(n_out.item())

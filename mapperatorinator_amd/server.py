@@ -9,7 +9,8 @@ batch layout: the negative prompt rows first, the prompt rows second, one shared
 (modeling_mapperatorinator.py:243-254).  `num_beams > 1` runs HF's beam search over the step-wise decode entry
 (mapperatorinator_amd/beam.py), with `do_sample` as HF's beam-sample (`generate_kwargs["beam_sample_fn"]` replaces the device's
 `torch.multinomial` draw; what is not built raises NotImplementedError -- never a silent approximation).  `RequestBatcher` at the end of the file is the batching policy of the reference's
-InferenceServer (server.py:343-424) in front of this function.
+InferenceServer (server.py:343-424) in front of this function.  The decode mode switches among the generate kwargs (`cross_kv_fp8`,
+`self_kv_fp8`, `beam_cache`, `beam_prefill`, `beam_sample_kernel`) are read, refused and renamed for the engine in decode_modes.py.
 """
 from __future__ import annotations
 
@@ -19,8 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .decode_modes import DecodeModes, require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8  # noqa: F401
 from .event import ContextType
-from .t5_engine import require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8
+from .t5_engine import eos_id_table
 
 MILISECONDS_PER_SECOND = 1000
 MILISECONDS_PER_STEP = 10
@@ -318,9 +320,7 @@ def build_row_sampling(tokenizer, generate_kwargs_list, max_target_positions: in
             row.cond_temp[j] = float(slots[slot][0]) if slot in slots else sp_e.temperature
             if slot in slots:                              # a rule the reference drops for this row stays masked out
                 row.cond_mask |= 1 << j
-    eos_tables = torch.zeros((len(tables), vocab), dtype=torch.uint8)
-    for i, ids in enumerate(tables):
-        eos_tables[i, torch.as_tensor(ids, dtype=torch.long)] = 1
+    eos_tables = torch.stack([eos_id_table(ids, vocab) for ids in tables])
     firsts = list(built.values())
     sp = firsts[0][0]
     flags = np.zeros(vocab, dtype=np.uint8)
@@ -409,24 +409,31 @@ def sampling_from_processors(processors, vocab_size_out: int, *, do_sample=False
     return sp
 
 
-def beam_cache_kwargs(generate_kwargs: dict) -> dict:
-    """generate_kwargs["beam_cache"] ("copy", the default, or "indexed") and ["beam_prefill"] as the keyword arguments of
-    T5Engine.generate_beam; nothing when both are at their defaults.  An unknown value, or the prefill without the indexed cache,
-    is a ValueError (beam.py)."""
-    from .beam import check_cache_mode
-    cache, prefill = generate_kwargs.get("beam_cache", "copy"), bool(generate_kwargs.get("beam_prefill", False))
-    check_cache_mode(cache, prefill)
-    return {} if cache == "copy" else dict(beam_cache=cache, beam_prefill=prefill)
-
-
-def _conditioning_bias(model, model_kwargs):
+def _conditioning_kwargs(model, model_kwargs) -> dict:
+    """`row_bias=` of the engine's generate entries for a model that carries conditioning embedders (modeling_mapperatorinator.py:
+    174-228), nothing for any other -- exactly the reference's `if self.do_*_embed` switches"""
     cond = getattr(model, "cond", None)
     if cond is None or not cond.active:
-        return None
-    vec = cond.vectors(model_kwargs["inputs"].shape[0], beatmap_idx=model_kwargs.get("beatmap_idx"),
-                       difficulty=model_kwargs.get("difficulty"), mapper_idx=model_kwargs.get("mapper_idx"),
-                       song_position=model_kwargs.get("song_position"))
-    return cond.channels(vec, model.dtype) if cond.as_channels else cond.row_bias(vec, model.dtype)
+        return {}
+    vec = cond.vectors(model_kwargs["inputs"].shape[0], **{k: model_kwargs.get(k) for k in cond.INPUTS})
+    return dict(row_bias=cond.encoder_bias(vec, model.dtype))
+
+
+def _check_max_length(sp, model):
+    if sp.max_length > model.config.max_target_positions:
+        raise ValueError(f"max_length {sp.max_length} exceeds max_target_positions {model.config.max_target_positions}")
+
+
+def _guidance_prompt(sp, model_kwargs):
+    """-> (negative prompt, its mask) of a guided call, (None, None) of any other"""
+    if sp.cfg_scale <= 1.0:
+        # the reference doubles the batch whenever a negative prompt is passed and, without the CFG processor, HF
+        # then fails on the shape mismatch; its own caller only passes one when cfg_scale > 1 (processor.py:1171)
+        return None, None
+    if model_kwargs.get("negative_prompt") is None:
+        # HF's processor would raise on the batch-size check (logits not doubled without a negative prompt)
+        raise ValueError("cfg_scale > 1 needs model_kwargs['negative_prompt'] (modeling_mapperatorinator.py:243-254)")
+    return model_kwargs["negative_prompt"], model_kwargs.get("negative_prompt_attention_mask")
 
 
 @torch.no_grad()
@@ -436,30 +443,18 @@ def model_generate_rows(model, tokenizer, model_kwargs, generate_kwargs_list):
     `model_generate` take one kwargs set per call).  Each row's ids are those of a `model_generate` call made of the rows that
     share its kwargs.  Same result and stats as `model_generate`; the rows must agree in the per-call settings."""
     sp, rows, eos_tables = build_row_sampling(tokenizer, generate_kwargs_list, model.config.max_target_positions)
-    if sp.max_length > model.config.max_target_positions:
-        raise ValueError(f"max_length {sp.max_length} exceeds max_target_positions {model.config.max_target_positions}")
+    _check_max_length(sp, model)
     gk0 = generate_kwargs_list[0]
     if len(generate_kwargs_list) != model_kwargs["decoder_input_ids"].shape[0]:
         raise ValueError(f"{len(generate_kwargs_list)} generate kwargs for {model_kwargs['decoder_input_ids'].shape[0]} rows")
     pad_token_id = gk0.get("pad_token_id", getattr(tokenizer, "pad_id", None))
-    neg = model_kwargs.get("negative_prompt")
-    if sp.cfg_scale > 1.0 and neg is None:
-        raise ValueError("cfg_scale > 1 needs model_kwargs['negative_prompt'] (modeling_mapperatorinator.py:243-254)")
-    if sp.cfg_scale <= 1.0:
-        neg = None
-    kv_fp8 = bool(gk0.get("cross_kv_fp8", False))
-    if kv_fp8:
-        require_bf16_for_cross_kv_fp8(model.dtype)
-    extra = {}
-    row_bias = _conditioning_bias(model, model_kwargs)
-    if row_bias is not None:
-        extra["row_bias"] = row_bias
-    if gk0.get("self_kv_fp8", False):
-        require_bf16_for_self_kv_fp8(model.dtype, 1)
-        extra["self_kv_fp8"] = True
+    neg, _ = _guidance_prompt(sp, model_kwargs)
+    modes = DecodeModes.of(gk0, getattr(model, "dtype", None), 1, beam_switches=False)   # (the rows agree in the fp8 modes; none has beams)
+    extra = _conditioning_kwargs(model, model_kwargs)
     start = time.perf_counter()
     out = model.engine.generate(model_kwargs["inputs"], model_kwargs["decoder_input_ids"], model_kwargs.get("decoder_attention_mask"),
-                                None, sp, negative_prompt=neg, cross_kv_fp8=kv_fp8, row_sampling=(sp, rows, eos_tables), **extra)
+                                None, sp, negative_prompt=neg, cross_kv_fp8=modes.cross_kv_fp8, row_sampling=(sp, rows, eos_tables),
+                                **extra, **modes.decode_kwargs())
     result = out["tokens"]
     return result, _build_generation_stats(result, model_kwargs, pad_token_id, time.perf_counter() - start)
 
@@ -468,54 +463,26 @@ def model_generate_rows(model, tokenizer, model_kwargs, generate_kwargs_list):
 def model_generate(model, tokenizer, model_kwargs, generate_kwargs):
     """See module docstring.  `model_kwargs['inputs']`: raw audio float32 (B, Ns)."""
     generate_kwargs = dict(generate_kwargs)
-    # conditioning inputs (modeling_mapperatorinator.py:174-228): used when the model carries the embedders, ignored
-    # otherwise -- exactly the reference's `if self.do_*_embed` switches
-    row_bias = _conditioning_bias(model, model_kwargs)
-    audio = model_kwargs["inputs"]
-    prompt = model_kwargs["decoder_input_ids"]
-    mask = model_kwargs.get("decoder_attention_mask")
+    extra = _conditioning_kwargs(model, model_kwargs)
+    audio, prompt, mask = model_kwargs["inputs"], model_kwargs["decoder_input_ids"], model_kwargs.get("decoder_attention_mask")
     sp, eos = build_sampling(tokenizer, generate_kwargs, model.config.max_target_positions)
-    if sp.max_length > model.config.max_target_positions:
-        raise ValueError(f"max_length {sp.max_length} exceeds max_target_positions "
-                         f"{model.config.max_target_positions}")
+    _check_max_length(sp, model)
     pad_token_id = generate_kwargs.get("pad_token_id", getattr(tokenizer, "pad_id", None))
-
-    neg, neg_mask = model_kwargs.get("negative_prompt"), model_kwargs.get("negative_prompt_attention_mask")
-    if sp.cfg_scale > 1.0 and neg is None:
-        # HF's processor would raise on the batch-size check (logits not doubled without a negative prompt)
-        raise ValueError("cfg_scale > 1 needs model_kwargs['negative_prompt'] (modeling_mapperatorinator.py:243-254)")
-    if sp.cfg_scale <= 1.0:
-        # the reference doubles the batch whenever a negative prompt is passed and, without the CFG processor, HF
-        # then fails on the shape mismatch; its own caller only passes one when cfg_scale > 1 (processor.py:1171)
-        neg = neg_mask = None
-
-    kv_fp8 = bool(generate_kwargs.get("cross_kv_fp8", False))
-    if kv_fp8:
-        require_bf16_for_cross_kv_fp8(model.dtype)
-    beam_cache = beam_cache_kwargs(generate_kwargs)              # (refused here, before anything is encoded)
+    neg, neg_mask = _guidance_prompt(sp, model_kwargs)
+    n_beams = int(getattr(sp, "num_beams", 1) or 1)
+    modes = DecodeModes.of(generate_kwargs, getattr(model, "dtype", None), n_beams)     # (refused here, before anything is encoded)
     start = time.perf_counter()
-    extra = {} if row_bias is None else dict(row_bias=row_bias)
-    if generate_kwargs.get("self_kv_fp8", False):
-        # the token steps attend an e4m3 shadow of the self-attention cache (T5Engine.decode); bf16 storage; under beams only with
-        # beam_cache="indexed" (beam.py `self_kv_fp8`), where the engine's keyword is `beam_self_kv_fp8`
-        n_beams = int(getattr(sp, "num_beams", 1) or 1)
-        require_bf16_for_self_kv_fp8(model.dtype, n_beams, generate_kwargs.get("beam_cache", "copy"))
-        extra["beam_self_kv_fp8" if n_beams > 1 else "self_kv_fp8"] = True
-    if getattr(sp, "num_beams", 1) > 1:
-        if generate_kwargs.get("beam_sample_kernel", False):      # opt-in: beam-sample draws inside the step kernel (beam.py `device_draw`)
-            extra["device_draw"] = True
-        extra.update(beam_cache)                                 # opt-in: the self-attention cache by index, the prompt prefilled
+    if n_beams > 1:
         # HF beam search (processor.py:159 `num_beams`; the timing generator uses two beams): mapperatorinator_amd/beam.py
         out = model.engine.generate_beam(audio, prompt, mask, eos, sp, sp.num_beams, negative_prompt=neg,
                                          sample_fn=generate_kwargs.get("beam_sample_fn"),
-                                         use_kernel=generate_kwargs.get("beam_use_kernel"), cross_kv_fp8=kv_fp8, **extra)
+                                         use_kernel=generate_kwargs.get("beam_use_kernel"), cross_kv_fp8=modes.cross_kv_fp8,
+                                         **extra, **modes.generate_beam_kwargs())
     else:
         out = model.engine.generate(audio, prompt, mask, eos, sp, negative_prompt=neg, negative_mask=neg_mask,
-                                    cross_kv_fp8=kv_fp8, **extra)
-    elapsed = time.perf_counter() - start
+                                    cross_kv_fp8=modes.cross_kv_fp8, **extra, **modes.decode_kwargs())
     result = out["tokens"]
-    stats = _build_generation_stats(result, model_kwargs, pad_token_id, elapsed)
-    return result, stats
+    return result, _build_generation_stats(result, model_kwargs, pad_token_id, time.perf_counter() - start)
 
 
 def _forward_inputs(model, model_kwargs, generate_kwargs):

@@ -21,6 +21,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .decode_modes import DecodeModes, check_cache_mode, require_bf16_for_cross_kv_fp8, require_bf16_for_self_kv_fp8  # noqa: F401
 from .mel import MelSpectrogram
 
 
@@ -194,25 +195,24 @@ class PackedT5:
         return sum(t.numel() * t.element_size() for t in self._keep)
 
 
-def require_bf16_for_cross_kv_fp8(dtype) -> None:
-    """`cross_kv_fp8` on a model that does not store bf16: refused on the host, before anything is encoded (the copy is made of
-    bf16 rows, and the fp32 cross-attention kernel has no e4m3 form)."""
-    if dtype != torch.bfloat16:
-        raise ValueError(f"cross_kv_fp8 needs bf16 storage (this model stores {dtype}): the e4m3 copy of the cross-attention K / V "
-                         "is made of bf16 rows")
+def guided_rows(prompt: torch.Tensor, prompt_mask, negative_prompt: torch.Tensor, forced=None):
+    """The doubled batch of classifier-free guidance as the reference's prepare_inputs_for_generation builds it (modeling_mapperatorinator.py:
+    243-254): -> (prompt, mask, forced) as [negative rows | prompt rows], the negative prompt over the first columns of a copy of the
+    prompt.  The negative rows attend under the PROMPT's mask: in the reference the kwarg `negative_prompt_attention_mask` is
+    swallowed by HF `generate()` (a named parameter of its own) before prepare_inputs_for_generation runs."""
+    n = negative_prompt.shape[1]
+    if n > prompt.shape[1]:
+        raise ValueError("negative prompt longer than the prompt")
+    neg = prompt.clone()
+    neg[:, :n] = negative_prompt.to(prompt.dtype)
+    return (torch.cat([neg, prompt], 0), *(None if t is None else torch.cat([t, t], 0) for t in (prompt_mask, forced)))
 
 
-def require_bf16_for_self_kv_fp8(dtype, num_beams: int = 1, beam_cache: str = "copy") -> None:
-    """`self_kv_fp8` where it is not built: refused on the host, before anything is encoded.  The shadow cache is made of bf16 rows
-    (fp32 storage has no e4m3 self-attention kernel), and the step-wise entries of beam search over the copied cache (`mh_t5_step`,
-    `mh_t5_step_fp8`, `mh_t5_reorder_cache`) have no shadow-cache form.  Beams over the indexed cache have one
-    (`mh_t5_step_indexed_skv8`) and pass."""
-    if dtype != torch.bfloat16:
-        raise ValueError(f"self_kv_fp8 needs bf16 storage (this model stores {dtype}): the e4m3 self-attention cache is made of "
-                         "bf16 rows")
-    if num_beams > 1 and beam_cache != "indexed":
-        raise ValueError(f"self_kv_fp8 is not built for beam search over the copied cache (num_beams={num_beams}): mh_t5_step and the "
-                         "cache reorder have no e4m3 shadow-cache form; pass beam_cache='indexed', use num_beams=1 or drop the flag")
+def eos_id_table(eos_ids, vocab_out: int) -> torch.Tensor:
+    """uint8 (vocab_out,) on the host: 1 at every EOS id inside the output vocabulary"""
+    table = torch.zeros(vocab_out, dtype=torch.uint8)
+    table[torch.as_tensor(sorted({int(e) for e in (eos_ids or ()) if 0 <= int(e) < vocab_out}), dtype=torch.long)] = 1
+    return table
 
 
 def next_token_targets(ids: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -541,36 +541,23 @@ class T5Engine:
         with `device_draw=True` inside the step kernel (mh_beam_step_sample; seed sampling.seed: beam.py).
         `cross_kv_fp8`: every step streams the e4m3 copy of the cross-attention K / V (see `cross_kv_fp8()`; under guidance the copy
         is made of the doubled rows).
-        `beam_cache` "copy" | "indexed" and `beam_prefill`: beam.py `cache` / `prefill` -- the self-attention cache followed by an
-        index table instead of copied after every token, and the prompt prefilled once per chunk (needs the indexed cache).
-        `beam_self_kv_fp8` (beam.py `self_kv_fp8`; needs the indexed cache and bf16 storage): the steps attend the e4m3 shadow of
-        the self-attention cache through the same table (`mh_t5_step_indexed_skv8`)."""
-        from .beam import beam_search, check_cache_mode
-        check_cache_mode(beam_cache, beam_prefill)
-        if beam_self_kv_fp8:
-            require_bf16_for_self_kv_fp8(self.dtype, int(num_beams), beam_cache)
-        if cross_kv_fp8:
-            require_bf16_for_cross_kv_fp8(self.dtype)
+        `beam_cache` "copy" | "indexed", `beam_prefill`, `beam_self_kv_fp8`: beam.py `cache` / `prefill` / `self_kv_fp8` (decode_modes.py)
+        -- the self-attention cache followed by an index table instead of copied after every token, the prompt prefilled once per
+        chunk, the e4m3 shadow of the cache read through the same table (the last two need the indexed cache)."""
+        from .beam import beam_search
+        modes = DecodeModes.of(dict(cross_kv_fp8=cross_kv_fp8, self_kv_fp8=beam_self_kv_fp8, beam_cache=beam_cache, beam_prefill=beam_prefill,
+                                    beam_sample_kernel=device_draw), self.dtype, int(num_beams), order=("cache", "self", "cross"))
         audio = audio.to(self.device, torch.float32)
         if (negative_prompt is not None) != (sampling.cfg_scale > 1.0):
             raise ValueError("negative_prompt and sampling.cfg_scale > 1 go together")
         if negative_prompt is not None:
-            n = negative_prompt.shape[1]
-            if n > prompt.shape[1]:
-                raise ValueError("negative prompt longer than the prompt")
-            neg = prompt.clone()
-            neg[:, :n] = negative_prompt.to(prompt.dtype)
-            prompt = torch.cat([neg, prompt], 0)
-            if prompt_mask is not None:      # (the negative rows attend under the prompt's mask: see `generate`)
-                prompt_mask = torch.cat([prompt_mask, prompt_mask], 0)
+            prompt, prompt_mask, _ = guided_rows(prompt, prompt_mask, negative_prompt)
         self._enter()
         with torch.cuda.stream(self.stream):
             kv = self.cross_kv(self.encode_mel(self.mel(audio), row_bias=row_bias))
         self._leave()
         out = beam_search(self, kv, prompt, prompt_mask, eos_ids, sampling, num_beams, length_penalty, early_stopping,
-                          sample_fn=sample_fn, use_kernel=use_kernel, kv_fp8=True if cross_kv_fp8 else None, device_draw=device_draw,
-                          **({} if beam_cache == "copy" else dict(cache=beam_cache, prefill=bool(beam_prefill))),
-                          **(dict(self_kv_fp8=True) if beam_self_kv_fp8 else {}))
+                          sample_fn=sample_fn, use_kernel=use_kernel, **modes.beam_search_kwargs())
         return dict(tokens=out.cpu(), n_cols=int(out.shape[1]), logits=None)
 
     def generate(self, audio: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
@@ -585,14 +572,9 @@ class T5Engine:
         cross-attention K / V (see `cross_kv_fp8()`); `self_kv_fp8`: they attend the e4m3 shadow of the self-attention cache (see `decode`; the two
         compose to a whole fp8 K/V cache).  Inputs may be CPU tensors (copied like
         server.py:86-87 does).  Returns dict(tokens=int64 CPU (B, n_cols), logits=..., n_cols=int).
-        With `negative_prompt` (classifier-free guidance) the decode batch is doubled the way the reference's
-        prepare_inputs_for_generation does it (modeling_mapperatorinator.py:243-254): the first half carries the
-        negative prompt over the first columns of the prompt; the returned rows are the prompt rows."""
+        With `negative_prompt` (classifier-free guidance) the decode batch is doubled (`guided_rows`); the returned rows are the prompt rows."""
         dev = self.device
-        if cross_kv_fp8:
-            require_bf16_for_cross_kv_fp8(self.dtype)
-        if self_kv_fp8:
-            require_bf16_for_self_kv_fp8(self.dtype)
+        DecodeModes.of(dict(cross_kv_fp8=cross_kv_fp8, self_kv_fp8=self_kv_fp8), self.dtype)
         if encoder_states is None:
             audio = audio.to(dev, torch.float32)
         else:
@@ -603,27 +585,12 @@ class T5Engine:
         cfg = negative_prompt is not None
         if cfg != (sampling.cfg_scale > 1.0):
             raise ValueError("negative_prompt and sampling.cfg_scale > 1 go together")
-        if cfg:
-            n = negative_prompt.shape[1]
-            if n > prompt.shape[1]:
-                raise ValueError("negative prompt longer than the prompt")
-            neg = prompt.clone()
-            neg[:, :n] = negative_prompt.to(prompt.dtype)
-            prompt = torch.cat([neg, prompt], 0)
-            if prompt_mask is not None:
-                # `negative_mask` is accepted for signature parity and deliberately unused: in the reference the
-                # kwarg `negative_prompt_attention_mask` is swallowed by HF `generate()` (a named parameter of its
-                # own) before prepare_inputs_for_generation runs, so the negative rows attend under the prompt's mask
-                prompt_mask = torch.cat([prompt_mask, prompt_mask], 0)
-            if forced is not None:
-                forced = torch.cat([forced, forced], 0)
+        if cfg:      # (`negative_mask` is accepted for signature parity and deliberately unused: see `guided_rows`)
+            prompt, prompt_mask, forced = guided_rows(prompt, prompt_mask, negative_prompt, forced)
         prompt_d = prompt.to(dev, torch.int32).contiguous()
         mask_d = prompt_mask.to(dev).to(torch.uint8).contiguous() if prompt_mask is not None else None
         forced_d = forced.to(dev, torch.int32).contiguous() if forced is not None else None
-        eos_table = torch.zeros(self.packed.vocab_out, dtype=torch.uint8)
-        eos_table[torch.as_tensor(sorted(set(int(e) for e in (eos_ids or ()) if 0 <= int(e) < self.packed.vocab_out)),
-                                  dtype=torch.long)] = 1
-        eos_table = eos_table.to(dev)
+        eos_table = eos_id_table(eos_ids, self.packed.vocab_out).to(dev)
         self._enter()
         with torch.cuda.stream(self.stream):
             enc = encoder_states if encoder_states is not None else self.encode_mel(self.mel(audio), row_bias=row_bias)
