@@ -54,32 +54,51 @@ enum { KID_GEMV = 0 /* + EPI * 2 + (NWV == 8) */, KID_SELF = 10, KID_CROSS = 11,
 // the 256 MB Infinity Cache between token steps.
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-template <typename T> __device__ inline void load8_stream(const T* p, float (&o)[8]);
-template <> __device__ inline void load8_stream<bf16_t>(const bf16_t* p, float (&o)[8]) {
-  const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+// The two halves of a streamed chunk: `load` only REQUESTS the 8 elements as they lie in memory (16 bytes per lane for bf16, 8 for
+// e4m3), `unpack` widens them where they are used -- a request can then be issued long before its data is needed at the cost of
+// the raw registers alone (Raw8 below does the same for the weights).
+template <typename T> struct StreamRaw8;
+template <> struct StreamRaw8<bf16_t> {
+  u32x4_t v;
+  __device__ inline void load(const bf16_t* p) { v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p)); }
+  __device__ inline void unpack(float (&o)[8]) const {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    o[2 * i] = __uint_as_float(v[i] << 16);
-    o[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+    for (int i = 0; i < 4; ++i) {
+      o[2 * i] = __uint_as_float(v[i] << 16);
+      o[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+    }
   }
-}
-template <> __device__ inline void load8_stream<float>(const float* p, float (&o)[8]) {
-  const u32x4_t a = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-  const u32x4_t b = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p + 4));
+};
+template <> struct StreamRaw8<float> {
+  u32x4_t a, b;
+  __device__ inline void load(const float* p) {
+    a = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+    b = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p + 4));
+  }
+  __device__ inline void unpack(float (&o)[8]) const {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { o[i] = __uint_as_float(a[i]); o[4 + i] = __uint_as_float(b[i]); }
-}
+    for (int i = 0; i < 4; ++i) { o[i] = __uint_as_float(a[i]); o[4 + i] = __uint_as_float(b[i]); }
+  }
+};
 // OCP e4m3 rows (the fp8 copy of the cross-attention K / V): 8 elements = 8 bytes per lane
 struct fp8_t { uint8_t v; };
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-template <> __device__ inline void load8_stream<fp8_t>(const fp8_t* p, float (&o)[8]) {
-  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
+template <> struct StreamRaw8<fp8_t> {
+  u32x2_t v;
+  __device__ inline void load(const fp8_t* p) { v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p)); }
+  __device__ inline void unpack(float (&o)[8]) const {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);
-    const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);
-    o[4 * i] = lo[0]; o[4 * i + 1] = lo[1]; o[4 * i + 2] = hi[0]; o[4 * i + 3] = hi[1];
+    for (int i = 0; i < 2; ++i) {
+      const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);
+      const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);
+      o[4 * i] = lo[0]; o[4 * i + 1] = lo[1]; o[4 * i + 2] = hi[0]; o[4 * i + 3] = hi[1];
+    }
   }
+};
+template <typename T> __device__ inline void load8_stream(const T* p, float (&o)[8]) {
+  StreamRaw8<T> r;
+  r.load(p);
+  r.unpack(o);
 }
 template <typename T> __device__ inline void store8(T* p, const float (&o)[8]);
 template <> __device__ inline void store8<bf16_t>(bf16_t* p, const float (&o)[8]) {
@@ -869,6 +888,35 @@ __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key g
   s.m = mw;
 }
 
+// The first iteration of a lane group -- keys j0, j0 + jstride, ..., U of them, K and V -- as its caller requested it AHEAD of the loop:
+// raw, as the rows lie in memory (16 bytes per lane and matrix for bf16, 8 for e4m3), unpacked only where attend_keys uses them.  The
+// addresses need nothing but kernel arguments, so a kernel can have this round trip under way while it still computes its query.
+// `issue` is unconditional: the row index is clamped into [0, max(jend, 1) - 1] like every other load here, and for a group with
+// j0 < jend the rows are exactly those the loop's first iteration reads (keys past jend fall back to row j0).  A group with
+// j0 >= jend reads some mapped row whose content attend_keys never looks at.
+template <typename E, int U, bool IDX = false>
+struct FirstKeys {
+  StreamRaw8<E> k[U], v[U];
+  __device__ inline void issue(const E* kbase, const E* vbase, int j0, int jend, int jstride, const uint8_t* origin = nullptr,
+                               long row_stride = 0) {
+    const int c8 = (threadIdx.x & 7) * 8;
+    const int last = (jend > 1 ? jend : 1) - 1;
+    long row[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int jj = j0 + u * jstride;
+      int jc = jj < jend ? jj : j0;
+      jc = jc < last ? jc : last;
+      row[u] = (long)jc * 64 + c8;
+      if constexpr (IDX) row[u] += (long)origin[jc] * row_stride;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) k[u].load(kbase + row[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u].load(vbase + row[u]);
+  }
+};
+
 // SC (the e4m3 self-attention cache): every key row carries its own fp32 scale pair, kscale_row[j] / vscale_row[j], fetched the
 // way the bias is (one value per key per 8-lane group, clamped index, unconditional load); the key scale multiplies the score
 // before bias and mask, the value scale multiplies the probability before the accumulate
@@ -877,12 +925,17 @@ __device__ inline void partial_merge_groups(Partial& s) {  // across the 8 key g
 // cache rows (H * tgt_len * 64).  An 8-lane group still reads one whole row; only the row's base differs from key to key.
 // SC with IDX (mh_t5_step_indexed_skv8): kscale_row / vscale_row are head h of shadow row 0 and key j's pair sits at
 // origin[j] * (row_stride / 64) + j -- the scales of the row that holds the key, never those of the decode row.
-template <typename T, int U, typename E = T, bool SC = false, bool IDX = false>
+// EARLY: `first` holds the requests of the first iteration (FirstKeys::issue with the same kbase / vbase / j0 / jend / jstride /
+// origin / row_stride); the first iteration takes its rows from there -- if the group has one: the loop header is what discards the
+// requests of a group with j0 >= jend -- and every later one loads as ever.  There is ONE loop body: every other load (bias, mask,
+// scale pairs, table) and every product, sum, maximum and exponential is where it always was.
+template <typename T, int U, typename E = T, bool SC = false, bool IDX = false, bool EARLY = false>
 __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kbase, const E* vbase, int j0,
                                    int jend, int jstride, const float* bias_row, int pos, const uint8_t* mask_row,
                                    int P, float scale, int jmin = 0,   // keys below jmin are masked (sliding window)
                                    const float* kscale_row = nullptr, const float* vscale_row = nullptr,
-                                   const uint8_t* origin = nullptr, long row_stride = 0) {
+                                   const uint8_t* origin = nullptr, long row_stride = 0,
+                                   const FirstKeys<E, U, IDX>* first = nullptr) {
   // processes keys j0, j0+jstride, ... < jend for this lane's key group, U at a time
   const int c8 = (threadIdx.x & 7) * 8;
   for (int j = j0; j < jend; j += jstride * U) {
@@ -890,7 +943,23 @@ __device__ inline void attend_keys(Partial& st, const float (&q)[8], const E* kb
     float kv[U][8];
     float vv[U][8];
     int org_u[U];   // (IDX) the table value of key u: its scale pair below is addressed from the same LDS read as its K / V
-    if constexpr (IDX) {
+    bool requested = false;   // (EARLY) the rows of this iteration are those of `first`
+    if constexpr (EARLY) {
+      requested = j == j0;
+      if (requested) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if constexpr (IDX) {
+            const int jj = j + u * jstride;
+            org_u[u] = origin[jj < jend ? jj : j];
+          }
+          first->k[u].unpack(kv[u]);
+          first->v[u].unpack(vv[u]);
+        }
+      }
+    }
+    if (requested) {   // (nothing to load; the branches below are the loads as they always were)
+    } else if constexpr (IDX) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int jj = j + u * jstride;
@@ -1243,16 +1312,28 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
   // head's 64 x d slice of Wq, which does not depend on the activations; then the remaining kernel arguments
   nrow.issue(hp, b);
   if (sizeof(T) == 2) proj.load(hp, row0);
-  // (LDS-DMA prefetch of every wave's first 1-3 key iterations during this prologue -- 32 KB of LDS per iteration, issued as
-  // inline asm behind shadow loads so that no wait of the prologue covers it -- was built and measured: 703 / 703 / 729 us
-  // per token step for 1 / 2 / 3 iterations against 679 without.  Not kept.  Round 5, the same idea through REGISTERS (every lane
-  // group's first key / value row, 32 bytes per lane, requested beside the prologue's operands): 285.8-286.5 ms per batch against
-  // 276.7-277.0 -- the stream's requests queue in front of the weight slice the prologue waits for.  Not kept either.)
+  // The key stream cannot USE a row before the query exists, but the addresses of every lane group's first K / V row need nothing
+  // but kernel arguments.  Three placements of that first request:
+  // 1. At kernel entry through LDS-DMA (every wave's first 1-3 key iterations, 32 KB of LDS per iteration, issued as inline asm
+  //    behind shadow loads so that no wait of the prologue covers it): 703 / 703 / 729 us per token step for 1 / 2 / 3 iterations
+  //    against 679 without.  Not kept.
+  // 2. At kernel entry into REGISTERS (32 bytes per lane, beside the prologue's operands): 285.8-286.5 ms per batch against
+  //    276.7-277.0 -- the stream's requests queue in front of the weight slice and the residual row the prologue waits for.  Not kept.
+  // 3. kEarlyKV, below: into registers AFTER the row is normalised -- the prologue's operands have arrived, nothing of this workgroup
+  //    is queued -- and BEFORE the projection's arithmetic, ~0.9 us of VALU and LDS work with no vector-memory request
+  //    outstanding, which now covers the round trip that attend_keys used to start behind the projection's barrier.  Kept: the
+  //    kernel 14.39 -> 13.64 us at 16 rows, 260.13 -> 256.21 ms per batch (profiles/decode_early_kv.txt).
+  // bf16 storage only: the fp32 weight slice is requested after the normalisation and would queue behind the K / V rows.  Not the
+  // Whisper family (WH): with 8 (bf16) / 4 (e4m3) more registers live across the projection its bf16 forms at d = 768 and 896 spill
+  // and others reach the 64 registers that two workgroups per CU allow; the family keeps the old order.
+  constexpr bool kEarlyKV = sizeof(T) == 2 && !WH;
+  FirstKeys<E, U> first;
   unsigned long long t_start = 0;
   if (p.tstamp && threadIdx.x == 0) t_start = (unsigned long long)wall_clock64();
   nrow.finish(hp, xn, red16);
   MH_STAMP(KID_CROSS, 0);   // row normalised
   if (sizeof(T) != 2) proj.load(hp, row0);
+  if constexpr (kEarlyKV) first.issue(kb, vb, wid * 8 + g, p.L, 8 * NW);
   proj.apply(xn, qs, WH ? p.q_bias : nullptr, row0);
   __syncthreads();
   MH_STAMP(KID_CROSS, 1);   // query projected
@@ -1262,7 +1343,8 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
   const float ks = (F8 ? p.kscale[kvb * p.H + h] : 1.0f) * (WH ? p.scale : 1.0f), vs = F8 ? p.vscale[kvb * p.H + h] : 1.0f;
   Partial st;
   partial_init(st);
-  attend_keys<T, U, E>(st, q, kb, vb, wid * 8 + g, p.L, 8 * NW, nullptr, 0, nullptr, 0, ks);
+  attend_keys<T, U, E, false, false, kEarlyKV>(st, q, kb, vb, wid * 8 + g, p.L, 8 * NW, nullptr, 0, nullptr, 0, ks, 0, nullptr, nullptr,
+                                               nullptr, 0, &first);
   MH_STAMP(KID_CROSS, 2);   // keys streamed (this wave)
   partial_merge_groups<T>(st);
   float m, l, a;
