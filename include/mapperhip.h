@@ -633,6 +633,65 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
                         const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
                         void* stream, void* self_kv_fp8, const MhRowSampling* rows, const uint8_t* eos_tables, int n_eos_sets);
 
+/* In-flight decode: S slots, every slot a row that decodes a window of its OWN -- its own prompt, position, settings and end -- so
+ * that a finished row's place goes to the next window while its neighbours keep stepping (additive at ABI 11: symbols only, the
+ * session is an opaque handle, no struct).  No reference counterpart: the reference decodes one window per call.  Opt-in; the other
+ * entries run the kernels, graphs and results they always did.
+ * What a slot computes: the batch-1 call mh_t5_generate_rows(B = 1, the window's unpadded prompt and mask, rows[slot]) -- token ids
+ *   up to the row's end and its rows of logits_dump, bit for bit (rows are batch-invariant).  The slot sits at its own columns
+ *   0 .. n: no left padding, RoPE rows / learned positions / the relative bias are those of the row's own position.
+ * Kernels: the token step of mh_t5_generate_rows with two kernels in their slot form (csrc/decode_kernels.hpp, csrc/t5.hip): the
+ *   self-attention reads the position of row b from an int32 [S] array (negative: the slot is idle and its workgroups return before
+ *   they store anything), the sampler reads and advances that position, the row's prompt length, pos_off, the parity of its score
+ *   history and its row of logits_dump; a row that is done writes its finish column, sets its flag and stops (no pad ids, the
+ *   position moves no further).  The GEMVs, the fused tail and the cross-attention are row-independent and run as they are: an idle
+ *   slot's rows of their outputs hold anything and are never read; its cross K/V row is still streamed.
+ * Chains: mh_t5_decode_chains_cfg(cfg, S) static row blocks (slot s belongs to chain s / ceil(S / chains)), one control block and one
+ *   captured step each, kept in the step-graph cache under a key that holds the slot arrays.
+ * mh_t5_slots_workspace_bytes: bytes of the session's workspace (the decode workspace of S rows, the slot arrays, the prompt prefill
+ *   of one row); -1 for S outside [1, 64].
+ * mh_t5_slots_open: the caller owns, for the life of the session, cfg, w, and the device buffers
+ *     rows            S MhRowSampling entries, read by every step: rows[slot] is the caller's to fill BEFORE admit(slot) and to
+ *                     leave alone while the slot is live
+ *     eos_tables      uint8 [n_eos_sets][vocab_out]
+ *     cross_kv_slots  [n_dec][2][S][H][L][64] cfg.dtype: row `slot` is filled by admit
+ *     tokens          int32 [S][sp->max_length]: row `slot` = the prompt, then the produced ids (nothing behind the row's end)
+ *     logits_dump     optional fp32 [sp->max_length][S][vocab_out]
+ *     workspace       mh_t5_slots_workspace_bytes(cfg, S) bytes
+ *   sp: the per-call settings, read as in mh_t5_generate_rows (max_length = the stride of `tokens`).  `forced` and `self_kv_fp8` exist
+ *   to be refused.  Refused with MH_ERR_ARG and a message before any launch: S outside [1, 64], sp->cfg_scale > 1 (guidance), forced
+ *   ids, sp->cross_kv_fp8, a shadow cache, sp->n_cond > 0 with cond_per_row == 0, and whatever mh_t5_generate_rows refuses.
+ *   `stream`: the work so far on it is what the session starts behind.  *handle: the session.
+ * mh_t5_slots_admit: slot must be idle (MH_ERR_ARG otherwise).  On the session's admission stream, behind `stream` (the caller's
+ *   work that wrote the arguments; may be NULL) and behind the slot's release: copies the window's compact cross K/V
+ *   [n_dec][2][1][H][L][64] into the slot, the prompt (device int32 [P]) into tokens[slot], the mask (device uint8 [P], NULL = ones)
+ *   into the slot's mask row; runs the batched prompt prefill with B = 1 into the slot's cache rows (positions 0 .. P-2; nothing under
+ *   option decode_prefill = 0, where the prompt is fed token by token); then the one-row init.  Returns without waiting: cross_kv_row,
+ *   prompt and prompt_mask must stay valid until the next mh_t5_slots_run returns.  The chain of the slot waits for the admission's
+ *   event before the step that first sees the slot live; the other chain steps on.
+ * mh_t5_slots_run: every chain with a live slot replays its step up to n_steps times (a poll every poll_every steps; it stops when
+ *   no row of the chain is running), then ONE poll per chain returns, for every slot, finished_out[slot] (uint8, host) and
+ *   length_out[slot] (int32, host: valid columns of tokens[slot] -- the finish column + 1 of a finished slot, the columns so far of a
+ *   running one, 0 for an idle one); *steps_out (optional): graph replays of this call, summed over the chains.  The chains are idle
+ *   when it returns.  The bounded hand-offs of the fused tail are reported as by mh_t5_generate (MH_ERR_DECODE_TAIL_TIMEOUT); their
+ *   counters restart at zero with every call, so no session length can wrap them.  The early-stop poll happens between bursts of
+ *   poll_every steps: a call of n_steps <= poll_every replays all its steps.
+ * mh_t5_slots_release: the slot (live: MH_ERR_ARG otherwise; finished or not) becomes idle, on its chain's stream behind its last
+ *   step; the caller reads tokens[slot] before it admits the next window there.
+ * mh_t5_slots_close: joins the chains and the admissions, releases the graph references, frees the session.
+ * Ordering is by events alone (release -> admit -> first step): nothing on the device spins or waits for another launch.  One host
+ * thread per session.  Not built: guidance pairs, beams, the e4m3 caches, teacher forcing, several rows per admission. */
+int64_t mh_t5_slots_workspace_bytes(const MhT5Config* cfg, int S);
+int mh_t5_slots_open(const MhT5Config* cfg, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                     const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                     const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                     void* stream, void** handle);
+int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
+                      void* stream);
+int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out, int32_t* length_out, int32_t* steps_out);
+int mh_t5_slots_release(void* handle, int slot);
+int mh_t5_slots_close(void* handle);
+
 /* (ABI 10) One beam-search step between two decoder positions as ONE kernel (csrc/beam.hip).  Replaces the per-step body of HF
  * `GenerationMixin._beam_search` (third-party, transformers >= 4.50's vectorised form) as the reference reaches it with
  * `num_beams > 1` (osuT5/osuT5/inference/processor.py:147,159; server.py:137; super_timing_generator.py:28 decodes with two beams):

@@ -197,6 +197,14 @@ SYMBOLS = {
                                 C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP, VP]),
     "mh_t5_generate_rows": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, VP, VP, I, VP,
                                 C.POINTER(MhSampling), VP, VP, VP, VP, VP, I64, I, VP, VP, VP, VP, I]),
+    # in-flight decode: a session of S slots behind an opaque handle (no struct of its own)
+    "mh_t5_slots_workspace_bytes": (I64, [C.POINTER(MhT5Config), I]),
+    "mh_t5_slots_open": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), I, C.POINTER(MhSampling), VP, VP, I, VP, VP, VP, VP, VP,
+                             VP, I64, I, VP, C.POINTER(VP)]),
+    "mh_t5_slots_admit": (I, [VP, I, VP, VP, VP, I, VP]),
+    "mh_t5_slots_run": (I, [VP, I, VP, VP, C.POINTER(I)]),
+    "mh_t5_slots_release": (I, [VP, I]),
+    "mh_t5_slots_close": (I, [VP]),
     "mh_quantize_kv_rows": (I, [VP, I64, VP, VP, VP]),
     "mh_t5_decode_self_cache": (I, [C.POINTER(MhT5Config), I, VP, C.POINTER(VP), C.POINTER(VP)]),
     "mh_t5_step": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), VP, I, I, VP, I, VP, I, VP, VP, I64, VP]),

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -485,6 +486,10 @@ struct SampleP {
 // dec_sample_kernel's trailing argument: the row settings of mh_t5_generate_rows (the ROWS instantiations), or nothing
 struct RowSetP { const MhRowSampling* rows; const uint8_t* eos_tables; int n_eos_sets; };
 struct NoRowSetP {};
+// ... or those of an in-flight decode (the SLOT instantiation, mh_t5_slots_*): the row settings, and what is the row's own there instead
+// of the call's -- pos [S]: the position slot b is fed at this step (negative: the slot is idle), advanced by the row's own workgroup;
+// plen [S]: the slot's prompt length.  Both are indexed by the global row.
+struct SlotSetP : RowSetP { int32_t* pos; const int32_t* plen; };
 struct RowVals {   // one entry as the sampler holds it (scalars: no indexed member, nothing that would live in scratch)
   float temperature, cond_temp0, cond_temp1, cond_temp2, top_p, timeshift_bias, cfg_scale;
   int cond_mask, top_k, lookback_mask_end, max_length, eos_set;
@@ -544,6 +549,80 @@ __global__ __launch_bounds__(256) void dec_init_kernel(SampleP p, int chain_rows
   for (int i = threadIdx.x; i < p.d; i += 256) p.h[(long)lb * p.d + i] = Elem<T>::to_f32(e[i]) + (pe ? pe[i] : 0.f);
 }
 
+// The same for ONE slot of an in-flight decode (mh_t5_slots_admit), row b of the slot buffers: the time-shift state over the prompt
+// columns 0 .. start_pos, finished / finish_col, pos_off (the mask row has the stride of `tokens`: ones behind the prompt), the prompt
+// length, the embedding of the token at start_pos -- and LAST the position, which is what makes the slot live for the token steps (the
+// chain waits for the admission's event before the step that first reads it, so the order inside this kernel is belt and braces).
+template <typename T>
+__global__ __launch_bounds__(256) void dec_slot_init_kernel(SampleP p, int b, int P, int start_pos, int32_t* slot_pos, int32_t* slot_plen) {
+  const int lb = b - p.b0;
+  __shared__ int s_off;
+  if (threadIdx.x == 0) {
+    int32_t v = -1;
+    for (int i = 0; i <= start_pos; ++i) v = next_ts_state(p.sp, p.tokens[(long)b * p.max_length + i], v);
+    p.last_ts_val[b] = v;
+    p.finish_col[b] = p.max_length - 1;
+    slot_plen[b] = P;
+    int off = 0;
+    if (p.pos_off) {
+      for (int i = 0; i < P; ++i) off += p.prompt_mask[(long)b * p.max_length + i] == 0;
+      p.pos_off[b] = off;
+    }
+    s_off = off;
+  }
+  __syncthreads();
+  const int tok = p.tokens[(long)b * p.max_length + start_pos];
+  const T* e = reinterpret_cast<const T*>(p.dec_embed) + (long)tok * p.d;
+  const float* pe = p.dec_pos ? p.dec_pos + (long)(start_pos - s_off > 0 ? start_pos - s_off : 0) * p.d : nullptr;
+  for (int i = threadIdx.x; i < p.d; i += 256) p.h[(long)lb * p.d + i] = Elem<T>::to_f32(e[i]) + (pe ? pe[i] : 0.f);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    p.finished[b] = 0;
+    slot_pos[b] = start_pos;
+  }
+}
+
+// Step bookkeeping without a launch of its own: every workgroup read `pos` when it started, so the one that arrives
+// last may advance it; it also recounts the running rows for the host's early-stop poll.  The `finished` flags are
+// agent-scope stores drained before the ticket is taken and agent-scope loads here (write-through hand-off, no
+// fence); a stale flag could only delay the early stop by a poll, never change a token.
+// The recount is ONE round trip of the last workgroup's first wave (lane i reads row i's flag), not chain_rows serial ones.
+// SLOT: every row advances its own position (the sampler); the last workgroup only recounts (an idle slot keeps its flag set).
+template <bool SLOT>
+__device__ __forceinline__ void sample_arrive(const SampleP& p, int pos, int* s_is_last) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (tid == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int t = __hip_atomic_fetch_add(&p.st->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *s_is_last = t == (int)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (*s_is_last && wid == 0) {
+    int run = 0;
+    for (int i0 = 0; i0 < p.chain_rows; i0 += 64) {
+      const int i = i0 + lane;
+      const bool running = i < p.chain_rows &&
+                           __hip_atomic_load(&p.finished[p.b0 + (i < p.chain_rows ? i : 0)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+      run += __popcll(__ballot(running));
+    }
+    if (lane == 0) {
+      __hip_atomic_store(&p.st->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dec::store_wt(&p.st->n_running, run);
+      if (!SLOT) dec::store_wt(&p.st->pos, pos + 1);
+    }
+  }
+}
+
+template <bool SLOT, typename RS> __device__ __forceinline__ int sample_pos(const SampleP& p, const RS& rs, int b) {
+  if constexpr (SLOT) return rs.pos[b];
+  else return p.st->pos;
+}
+template <bool SLOT, typename RS> __device__ __forceinline__ int sample_plen(const RS& rs, int b) {
+  if constexpr (SLOT) return rs.plen[b];
+  else return 0;
+}
+
 constexpr int kSampleRegs = 16;   // the register sampling path holds up to 16 ids per thread: vocabularies of <= 4096 ids
 
 // One workgroup per returned row (per CFG pair): processors -> selection -> bookkeeping -> next-token embedding.
@@ -551,8 +630,15 @@ constexpr int kSampleRegs = 16;   // the register sampling path holds up to 16 i
 // LookbackBias, then HF's own top-k / top-p warpers and the multinomial draw.
 // ROWS (mh_t5_generate_rows): temperature, the conditional temperatures and their mask, top-k / top-p, the time-shift bias, the
 // lookback end, the length cap, the EOS set, the RNG key and the guidance scale come from rs.rows[returned row] instead of p.sp
-template <typename T, bool ROWS = false>
-__global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std::conditional<ROWS, RowSetP, NoRowSetP>::type rs) {
+// SLOT (mh_t5_slots_*, on top of ROWS): every row is a slot with a window of its own.  The row's own, from rs.pos / rs.plen and the
+// buffers indexed by the row: its position and column, its prompt length (the "still inside the prompt" branch under option
+// decode_prefill = 0), pos_off (arch 2), the parity of hist_scores, its row of logits_dump [max_length][S][V].  A row that is done (an
+// id of its EOS set, or its max_length) writes its finish column, sets its flag and stops: no pad ids afterwards, its position moves no
+// further.  An idle slot (negative position) does nothing.  The last-arriving workgroup recounts n_running and advances nothing.  No
+// guidance (pair = 0) and cond_per_row = 1: checked on the host.
+template <typename T, bool ROWS = false, bool SLOT = false>
+__global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std::conditional<SLOT, SlotSetP, typename std::conditional<ROWS, RowSetP, NoRowSetP>::type>::type rs) {
+  static_assert(!SLOT || ROWS, "the slot form always reads rs.rows");
   __shared__ float sf[8];
   __shared__ int si[8];
   __shared__ float s3[12];
@@ -599,19 +685,27 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
   }
   const bool was_finished = p.finished[b] != 0;
   const int ltv = p.last_ts_val[b];
-  const int pos = p.st->pos;
+  const int pos = sample_pos<SLOT>(p, rs, b);   // the position fed this step: the call's, or (SLOT) the row's own
+  const int plen = sample_plen<SLOT>(rs, b);
+#define MH_PROMPT_LEN (SLOT ? plen : p.P)     // the prompt length: the call's, or (SLOT) the row's own
   const int col = pos + 1;  // column being produced
   const MhSampling& sp = p.sp;
   // a per-row setting where it is used: the row's value, or the very expression the uniform form always had
 #define MH_ROWV(f) (ROWS ? row.f : sp.f)
-  if (col >= p.max_length) return;
+  if constexpr (SLOT) {
+    // an idle slot, or a row that is done and waits to be taken: only the step's arrival (workgroup-uniform: one word each)
+    if (pos < 0 || was_finished || col >= p.max_length) { sample_arrive<true>(p, pos, &s_is_last); return; }
+  } else {
+    if (col >= p.max_length) return;
+  }
   int nxt[2] = {0, 0};      // the ids the next step is fed (row b, and under guidance its negative-prompt row)
 
-  if (col < p.P) {
+  if (col < MH_PROMPT_LEN) {
     // still inside the prompt: the token is given; only advance the processor state + embedding
     nxt[0] = p.tokens[(long)b * p.max_length + col];
     if (cfg) nxt[1] = p.tokens[(long)bneg * p.max_length + col];
     if (tid == 0) dec::store_wt(&p.last_ts_val[b], next_ts_state(sp, nxt[0], ltv));
+    if constexpr (SLOT) { if (tid == 0) dec::store_wt(&rs.pos[b], pos + 1); }
   } else {
     if (tid == 0) {
       // ConditionalTemperatureLogitsWarper: the lookback is ROW 0's history for the whole batch
@@ -628,7 +722,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
       }
       s_temp = temp;
       // LookbackBiasLogitsWarper types_first: "the scores are for a timeshift event" when the last id is a timed event
-      s_timed = (sp.lookback_types_first && col > p.P) ? (sp.tok_flags[history_id(p, b, col - 1)] & 1) : 0;
+      s_timed = (sp.lookback_types_first && col > MH_PROMPT_LEN) ? (sp.tok_flags[history_id(p, b, col - 1)] & 1) : 0;
     }
     __syncthreads();
     const float temp = s_temp;
@@ -933,6 +1027,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
         }
       }
       dec::store_wt(&p.last_ts_val[b], next_ts_state(sp, nxt[0], ltv));
+      if constexpr (SLOT) { if (!done) dec::store_wt(&rs.pos[b], pos + 1); }   // (a row that is done stays where it ended)
     }
   }
   // embedding of the token that the next step consumes (decoder_embedder, modeling_mapperatorinator.py:205-206)
@@ -947,34 +1042,11 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
       dec::store_piece_wt<float>(p.h + (long)lrow * p.d + i, v4, 4, 4);
     }
   }
-  // Step bookkeeping without a launch of its own: every workgroup read `pos` when it started, so the one that arrives
-  // last may advance it; it also recounts the running rows for the host's early-stop poll.  The `finished` flags are
-  // agent-scope stores drained before the ticket is taken and agent-scope loads here (write-through hand-off, no
-  // fence); a stale flag could only delay the early stop by a poll, never change a token.
-  // The recount is ONE round trip of the last workgroup's first wave (lane i reads row i's flag), not chain_rows serial ones.
-  if (tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(&p.st->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_is_last = t == (int)gridDim.x - 1;
-  }
-  __syncthreads();
-  if (s_is_last && wid == 0) {
-    int run = 0;
-    for (int i0 = 0; i0 < p.chain_rows; i0 += 64) {
-      const int i = i0 + lane;
-      const bool running = i < p.chain_rows &&
-                           __hip_atomic_load(&p.finished[p.b0 + (i < p.chain_rows ? i : 0)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
-      run += __popcll(__ballot(running));
-    }
-    if (lane == 0) {
-      __hip_atomic_store(&p.st->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      dec::store_wt(&p.st->n_running, run);
-      dec::store_wt(&p.st->pos, pos + 1);
-    }
-  }
+  sample_arrive<SLOT>(p, pos, &s_is_last);
 }
 
 #undef MH_ROWV
+#undef MH_PROMPT_LEN
 
 __global__ void dec_finalize_kernel(const int32_t* finish_col, int B, int32_t* n_steps_out) {
   if (threadIdx.x == 0) {
@@ -1153,10 +1225,19 @@ DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
 // the F8 + IDX one: the shadow rows and their scales through the same table (mh_t5_step_indexed_skv8)
 template <typename T, int KC>
 int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8,
-                    const uint8_t* origin = nullptr) {
+                    const uint8_t* origin = nullptr, const int32_t* slot_pos = nullptr) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d && inner == sa.H * 64, "decode: dense residual rows / projection weights expected");
   const dec::NoSelfKv8P no8{};
-  if (origin && f8) {   // both: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
+  if (slot_pos) {   // slot_pos != NULL: the SLOT instantiation, every row at its own position (mh_t5_slots_*): the plain caches only
+    MH_REQUIRE(!origin && !f8, "decode: the slot form of the self-attention has no e4m3 and no indexed cache");
+    const dec::SelfSlotP sl{slot_pos};
+    if (sa.rope && hp.ln_b)
+      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
+    else if (sa.rope)
+      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
+    else
+      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
+  } else if (origin && f8) {   // both: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
     MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
                dec::kSelfIdxMaxTgt, sa.tgt_len);
     if constexpr (sizeof(T) == 2) {
@@ -1243,6 +1324,8 @@ struct StepCall {
   int has_rows; RowSetP rows;            // has_rows: the sampler reads its settings per returned row (mh_t5_generate_rows)
   unsigned long long* timing_buf; int timing_ring;   // the timing hook as it stood when the call was built
   const uint8_t* origin;                 // beam search by index (mh_t5_step_indexed): uint8 [Bfull][tgt_len], else NULL
+  int32_t* slot_pos; const int32_t* slot_plen;   // in-flight decode (mh_t5_slots_*): the positions and prompt lengths of all Bfull slots
+                                                 // (global row index; the SLOT kernels), else NULL.  Needs has_rows.
 };
 static_assert(std::is_trivially_copyable<StepCall>::value, "StepCall is keyed by its bytes");
 void step_call_init(StepCall* k, const MhT5Config* c, const MhT5Weights* w) {
@@ -1317,7 +1400,9 @@ int enqueue_step(const StepCall& k, hipStream_t s) {
       f8.ks = bf.self8_scales + self8.scale(l, 0); f8.vs = bf.self8_scales + self8.scale(l, 1);
     }
     const dec::HeadProjP qkv = head_proj(c, bf.h, w->dec_ln1[l], hf ? w->dec_ln1_b[l] : nullptr, w->dec_qkv[l]);
-    MH_TRY(dispatch_kc(qkv.d, [&](auto kc) { return launch_self_qkv<T, decltype(kc)::value>(sa, qkv, inner, s, bf.self8 ? &f8 : nullptr, k.origin); }));
+    MH_TRY(dispatch_kc(qkv.d, [&](auto kc) {
+      return launch_self_qkv<T, decltype(kc)::value>(sa, qkv, inner, s, bf.self8 ? &f8 : nullptr, k.origin, k.slot_pos ? k.slot_pos + k.smp.b0 : nullptr);
+    }));
     MH_TRY(skinny_resid<T>(o_gemv(k, w->dec_o[l], w->dec_o_b[l]), s));
     // cross attention (+ query projection)
     dec::CrossAttnP ca = cross_attn(c, k.cross_kv, kvB, l, bf.attn, B);
@@ -1356,7 +1441,12 @@ int enqueue_step(const StepCall& k, hipStream_t s) {
   else MH_TRY((skinny<T, dec::PRO_RMSNORM, dec::SK_LOGITS>(sk, s)));
   if (!k.with_sampler) return MH_OK;
   const SampleP& smp = k.smp;
-  if (k.has_rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, k.rows);
+  if (k.slot_pos) {
+    MH_REQUIRE(k.has_rows && smp.pair == 0, "decode: the slot form of the sampler reads row settings and has no guidance");
+    SlotSetP ss{};
+    ss.rows = k.rows.rows; ss.eos_tables = k.rows.eos_tables; ss.n_eos_sets = k.rows.n_eos_sets; ss.pos = k.slot_pos; ss.plen = k.slot_plen;
+    hipLaunchKernelGGL((dec_sample_kernel<T, true, true>), dim3(B), dim3(256), 0, s, smp, ss);
+  } else if (k.has_rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, k.rows);
   else hipLaunchKernelGGL((dec_sample_kernel<T, false>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, NoRowSetP{});
   return check_launch("dec_sample_kernel");
 }
@@ -1829,6 +1919,7 @@ struct Chain {
 
 // A chain enters the call on its own stream, behind the caller's work so far (`fork`): dec_init_kernel, then one step of the chain (every
 // kernel reads the position from device memory) as a graph for replay: an earlier call's, if its key is this one's, else captured now
+static int chain_step_graph(const StepCall& call, const char* who, Chain* ch);
 static int start_chain(const StepCall& call, int start_pos, hipEvent_t fork, const char* who, Chain* ch) {
   hipStream_t cs = ch->stream;
   ch->st = call.bf.st;
@@ -1836,6 +1927,11 @@ static int start_chain(const StepCall& call, int start_pos, hipEvent_t fork, con
   if (call.c->dtype == MH_BF16) hipLaunchKernelGGL(dec_init_kernel<bf16_t>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
   else hipLaunchKernelGGL(dec_init_kernel<float>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
   MH_TRY(check_launch("dec_init_kernel"));
+  return chain_step_graph(call, who, ch);
+}
+// One step of the chain as a graph for replay on ch->stream: an earlier call's, if its key is this one's, else captured now
+static int chain_step_graph(const StepCall& call, const char* who, Chain* ch) {
+  hipStream_t cs = ch->stream;
   std::vector<unsigned char> key;
   if (option(OPT_DECODE_GRAPH_CACHE) != 0) {
     key = step_graph_key(call);
@@ -1911,29 +2007,35 @@ struct GenerateArgs {
   void* workspace; int64_t workspace_bytes; int poll_every; void* stream; void* self_kv_fp8; const RowSetP* rowset; const char* who;
 };
 
-static int check_generate_args(const GenerateArgs& a) {
-  const MhT5Config* c = a.c;
-  const MhSampling* sp = a.sp;
-  const char* who = a.who;
+// What every entry that runs the sampled token step checks of its configuration and settings, in this order (ptrs_ok: the entry's own
+// pointer arguments are all there; P: the call's prompt length, or NULL where every row brings its own -- mh_t5_slots_admit checks it)
+static int check_decode_call(const MhT5Config* c, const MhT5Weights* w, const MhSampling* sp, int B, bool ptrs_ok, void* stream,
+                             const int* P, bool rows, const char* who) {
   MH_TRY(check_cfg(c, who));
   MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(a.w && a.cross_kv && a.prompt && (a.eos_table || a.rowset) && sp && a.tokens && a.n_steps_out && a.workspace,
-             "%s: null argument", who);
-  MH_REQUIRE(a.stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
-  MH_REQUIRE(a.B > 0 && a.B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, a.B);
-  MH_REQUIRE(a.P >= 1 && a.P < sp->max_length, "%s: prompt length %d must be in [1, max_length)", who, a.P);
+  MH_REQUIRE(w && sp && ptrs_ok, "%s: null argument", who);
+  MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
+  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, B);
+  MH_REQUIRE(!P || (*P >= 1 && *P < sp->max_length), "%s: prompt length %d must be in [1, max_length)", who, P ? *P : 0);
+  MH_REQUIRE(sp->max_length >= 2, "%s: max_length %d must be >= 2", who, sp->max_length);
   MH_REQUIRE(sp->max_length <= c->tgt_len, "%s: max_length %d exceeds tgt_len %d", who, sp->max_length, c->tgt_len);
-  MH_REQUIRE(a.rowset || sp->temperature > 0.f, "%s: temperature must be > 0", who);
+  MH_REQUIRE(rows || sp->temperature > 0.f, "%s: temperature must be > 0", who);
   MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "%s: too many sos ids", who);
-  MH_REQUIRE(!(sp->cfg_scale > 1.0f) || a.B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
+  MH_REQUIRE(!(sp->cfg_scale > 1.0f) || B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
   MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "%s: n_cond %d not in [0, 3]", who, sp->n_cond);
   for (int j = 0; j < sp->n_cond; ++j)
-    MH_REQUIRE((a.rowset || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
+    MH_REQUIRE((rows || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
   MH_REQUIRE(sp->tok_flags || (sp->n_cond == 0 && !sp->lookback_types_first),
              "%s: tok_flags is required by the conditional temperature / types_first lookback processors", who);
   MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
-  MH_REQUIRE(a.workspace_bytes >= mh_t5_decode_workspace_bytes(c, a.B), "%s: workspace too small", who);
-  return check_arch2_weights(c, a.w, who);
+  return MH_OK;
+}
+
+static int check_generate_args(const GenerateArgs& a) {
+  const bool ptrs_ok = a.cross_kv && a.prompt && (a.eos_table || a.rowset) && a.tokens && a.n_steps_out && a.workspace;
+  MH_TRY(check_decode_call(a.c, a.w, a.sp, a.B, ptrs_ok, a.stream, &a.P, a.rowset != nullptr, a.who));
+  MH_REQUIRE(a.workspace_bytes >= mh_t5_decode_workspace_bytes(a.c, a.B), "%s: workspace too small", a.who);
+  return check_arch2_weights(a.c, a.w, a.who);
 }
 
 // Chain ci of the call as a StepCall: rows [ci rows_per, + Bc) of every buffer, of the e4m3 copies and of the sampler's view
@@ -2112,6 +2214,308 @@ extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, co
   const mh::RowSetP rowset{rows, eos_tables, n_eos_sets};
   return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
                         workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, "mh_t5_generate_rows"});
+}
+
+// ------------------------------------------------------------------------------------------------
+// In-flight decode (mh_t5_slots_*; contract in include/mapperhip.h): S slots, every slot a row with a window of its own that enters
+// (admit) and leaves (release) while its neighbours keep stepping.  The chains are those of mh_t5_generate_rows over S rows -- the
+// same static row blocks, one DecState and one step graph each (the SLOT kernels: the key holds StepCall::slot_pos) -- on streams
+// the session owns; admissions run on a stream of their own.
+//
+// Why no step can write a cache row, a token or a state word that an admission is filling, and no admission one that a step reads:
+//   * an idle slot's position is negative: its self-attention workgroups return before they store, its sampler workgroup only
+//     arrives; the GEMVs, the tail and the cross-attention write the slot's rows of h / attn / ff / logits, which nothing reads;
+//   * release(slot) makes the position negative ON THE CHAIN'S STREAM, behind the slot's last step, and records freed[slot] there;
+//   * admit(slot) waits for freed[slot] on the admission stream before its first write, and the slot's position -- the one word that
+//     makes it live -- is the last thing its last kernel writes; then it records admitted[chain];
+//   * run() makes the chain's stream wait for admitted[chain] before the first step enqueued after the admission.
+// Events only: nothing on the device spins or waits for another launch.
+namespace mh {
+struct SlotSession {
+  const MhT5Config* c = nullptr; const MhT5Weights* w = nullptr;
+  int S = 0, n_chains = 0, rows_per = 0, dev = 0, max_length = 0, poll_every = 16;
+  DecodeLayout ly{};
+  int32_t* pos = nullptr; int32_t* plen = nullptr; uint8_t* mask = nullptr;   // [S], [S], [S][max_length]
+  char* prefill_base = nullptr; int64_t prefill_bytes = 0;
+  char* cross_kv = nullptr; int32_t* tokens = nullptr;
+  Chain chains[kMaxChains];
+  StepCall calls[kMaxChains];
+  hipStream_t admit_stream = nullptr;
+  hipEvent_t admitted[kMaxChains] = {}, freed[64] = {}, caller_ev = nullptr;
+  bool pending[kMaxChains] = {};    // an admission into the chain since its last step was enqueued
+  bool live[64] = {};               // admitted and not released
+  int32_t host_pos[64] = {}, host_col[64] = {}; uint8_t host_fin[64] = {};
+  ~SlotSession() {
+    // joins the chains and the admissions (a graph object must outlive its launches; the Chain members release theirs after this body)
+    if (admit_stream) { (void)hipStreamSynchronize(admit_stream); (void)hipStreamDestroy(admit_stream); }
+    for (int i = 0; i < kMaxChains; ++i) {
+      if (chains[i].stream) { (void)hipStreamSynchronize(chains[i].stream); (void)hipStreamDestroy(chains[i].stream); }
+      if (admitted[i]) (void)hipEventDestroy(admitted[i]);
+    }
+    for (int i = 0; i < 64; ++i) if (freed[i]) (void)hipEventDestroy(freed[i]);
+    if (caller_ev) (void)hipEventDestroy(caller_ev);
+  }
+  int chain_of(int slot) const { return slot / rows_per; }
+};
+struct SlotDeviceGuard {
+  int prev = -1;
+  explicit SlotDeviceGuard(int want) { if (hipGetDevice(&prev) == hipSuccess && prev != want) (void)hipSetDevice(want); else prev = -1; }
+  ~SlotDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+// the slot buffers behind the decode layout of S rows, then the prompt prefill of ONE row (an admission prefills one window)
+static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession* ss) {
+  const DecodeLayout ly = decode_layout(c, S, base);
+  Arena ar(base ? (char*)base + ly.end : nullptr, INT64_MAX);
+  int32_t* pos = (int32_t*)ar.take((int64_t)S * 4);
+  int32_t* plen = (int32_t*)ar.take((int64_t)S * 4);
+  uint8_t* mask = (uint8_t*)ar.take((int64_t)S * c->tgt_len);
+  const int64_t pre = prefill_layout(c, 1, c->tgt_len - 1, nullptr, 0, nullptr);
+  if (ss) {
+    ss->ly = ly; ss->pos = pos; ss->plen = plen; ss->mask = mask;
+    ss->prefill_base = (char*)base + ly.end + ar.off; ss->prefill_bytes = pre;
+  }
+  return ly.end + ar.off + pre;
+}
+// up to n_steps replays of one chain, a poll every poll_every (none behind the last burst): stops when no row of the chain runs
+static void slots_run_chain(const Chain& ch, int n_steps, int poll_every, int* rc, int* steps) {
+  for (int step = 0; step < n_steps && *rc == MH_OK;) {
+    const int burst = n_steps - step < poll_every ? n_steps - step : poll_every;
+    for (int i = 0; i < burst && *rc == MH_OK; ++i) {
+      if (hipGraphLaunch(ch.exec, ch.stream) != hipSuccess) *rc = MH_ERR_LAUNCH;
+      else ++*steps;
+    }
+    step += burst;
+    bool running = true;
+    if (step < n_steps && *rc == MH_OK) *rc = poll_chain(ch, &running);
+    if (!running) break;
+  }
+}
+}  // namespace mh
+
+extern "C" int64_t mh_t5_slots_workspace_bytes(const MhT5Config* c, int S) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  if (!c || S < 1 || S > 64) return -1;
+  return mh::slots_layout(c, S, nullptr, nullptr);
+}
+
+extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                                const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                                const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                                void* stream, void** handle) {
+  using namespace mh;
+  OptionScope option_scope(c ? c->options : nullptr);
+  const char* who = "mh_t5_slots_open";
+  MH_TRY(check_cfg(c, who));
+  MH_REQUIRE(handle, "%s: null argument (handle)", who);
+  *handle = nullptr;
+  MH_REQUIRE(S >= 1 && S <= 64, "%s: %d slots not in [1, 64]", who, S);
+  MH_REQUIRE(rows && eos_tables, "%s: null argument (rows: one MhRowSampling per slot; eos_tables: [n_eos_sets][vocab_out])", who);
+  MH_REQUIRE(n_eos_sets >= 1, "%s: n_eos_sets %d must be >= 1", who, n_eos_sets);
+  MH_REQUIRE(sp, "%s: null argument (sp)", who);
+  MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
+  MH_REQUIRE(!forced, "%s: teacher forcing (forced ids) has no slot form", who);
+  MH_REQUIRE(!sp->cross_kv_fp8, "%s: the e4m3 copy of the cross K/V (cross_kv_fp8) has no slot form", who);
+  MH_REQUIRE(!self_kv_fp8, "%s: the e4m3 shadow of the self-attention cache has no slot form", who);
+  MH_REQUIRE(sp->n_cond == 0 || sp->cond_per_row, "%s: conditional temperature rules need cond_per_row = 1 (every slot is a window of its own)", who);
+  // whatever mh_t5_generate_rows refuses of a configuration and its settings (the prompt length is each admission's)
+  MH_TRY(check_decode_call(c, w, sp, S, cross_kv_slots && tokens && workspace, stream, nullptr, true, who));
+  MH_REQUIRE(workspace_bytes >= slots_layout(c, S, nullptr, nullptr), "%s: workspace too small (mh_t5_slots_workspace_bytes)", who);
+  MH_TRY(check_arch2_weights(c, w, who));
+  hipStream_t s = (hipStream_t)stream;
+  int dev = 0;
+  if (hipStreamGetDevice(s, &dev) != hipSuccess) { (void)hipGetLastError(); if (hipGetDevice(&dev) != hipSuccess) return check_launch("hipGetDevice"); }
+  SlotDeviceGuard device_guard(dev);
+  std::unique_ptr<SlotSession> ss(new SlotSession());
+  ss->c = c; ss->w = w; ss->S = S; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
+  ss->cross_kv = (char*)cross_kv_slots; ss->tokens = tokens;
+  slots_layout(c, S, workspace, ss.get());
+  ss->n_chains = pick_chains(S);
+  ss->rows_per = ceil_div(S, ss->n_chains);
+  // every slot idle: position -1, flag set (the recount of n_running counts clear flags); the chains' control blocks zero
+  if (hipMemsetAsync(ss->pos, 0xff, (size_t)S * 4, s) != hipSuccess || hipMemsetAsync(ss->plen, 0, (size_t)S * 4, s) != hipSuccess ||
+      hipMemsetAsync(ss->ly.bf.finished, 1, (size_t)S, s) != hipSuccess ||
+      hipMemsetAsync(ss->mask, 1, (size_t)S * sp->max_length, s) != hipSuccess ||
+      hipMemsetAsync(ss->ly.bf.st, 0, (size_t)align256(sizeof(DecState)) * kMaxChains, s) != hipSuccess)
+    return check_launch("slot state memset");
+  if (hipStreamCreateWithFlags(&ss->admit_stream, hipStreamNonBlocking) != hipSuccess) return check_launch("slot stream create");
+  for (int b = 0; b < S; ++b) {
+    if (hipEventCreateWithFlags(&ss->freed[b], hipEventDisableTiming) != hipSuccess) return check_launch("slot event create");
+    if (hipEventRecord(ss->freed[b], s) != hipSuccess) return check_launch("slot event record");
+  }
+  const RowSetP rowset{rows, eos_tables, n_eos_sets};
+  GenerateArgs a{c, w, cross_kv_slots, S, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
+                 workspace_bytes, poll_every, stream, nullptr, &rowset, who};
+  int used = 0;
+  for (int ci = 0; ci < ss->n_chains; ++ci) {
+    StepCall& call = ss->calls[ci];
+    chain_call(a, ss->ly, ci, ss->rows_per, nullptr, &call);   // prompt_mask: the slot mask rows, stride max_length (call.P)
+    if (call.Bc <= 0) break;
+    call.slot_pos = ss->pos; call.slot_plen = ss->plen;
+    Chain& ch = ss->chains[ci];
+    if (hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&ss->admitted[ci], hipEventDisableTiming) != hipSuccess)
+      return check_launch("slot stream create");
+    ch.st = call.bf.st;
+    if (hipStreamWaitEvent(ch.stream, ss->freed[0], 0) != hipSuccess) return check_launch("slot stream wait");   // behind the memsets
+    MH_TRY(chain_step_graph(call, who, &ch));
+    ++used;
+  }
+  ss->n_chains = used;
+  if (hipStreamSynchronize(s) != hipSuccess) return check_launch("slot open");
+  *handle = ss.release();
+  return MH_OK;
+}
+
+extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
+                                 void* stream) {
+  using namespace mh;
+  SlotSession* ss = (SlotSession*)handle;
+  const char* who = "mh_t5_slots_admit";
+  MH_REQUIRE(ss, "%s: null handle", who);
+  OptionScope option_scope(ss->c->options);
+  MH_REQUIRE(cross_kv_row && prompt, "%s: null argument", who);
+  MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
+  MH_REQUIRE(!ss->live[slot], "%s: slot %d is live (release it first)", who, slot);
+  MH_REQUIRE(P >= 1 && P < ss->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
+  SlotDeviceGuard device_guard(ss->dev);
+  const MhT5Config* c = ss->c;
+  const int ci = ss->chain_of(slot), es = es_of(c->dtype), H = c->n_heads, inner = H * 64;
+  hipStream_t as = ss->admit_stream;
+  if (hipStreamWaitEvent(as, ss->freed[slot], 0) != hipSuccess) return check_launch("admit wait");
+  if (stream) {   // the caller's stream wrote cross_kv_row / prompt / prompt_mask: the admission reads them behind that work
+    if (!ss->caller_ev && hipEventCreateWithFlags(&ss->caller_ev, hipEventDisableTiming) != hipSuccess) return check_launch("admit event create");
+    if (hipEventRecord(ss->caller_ev, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(as, ss->caller_ev, 0) != hipSuccess)
+      return check_launch("admit caller wait");
+  }
+  // the window's compact cross K/V [n_dec][2][1][H][L][64] -> row `slot` of [n_dec][2][S][H][L][64]
+  const size_t row_bytes = (size_t)H * c->src_len * 64 * es;
+  if (hipMemcpy2DAsync(ss->cross_kv + (size_t)slot * row_bytes, (size_t)ss->S * row_bytes, cross_kv_row, row_bytes, row_bytes,
+                       (size_t)c->n_dec_layers * 2, hipMemcpyDeviceToDevice, as) != hipSuccess)
+    return check_launch("admit cross K/V copy");
+  int32_t* trow = ss->tokens + (long)slot * ss->max_length;
+  uint8_t* mrow = ss->mask + (long)slot * ss->max_length;
+  if (hipMemcpyAsync(trow, prompt, (size_t)P * 4, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit prompt copy");
+  if (hipMemsetAsync(mrow, 1, (size_t)ss->max_length, as) != hipSuccess) return check_launch("admit mask set");
+  if (prompt_mask && hipMemcpyAsync(mrow, prompt_mask, (size_t)P, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit mask copy");
+  int start_pos = 0;
+  if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {   // positions 0 .. P-2 into the slot's cache rows: the B = 1 prefill of a uniform call
+    PrefillBuf pb;
+    prefill_layout(c, 1, P - 1, ss->prefill_base, ss->prefill_bytes, &pb);
+    const long cache_row = (long)slot * inner * c->tgt_len * es;
+    MH_TRY(prefill_prompt(c, ss->w, cross_kv_row, 1, 1, prompt, prompt_mask, P, P - 1, (char*)ss->ly.bf.self_k + cache_row,
+                          (char*)ss->ly.bf.self_v + cache_row, pb, as, ss->S));
+    start_pos = P - 1;
+  }
+  const SampleP& smp = ss->calls[ci].smp;
+  if (c->dtype == MH_BF16) hipLaunchKernelGGL(dec_slot_init_kernel<bf16_t>, dim3(1), dim3(256), 0, as, smp, slot, P, start_pos, ss->pos, ss->plen);
+  else hipLaunchKernelGGL(dec_slot_init_kernel<float>, dim3(1), dim3(256), 0, as, smp, slot, P, start_pos, ss->pos, ss->plen);
+  MH_TRY(check_launch("dec_slot_init_kernel"));
+  if (hipEventRecord(ss->admitted[ci], as) != hipSuccess) return check_launch("admit record");
+  ss->pending[ci] = true;
+  ss->live[slot] = true;
+  return MH_OK;
+}
+
+extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out, int32_t* length_out, int32_t* steps_out) {
+  using namespace mh;
+  SlotSession* ss = (SlotSession*)handle;
+  const char* who = "mh_t5_slots_run";
+  MH_REQUIRE(ss, "%s: null handle", who);
+  OptionScope option_scope(ss->c->options);
+  MH_REQUIRE(n_steps >= 0 && finished_out && length_out, "%s: bad argument", who);
+  SlotDeviceGuard device_guard(ss->dev);
+  int rcs[kMaxChains] = {}, steps[kMaxChains] = {};
+  bool runs[kMaxChains] = {};
+  int n_run = 0;
+  for (int b = 0; b < ss->S; ++b) if (ss->live[b]) runs[ss->chain_of(b)] = true;
+  for (int ci = 0; ci < ss->n_chains; ++ci) {
+    if (!runs[ci]) continue;
+    ++n_run;
+    // The fused tail's hand-off counters only ever grow inside a call, and a launch takes its base as a multiple of its grid: a
+    // session has no dec_init_kernel between its steps, so they start every run at zero (the chain is idle here: the last run
+    // ended with its poll) and cannot wrap however long the session lives.  tail_err stays: a timed-out session stays reported.
+    if (n_steps > 0 && hipMemsetAsync(ss->chains[ci].st->tail_cnt, 0, sizeof(ss->chains[ci].st->tail_cnt), ss->chains[ci].stream) != hipSuccess)
+      return check_launch("tail counter reset");
+    if (ss->pending[ci]) {   // the step that first sees the admitted slots live waits for their admissions
+      if (hipStreamWaitEvent(ss->chains[ci].stream, ss->admitted[ci], 0) != hipSuccess) return check_launch("admission wait");
+      ss->pending[ci] = false;
+    }
+  }
+  if (n_steps > 0) {
+    if (n_run <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
+      // (one launcher: the chains' bursts one after the other -- poll_every replays are enqueued far faster than they run)
+      for (int ci = 0; ci < ss->n_chains; ++ci)
+        if (runs[ci]) slots_run_chain(ss->chains[ci], n_steps, ss->poll_every, &rcs[ci], &steps[ci]);
+    } else {
+      std::vector<std::thread> th;
+      const MhOptionSet* set = current_option_set();
+      int first = -1;
+      for (int ci = 0; ci < ss->n_chains; ++ci) {
+        if (!runs[ci]) continue;
+        if (first < 0) { first = ci; continue; }
+        th.emplace_back([&, ci, set] { OptionScope sc(set); slots_run_chain(ss->chains[ci], n_steps, ss->poll_every, &rcs[ci], &steps[ci]); });
+      }
+      slots_run_chain(ss->chains[first], n_steps, ss->poll_every, &rcs[first], &steps[first]);
+      for (auto& t : th) t.join();
+    }
+  }
+  int rc = MH_OK, total = 0;
+  for (int ci = 0; ci < ss->n_chains; ++ci) {
+    total += steps[ci];
+    if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
+    else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
+  }
+  // one poll per chain: its rows' flags, finish columns and positions, and the bounded hand-offs' last word
+  for (int ci = 0; ci < ss->n_chains; ++ci) {
+    const int b0 = ci * ss->rows_per, n = ss->calls[ci].Bc;
+    hipStream_t cs = ss->chains[ci].stream;
+    int word[2] = {0, 0};
+    if (hipMemcpyAsync(ss->host_fin + b0, ss->ly.bf.finished + b0, (size_t)n, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipMemcpyAsync(ss->host_col + b0, ss->ly.bf.finish_col + b0, (size_t)n * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipMemcpyAsync(ss->host_pos + b0, ss->pos + b0, (size_t)n * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipMemcpyAsync(word, &ss->chains[ci].st->n_running, 8, hipMemcpyDeviceToHost, cs) != hipSuccess ||
+        hipStreamSynchronize(cs) != hipSuccess)
+      return check_launch("slot poll");
+    if (rc == MH_OK && word[1] != 0) rc = mh_t5_decode_tail_status(word[1]);
+  }
+  for (int b = 0; b < ss->S; ++b) {
+    const bool fin = ss->live[b] && ss->host_fin[b] != 0;
+    finished_out[b] = fin ? 1 : 0;
+    length_out[b] = !ss->live[b] ? 0 : (fin ? ss->host_col[b] + 1 : ss->host_pos[b] + 1);
+  }
+  if (steps_out) *steps_out = total;
+  return rc;
+}
+
+extern "C" int mh_t5_slots_release(void* handle, int slot) {
+  using namespace mh;
+  SlotSession* ss = (SlotSession*)handle;
+  const char* who = "mh_t5_slots_release";
+  MH_REQUIRE(ss, "%s: null handle", who);
+  MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
+  MH_REQUIRE(ss->live[slot], "%s: slot %d is idle", who, slot);
+  SlotDeviceGuard device_guard(ss->dev);
+  const int ci = ss->chain_of(slot);
+  hipStream_t cs = ss->chains[ci].stream;
+  if (ss->pending[ci]) {   // released before a step saw it: still behind its own admission
+    if (hipStreamWaitEvent(cs, ss->admitted[ci], 0) != hipSuccess) return check_launch("admission wait");
+    ss->pending[ci] = false;
+  }
+  // on the chain's stream, behind the slot's last step: idle again (negative position, flag set), then the event an admission waits for
+  if (hipMemsetAsync(ss->pos + slot, 0xff, 4, cs) != hipSuccess || hipMemsetAsync(ss->ly.bf.finished + slot, 1, 1, cs) != hipSuccess ||
+      hipEventRecord(ss->freed[slot], cs) != hipSuccess)
+    return check_launch("slot release");
+  ss->live[slot] = false;
+  return MH_OK;
+}
+
+extern "C" int mh_t5_slots_close(void* handle) {
+  using namespace mh;
+  SlotSession* ss = (SlotSession*)handle;
+  if (!ss) return MH_OK;
+  SlotDeviceGuard device_guard(ss->dev);
+  delete ss;   // joins the chains, then releases the graph references (the cross-call cache keeps the graphs it owns)
+  return check_launch("slot close");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -55,7 +55,8 @@ def _left_pad(rows, pad_id: int, dtype):
 
 
 class SequentialWindowScheduler:
-    def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32, merge_kwargs: bool = False):
+    def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32, merge_kwargs: bool = False,
+                 inflight: bool = False, inflight_steps: int = 16):
         if decode_batch > 64 or decode_batch < 1:
             raise ValueError("decode_batch must be in [1, 64] (32 at most when windows run under classifier-free guidance)")
         self.model, self.tokenizer = model, tokenizer
@@ -67,6 +68,10 @@ class SequentialWindowScheduler:
         # (server.row_call_key) decode as ONE call, every row under its own settings (T5Engine.decode(row_sampling=)); a wave
         # whose first / last windows carry other EOS windows than the rest is then one decode call, not two or three
         self.merge_kwargs = bool(merge_kwargs)
+        # inflight (off by default): no waves -- decode_batch SLOTS are kept full (T5Engine.open_slots): a song's window w + 1 is
+        # admitted as soon as its window w was delivered, into whatever slot is idle, while the other slots keep stepping;
+        # `inflight_steps` token steps run between two looks at the slots.  See `_run_inflight`.
+        self.inflight, self.inflight_steps = bool(inflight), max(1, int(inflight_steps))
 
     # ---- stage 1: everything that depends on the audio only ------------------------------------------------
     @torch.no_grad()
@@ -137,6 +142,8 @@ class SequentialWindowScheduler:
         eng, tok = self.engine, self.tokenizer
         for j in jobs:   # a mode where it is not built: refused before anything is encoded
             self._modes(j.generate_kwargs, int(j.generate_kwargs.get("num_beams", 1) or 1))
+        if self.inflight:
+            return self._run_inflight(jobs)
         start = time.perf_counter()
         kvs = self.encode_all(jobs)
         n_waves = max(j.frames.shape[0] for j in jobs)
@@ -189,6 +196,121 @@ class SequentialWindowScheduler:
             step = max(1, self.decode_batch // 2) if float(rows[0][2].get("cfg_scale", 1.0)) > 1.0 else self.decode_batch
             for a in range(0, len(rows), step):
                 self._decode_group(jobs, kvs, w, rows[a:a + step], pad_id, merged=True)
+
+    # ---- stage 2, in flight: slots instead of waves ----------------------------------------------------------------------------
+    _INFLIGHT_REFUSED = (("num_beams", lambda gk: int(gk.get("num_beams", 1) or 1) > 1, "beam search"),
+                         ("cfg_scale", lambda gk: float(gk.get("cfg_scale", 1.0)) > 1.0, "classifier-free guidance"),
+                         ("cross_kv_fp8", lambda gk: bool(gk.get("cross_kv_fp8", False)), "the e4m3 copy of the cross K/V"),
+                         ("self_kv_fp8", lambda gk: bool(gk.get("self_kv_fp8", False)), "the e4m3 self-attention cache"),
+                         ("beam_sample_fn", lambda gk: gk.get("beam_sample_fn") is not None, "an injected sampler"),
+                         ("sample_fn", lambda gk: gk.get("sample_fn") is not None, "an injected sampler"))
+
+    def _check_inflight(self, gk: dict, what: str) -> None:
+        for name, on, words in self._INFLIGHT_REFUSED:
+            if on(gk):
+                raise ValueError(f"inflight: {what} asks for {words} ({name}={gk.get(name)!r}), which has no slot form: "
+                                 "run it with inflight=False")
+
+    def _inflight_row(self, probe: list, gk: dict, sp0=None):
+        """One window's kwargs -> (per-call settings, its row entry, its EOS table), built TOGETHER with the session's probe list so
+        that the conditional rules keep the session's indices; with `sp0` (the session's settings) the window must not need a
+        per-call setting the session was not opened with."""
+        sp, rows, tables = build_row_sampling(self.tokenizer, probe + [gk], self.model.config.max_target_positions)
+        if sp0 is not None:
+            same = (sp.n_cond == sp0.n_cond and list(sp.cond_offset) == list(sp0.cond_offset) and sp.do_sample == sp0.do_sample
+                    and sp.lookback_types_first == sp0.lookback_types_first and sp.pad_id == sp0.pad_id
+                    and (sp.host_tok_flags is None) == (sp0.host_tok_flags is None)
+                    and (sp.host_tok_flags is None or bool((sp.host_tok_flags == sp0.host_tok_flags).all())))
+            if not same:
+                raise ValueError("inflight: a window's generate_kwargs need per-call settings (conditional rules, types_first lookback, "
+                                 "do_sample, pad id) that the jobs' own generate_kwargs and first windows did not announce")
+        return sp, rows[len(probe)], tables[rows[len(probe)].eos_set]
+
+    @torch.no_grad()
+    def _run_inflight(self, jobs: list[SongJob]):
+        """`inflight=True`: decode_batch slots kept full.  Window w + 1 of a song is admitted as soon as its window w was delivered
+        through `on_result` (per song strictly in order; across songs in no order), into the lowest idle slot, songs first come first
+        served; every row decodes under its own kwargs (`build_row_sampling`), as the default policy's batch-1 call for that window
+        would: explicit seeds with this scheduler's own call counter, RNG row 0, no left padding (so no redo path).  The per-call
+        settings (`row_call_key`) must agree over all jobs; beams, guidance, the fp8 caches and injected samplers are refused --
+        both before anything is encoded."""
+        eng, tok = self.engine, self.tokenizer
+        keys = set()
+        for n, j in enumerate(jobs):
+            self._check_inflight(j.generate_kwargs, f"job {n}")
+            keys.add(row_call_key(dict(j.generate_kwargs, conditional_temperature_per_row=True)))
+        if len(keys) > 1:
+            raise ValueError("inflight: the jobs differ in a per-call setting (server.row_call_key: do_sample, types_first, pad_token_id, "
+                             "precision, ...): such jobs need schedulers of their own")
+        start = time.perf_counter()
+        kvs = self.encode_all(jobs)
+        pad_id = int(getattr(tok, "pad_id", 0))
+        S = self.decode_batch
+        self.stats.setdefault("admissions", 0)
+        self.stats.setdefault("decode_steps", 0)
+
+        def ask_of(i, w):
+            ask = dict(jobs[i].prompt_fn(w))
+            gk = dict(jobs[i].generate_kwargs, **ask.pop("generate_kwargs", {}))
+            self._check_inflight(gk, f"window {w} of job {i}")
+            return ask, gk
+        # the session's per-call settings: those of every song's first window (window 0 depends on nothing), and -- types_first --
+        # of the same windows with a lookback, which the later windows of a song carry
+        first = {i: ask_of(i, 0) for i in range(len(jobs))}
+        probe = []
+        for _, gk in first.values():
+            # (seed_call_index -1: no window's own kwargs equal a probe entry's, so a window is always a group of its own -- RNG row
+            # 0 -- and the probe advances no seed count)
+            base = dict(gk, conditional_temperature_per_row=True, seed_call_index=-1)
+            base.pop("max_length", None)      # (a cap is the row's own: songs that differ in it alone are one probe entry, so
+            for entry in ([base] +            #  an admission builds a handful of rows, not one per song)
+                          ([dict(base, lookback_time=max(float(gk.get("lookback_time", 0) or 0), 1000.0))] if gk.get("types_first", False) else [])):
+                if entry not in probe:
+                    probe.append(entry)
+        sp0 = build_row_sampling(tok, probe, self.model.config.max_target_positions)[0]
+        sp0.max_length = int(self.model.config.max_target_positions)
+        slots = eng.open_slots(S, sp0)
+        occupant = [None] * S                       # slot -> (job, window, ask, admitted at)
+        ready = list(range(len(jobs)))              # songs whose next window may enter, first come first served
+        next_w = [0] * len(jobs)
+        try:
+            while True:
+                for slot in range(S):
+                    if occupant[slot] is not None or not ready:
+                        continue
+                    i = ready.pop(0)
+                    w = next_w[i]
+                    ask, gk = first.pop(i) if w == 0 else ask_of(i, w)
+                    _, row, eos_table = self._inflight_row(probe, self._call_kwargs(gk), sp0)
+                    ids = ask["decoder_input_ids"].reshape(-1)
+                    mask = ask.get("decoder_attention_mask")
+                    slots.admit(slot, kvs[i][:, :, w], ids, None if mask is None else mask.reshape(-1), row, eos_table)
+                    occupant[slot] = (i, w, ask, time.perf_counter())
+                    self.stats["admissions"] += 1
+                if all(o is None for o in occupant):
+                    break
+                steps0 = slots.stats["steps"]
+                finished, _ = slots.run(self.inflight_steps)
+                self.stats["decode_steps"] += slots.stats["steps"] - steps0
+                self.stats["decode_calls"] += 1
+                for slot in range(S):
+                    if occupant[slot] is None or not finished[slot]:
+                        continue
+                    i, w, ask, t0 = occupant[slot]
+                    row = slots.take(slot)
+                    occupant[slot] = None
+                    st = _build_generation_stats(row[None], dict(decoder_input_ids=ask["decoder_input_ids"].reshape(1, -1)), pad_id,
+                                                 time.perf_counter() - t0)
+                    self.stats["windows"] += 1
+                    self.stats["generated_tokens"] += st["generated_tokens"]
+                    jobs[i].on_result(w, row, st)
+                    next_w[i] = w + 1
+                    if next_w[i] < jobs[i].frames.shape[0]:
+                        ready.append(i)
+        finally:
+            slots.close()
+        self.stats["elapsed_seconds"] += time.perf_counter() - start
+        return self.stats
 
     def _modes(self, gk: dict, nb: int) -> DecodeModes:
         """The mode switches of one decode call, the scheduler's own way: the cache route is read under beams only (a greedy window

@@ -498,6 +498,15 @@ class T5Engine:
             _lib.check(self.lib.mh_t5_generate(*args), "mh_t5_generate")
         return tokens, n_out, logits
 
+    def open_slots(self, S: int, sampling: _lib.MhSampling, dump_logits: bool = False, poll_every: int = 16) -> "DecodeSlots":
+        """In-flight decode (`mh_t5_slots_*`, contract in include/mapperhip.h): S slots, every slot a row that decodes a window of
+        its own; a finished row's place goes to the next window while its neighbours keep stepping.  `sampling`: the per-call
+        settings (`server.build_row_sampling(...)[0]`; `max_length` = the longest window the session can hold).  Returns a
+        `DecodeSlots` with `admit`, `run`, `take` and `close`.  Greedy and sampled rows, per-row settings; no guidance, beams,
+        e4m3 caches or teacher forcing (refused by the library).  One session per engine at a time: its buffers live in this
+        engine's workspaces like the row-settings ones, so their pointers -- part of the step graph's key -- do not move."""
+        return DecodeSlots(self, int(S), sampling, dump_logits, poll_every)
+
     def quantize_kv_rows(self, rows: torch.Tensor):
         """`mh_quantize_kv_rows`: bf16 (..., 64) on the device -> (e4m3 bytes uint8 (..., 64), fp32 scales (...)), the row form of the
         e4m3 self-attention cache (scale = absmax / 448, element = cvt_e4m3(x * (1 / scale)))."""
@@ -605,3 +614,135 @@ class T5Engine:
             tokens = tokens[G:]
         return dict(tokens=tokens[:, :n_cols].to(torch.int64).cpu(), n_cols=n_cols,
                     logits=None if logits is None else logits[:n_cols])
+
+
+class DecodeSlots:
+    """A session of `T5Engine.open_slots`: S slots over `mh_t5_slots_*` (contract in include/mapperhip.h).
+
+        slots = engine.open_slots(S, sp)
+        slots.admit(slot, cross_kv_row, prompt, prompt_mask, row, eos_table)     # an idle slot <- one window
+        finished, lengths = slots.run(n_steps)                                   # every chain steps; one poll
+        tokens = slots.take(slot)                                                # the row so far, and the slot is idle again
+        slots.close()
+
+    A slot computes what `T5Engine.decode(row_sampling=...)` computes for the window alone (B = 1, its unpadded prompt, its own
+    row entry), bit for bit.  `stats`: admissions and graph replays so far."""
+
+    def __init__(self, engine: "T5Engine", S: int, sampling: _lib.MhSampling, dump_logits: bool, poll_every: int):
+        if not 1 <= S <= 64:
+            raise ValueError(f"open_slots: {S} slots not in [1, 64]")
+        if getattr(engine, "_slot_session", None) is not None:
+            raise RuntimeError("open_slots: this engine has an open slot session (its buffers are the engine's): close it first")
+        self.engine, self.S, self.sampling = engine, S, sampling
+        self._handle = C.c_void_p()
+        p = engine.packed
+        dev, lib = engine.device, engine.lib
+        flags = getattr(sampling, "host_tok_flags", None)
+        if flags is not None:   # the device copy lives as long as the session
+            self._flags_d = torch.as_tensor(flags, dtype=torch.uint8).to(dev)
+            sampling.tok_flags = self._flags_d.data_ptr()
+        elif sampling.n_cond or sampling.lookback_types_first:
+            raise ValueError("sampling needs tok_flags (build it with server.build_row_sampling)")
+        self.max_length = maxlen = int(sampling.max_length)
+        es = torch.empty(0, dtype=engine.dtype).element_size()
+        d = engine.dims
+        row_sz = C.sizeof(_lib.MhRowSampling)
+        self._rows_d = engine._workspace("slot_rows", 64 * row_sz)
+        self._eos_d = engine._workspace("slot_eos_tables", 64 * p.vocab_out)
+        self._rows_d.zero_()
+        self._eos_d.zero_()
+        self.cross_kv = engine._workspace("slot_cross_kv", d.n_dec_layers * 2 * S * d.n_heads * p.src_len * 64 * es)
+        self.tokens = engine._workspace("slot_tokens", 64 * p.tgt_len * 4)[:S * maxlen * 4].view(torch.int32).view(S, maxlen)
+        self.logits = None
+        if dump_logits:
+            n = maxlen * S * p.vocab_out
+            self.logits = engine._workspace("slot_logits", n * 4)[:n * 4].view(torch.float32).view(maxlen, S, p.vocab_out)
+            self.logits.zero_()
+        ws = engine._workspace("slots", lib.mh_t5_slots_workspace_bytes(C.byref(p.cfg), S))
+        self._hold = [None] * S          # what an admission reads, kept until the slot is taken
+        self._lengths = [0] * S
+        self._finished = [False] * S
+        self.live = [False] * S
+        self.stats = dict(admissions=0, steps=0, runs=0)
+        engine._enter()
+        try:
+            _lib.check(lib.mh_t5_slots_open(C.byref(p.cfg), C.byref(p.w), S, C.byref(sampling), self._rows_d.data_ptr(),
+                                            self._eos_d.data_ptr(), 64, self.cross_kv.data_ptr(), self.tokens.data_ptr(),
+                                            _lib.ptr(self.logits), None, None, ws.data_ptr(), ws.numel(), int(poll_every), engine._s(),
+                                            C.byref(self._handle)), "mh_t5_slots_open")
+        finally:
+            engine._leave()
+        engine._slot_session = self
+
+    def admit(self, slot: int, cross_kv_row: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
+              row: _lib.MhRowSampling, eos_table: torch.Tensor) -> None:
+        """One window into an idle slot: `cross_kv_row` its cross K/V (n_dec, 2, [1,] H, L, 64), `prompt` its own ids (P,) or (1, P)
+        without padding, `prompt_mask` or None, `row` its settings (an entry of `server.build_row_sampling(...)[1]`) and
+        `eos_table` uint8 (vocab_out,) its EOS set.  Returns at once; the slot's chain picks the window up at its next step."""
+        eng, p = self.engine, self.engine.packed
+        if not 0 <= slot < self.S or self.live[slot]:
+            raise ValueError(f"admit: slot {slot} is not an idle slot of this session")
+        prompt = prompt.reshape(-1)
+        P = int(prompt.shape[0])
+        if not (1 <= P < row.max_length <= self.max_length) or not row.temperature > 0:
+            raise ValueError(f"admit: prompt length {P} < row.max_length {row.max_length} <= {self.max_length} and temperature > 0 expected")
+        d = eng.dims
+        entry = _lib.MhRowSampling.from_buffer_copy(bytes(row))
+        entry.eos_set = slot                     # every slot owns a table: the EOS set of the window it holds
+        eng._enter()
+        try:
+            with torch.cuda.stream(eng.stream):
+                kv = cross_kv_row.reshape(d.n_dec_layers, 2, 1, d.n_heads, p.src_len, 64).to(eng.device, eng.dtype).contiguous()
+                prompt_d = prompt.to(eng.device, torch.int32).contiguous()
+                mask_d = None if prompt_mask is None else prompt_mask.reshape(-1).to(eng.device).to(torch.uint8).contiguous()
+                sz = C.sizeof(_lib.MhRowSampling)
+                self._rows_d[slot * sz:(slot + 1) * sz].copy_(torch.frombuffer(bytearray(bytes(entry)), dtype=torch.uint8))
+                self._eos_d[slot * p.vocab_out:(slot + 1) * p.vocab_out].copy_(torch.as_tensor(eos_table, dtype=torch.uint8).reshape(-1))
+                self._hold[slot] = (kv, prompt_d, mask_d)
+                _lib.check(eng.lib.mh_t5_slots_admit(self._handle, slot, kv.data_ptr(), prompt_d.data_ptr(), _lib.ptr(mask_d), P, eng._s()),
+                           "mh_t5_slots_admit")
+        finally:
+            eng._leave()
+        self.live[slot], self._finished[slot], self._lengths[slot] = True, False, P
+        self.stats["admissions"] += 1
+
+    def run(self, n_steps: int = 16):
+        """Up to `n_steps` token steps of every chain that has a live slot -> (finished, lengths): per slot, whether its row is
+        done and the valid columns of `tokens[slot]` (0 for an idle slot)."""
+        fin = (C.c_uint8 * self.S)()
+        length = (C.c_int32 * self.S)()
+        steps = C.c_int(0)
+        _lib.check(self.engine.lib.mh_t5_slots_run(self._handle, int(n_steps), fin, length, C.byref(steps)), "mh_t5_slots_run")
+        self._finished = [bool(f) for f in fin]
+        self._lengths = [int(n) for n in length]
+        self.stats["steps"] += int(steps.value)
+        self.stats["runs"] += 1
+        return list(self._finished), list(self._lengths)
+
+    def take(self, slot: int) -> torch.Tensor:
+        """The slot's row as of the last `run` -- int64 CPU (length,), the prompt included -- and the slot is idle again."""
+        if not 0 <= slot < self.S or not self.live[slot]:
+            raise ValueError(f"take: slot {slot} is not a live slot of this session")
+        out = self.tokens[slot, :self._lengths[slot]].to(torch.int64).cpu()
+        _lib.check(self.engine.lib.mh_t5_slots_release(self._handle, slot), "mh_t5_slots_release")
+        self.live[slot], self._hold[slot], self._lengths[slot], self._finished[slot] = False, None, 0, False
+        return out
+
+    def close(self) -> None:
+        h, self._handle = self._handle, C.c_void_p()
+        if h:
+            if getattr(self.engine, "_slot_session", None) is self:
+                self.engine._slot_session = None
+            _lib.check(self.engine.lib.mh_t5_slots_close(h), "mh_t5_slots_close")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

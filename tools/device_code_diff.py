@@ -81,6 +81,16 @@ def main_kernels(old_lib: str, new_lib: str, fragment: str) -> int:
     old, new = kernel_texts(old_lib, fragment), kernel_texts(new_lib, fragment)
     if not old:
         raise RuntimeError(f"no kernel matching {fragment!r} in {old_lib}")
+    # a change that adds a template flag (defaulted to false, at the end of the list) renames every old instantiation to
+    # `<..., false>`: an old name that is gone is compared with the new name that only appends `false` arguments to it
+    for s in sorted(old):
+        if s in new or not s.endswith(">"):
+            continue
+        for n_flags in (1, 2, 3):
+            renamed = s[:-1] + ", false" * n_flags + ">"
+            if renamed in new:
+                new[s] = new.pop(renamed)
+                break
     changed = [s for s in sorted(old) if s in new and old[s] != new[s]]
     gone = [s for s in sorted(old) if s not in new]
     for s in changed:
