@@ -79,6 +79,17 @@ int dispatch_kc(int d, F&& f) {
   if constexpr (KC == 8) return f(std::integral_constant<int, 8>{});
   else return d == 128 * KC ? f(std::integral_constant<int, KC>{}) : dispatch_kc<KC + 1>(d, f);
 }
+// THE form table.  A decode attention kernel exists in exactly three forms, (rotary / scaled scores, affine LayerNorm) =
+//   (false, false)  T5: bias-free projections behind an RMS norm, relative position bias, unscaled scores
+//   (true,  false)  rotary Whisper: biased fused projections, RoPE, scaled scores, optional window
+//   (true,  true)   HF Whisper (arch 2): the same behind an affine LayerNorm, identity rotary table
+// f(std::bool_constant, std::bool_constant) with one of these three pairs; (false, true) is no model and is never instantiated
+template <typename F>
+void dispatch_attn_form(bool rope_or_scaled, bool ln_b, F&& f) {
+  if (rope_or_scaled && ln_b) f(std::true_type{}, std::true_type{});
+  else if (rope_or_scaled) f(std::true_type{}, std::false_type{});
+  else f(std::false_type{}, std::false_type{});
+}
 int check_arch2_weights(const MhT5Config* c, const MhT5Weights* w, const char* who) {
   MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "%s: arch 2 needs decoder.embed_positions and the LayerNorm biases", who);
   return MH_OK;
@@ -1227,75 +1238,54 @@ template <typename T, int KC>
 int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, hipStream_t s, const dec::SelfKv8P* f8,
                     const uint8_t* origin = nullptr, const int32_t* slot_pos = nullptr) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d && inner == sa.H * 64, "decode: dense residual rows / projection weights expected");
-  const dec::NoSelfKv8P no8{};
+  // dec_self_attn_qkv_kernel<.., F8, IDX> over its cache block, in the model's form (dispatch_attn_form)
+  auto qkv = [&](auto f8c, auto idx, const auto& cache) {
+    dispatch_attn_form(sa.rope, hp.ln_b, [&](auto wh, auto ln) {
+      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, decltype(wh)::value, decltype(ln)::value, decltype(f8c)::value, decltype(idx)::value>),
+                         dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, cache);
+    });
+  };
   if (slot_pos) {   // slot_pos != NULL: the SLOT instantiation, every row at its own position (mh_t5_slots_*): the plain caches only
     MH_REQUIRE(!origin && !f8, "decode: the slot form of the self-attention has no e4m3 and no indexed cache");
     const dec::SelfSlotP sl{slot_pos};
-    if (sa.rope && hp.ln_b)
-      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
-    else if (sa.rope)
-      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
-    else
-      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, sl);
-  } else if (origin && f8) {   // both: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
+    dispatch_attn_form(sa.rope, hp.ln_b, [&](auto wh, auto ln) {
+      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, decltype(wh)::value, decltype(ln)::value>), dim3(sa.B * sa.H), dim3(1024), 0, s,
+                         MH_SELF_LEAD_ARGS, sa, hp, sl);
+    });
+  } else if (origin) {   // with f8 as well: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
     MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
                dec::kSelfIdxMaxTgt, sa.tgt_len);
-    if constexpr (sizeof(T) == 2) {
+    if (!f8) {
+      qkv(std::false_type{}, std::true_type{}, dec::SelfIdxP{origin});
+    } else if constexpr (sizeof(T) == 2) {
       dec::SelfKv8IdxP ix8{};
       ix8.k8 = f8->k8; ix8.v8 = f8->v8; ix8.ks = f8->ks; ix8.vs = f8->vs; ix8.origin = origin;
-      if (sa.rope && hp.ln_b)
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
-      else if (sa.rope)
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
-      else
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix8);
+      qkv(std::true_type{}, std::true_type{}, ix8);
     } else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
-  } else if (origin) {
-    MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
-               dec::kSelfIdxMaxTgt, sa.tgt_len);
-    const dec::SelfIdxP ix{origin};
-    if (sa.rope && hp.ln_b)
-      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
-    else if (sa.rope)
-      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
-    else
-      hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, ix);
   } else if (f8) {
-    if constexpr (sizeof(T) == 2) {
-      if (sa.rope && hp.ln_b)
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
-      else if (sa.rope)
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
-      else
-        hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, false, false, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, *f8);
-    } else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
-  } else if (sa.rope && hp.ln_b)   // HF Whisper (arch 2): the same behind an affine LayerNorm, identity rotary table
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
-  else if (sa.rope)   // the Whisper family: biased fused Wqkv, RoPE, scaled scores, optional window
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC, true>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
-  else
-    hipLaunchKernelGGL((dec::dec_self_attn_qkv_kernel<T, KC>), dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, no8);
+    if constexpr (sizeof(T) == 2) qkv(std::true_type{}, std::false_type{}, *f8);
+    else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
+  } else {
+    qkv(std::false_type{}, std::false_type{}, dec::NoSelfKv8P{});
+  }
   return check_launch("dec_self_attn_qkv_kernel");
 }
 template <typename T, int KC>
 int launch_cross_q(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s) {
   MH_REQUIRE(hp.ldh == hp.d && hp.ldw == hp.d, "decode: dense residual rows / projection weights expected");
   // one key in flight per 8-lane group: 64 VGPRs without spills (two 16-wave workgroups per CU); U = 2 measured the
-  // same bandwidth
-  if (ca.scale != 0.f && ca.kscale != nullptr) {   // the Whisper family over the e4m3 copy (the scale folds into the key scale)
-    if constexpr (sizeof(T) == 2) {
-      if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
-      else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
-    } else { set_error("decode: the fp8 cross K/V copy needs bf16 storage"); return MH_ERR_ARG; }
-  } else if (ca.scale != 0.f) {   // the Whisper family: biased Wq, scaled scores
-    if (hp.ln_b) hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
-    else hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, false, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
-  } else if (ca.kscale != nullptr) {
-    if constexpr (sizeof(T) == 2)
-      hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, true>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+  // same bandwidth.  The Whisper family: biased Wq, scaled scores (over the e4m3 copy the scale folds into the key scale)
+  auto cross = [&](auto f8c) {
+    dispatch_attn_form(ca.scale != 0.f, hp.ln_b, [&](auto wh, auto ln) {
+      hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1, decltype(f8c)::value, decltype(wh)::value, decltype(ln)::value>),
+                         dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    });
+  };
+  if (ca.kscale != nullptr) {   // the e4m3 copy of the cross K/V
+    if constexpr (sizeof(T) == 2) cross(std::true_type{});
     else { set_error("decode: the fp8 cross K/V copy needs bf16 storage"); return MH_ERR_ARG; }
   } else {
-    hipLaunchKernelGGL((dec::dec_cross_attn_q_kernel<T, KC, 1>), dim3(ca.B * ca.H), dim3(1024), 0, s, MH_CROSS_LEAD_ARGS, ca, hp);
+    cross(std::false_type{});
   }
   return check_launch("dec_cross_attn_q_kernel");
 }
@@ -1778,6 +1768,16 @@ __global__ __launch_bounds__(256) void self_kv_quant_rows_kernel(const bf16_t* s
   mh::dec::quant_row64(x, q + (y * plane_rows + row) * 64, scales + y * plane_rows + row);
 }
 
+// positions 0 .. n_pos-1 of cache rows 0 .. n_rows-1 of a B-row batch's bf16 self-attention caches -> the B-row shadow self8, every
+// layer, k and v
+static int launch_self_kv_quant_rows(const MhT5Config* c, int B, const DecBuffers& bf, uint8_t* self8, int n_rows, int n_pos, hipStream_t s) {
+  const long n_slabs = (long)n_rows * c->n_heads, plane_rows = (long)B * c->n_heads * c->tgt_len;
+  hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * n_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
+                     (const bf16_t*)bf.self_k, (const bf16_t*)bf.self_v, self8,
+                     reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)n_pos, (long)c->tgt_len, plane_rows);
+  return check_launch("self_kv_quant_rows_kernel");
+}
+
 extern "C" int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, float* scales, void* stream) {
   MH_REQUIRE(x_bf16 && q && scales, "mh_quantize_kv_rows: null argument");
   MH_REQUIRE(n_rows > 0, "mh_quantize_kv_rows: n_rows %lld must be positive", (long long)n_rows);
@@ -1902,6 +1902,18 @@ static void step_graph_release(StepGraphEntry* e) {
   e->in_use = false;
 }
 
+// The device that owns the caller's stream (not whatever happens to be current)
+static int stream_device(hipStream_t s, int* dev) {
+  if (hipStreamGetDevice(s, dev) != hipSuccess) { (void)hipGetLastError(); if (hipGetDevice(dev) != hipSuccess) return check_launch("hipGetDevice"); }
+  return MH_OK;
+}
+// Streams, events and graphs of a call or a session are created under that device; the current one is restored on every return path
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int want) { if (hipGetDevice(&prev) == hipSuccess && prev != want) (void)hipSetDevice(want); else prev = -1; }
+  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 // A chain of the running call and the owner of its step graph: the cross-call cache (`cached`: handed back when the call ends) or the
 // call itself (destroyed with it, after the call's last synchronise)
 struct Chain {
@@ -1958,44 +1970,56 @@ static int poll_chain(const Chain& ch, bool* running) {
   return word[1] != 0 ? MH_ERR_DECODE_TAIL_TIMEOUT : MH_OK;
 }
 
-// The launcher of `n` chains from the calling thread: bursts of poll_every replays each, interleaved, then a poll of each (none behind the
-// last burst, none under teacher forcing: poll = false).  A chain is left out once its rows are done or it failed (rcs[i]).
-static void run_chains(const Chain* chains, int n, int total_steps, int poll_every, bool poll, int* rcs) {
+// The one burst-and-poll loop, of a uniform call and of a slot session alike.  The launcher of chains which[0 .. n) from the calling
+// thread: bursts of poll_every replays each, interleaved, then a poll of each (none behind the last burst, none under teacher forcing:
+// poll = false).  A chain is left out once its rows are done or it failed (rcs[chain]); replays[chain], if given, counts its
+// hipGraphLaunch calls that succeeded.
+static void run_chains(const Chain* chains, const int* which, int n, int n_steps, int poll_every, bool poll, int* rcs, int* replays) {
   bool alive[kMaxChains];
-  for (int ci = 0; ci < n; ++ci) alive[ci] = true;
-  for (int step = 0; step < total_steps;) {
-    const int burst = total_steps - step < poll_every ? total_steps - step : poll_every;
-    for (int i = 0; i < burst; ++i)
-      for (int ci = 0; ci < n; ++ci)
-        if (alive[ci] && rcs[ci] == MH_OK && hipGraphLaunch(chains[ci].exec, chains[ci].stream) != hipSuccess) rcs[ci] = MH_ERR_LAUNCH;
+  for (int i = 0; i < n; ++i) alive[i] = true;
+  for (int step = 0; step < n_steps;) {
+    const int burst = n_steps - step < poll_every ? n_steps - step : poll_every;
+    for (int r = 0; r < burst; ++r)
+      for (int i = 0; i < n; ++i) {
+        const int ci = which[i];
+        if (!alive[i] || rcs[ci] != MH_OK) continue;
+        if (hipGraphLaunch(chains[ci].exec, chains[ci].stream) != hipSuccess) rcs[ci] = MH_ERR_LAUNCH;
+        else if (replays) ++replays[ci];
+      }
     step += burst;
     bool any = false;
-    for (int ci = 0; ci < n; ++ci) {
-      if (!alive[ci] || rcs[ci] != MH_OK) continue;
-      if (step < total_steps && poll && (rcs[ci] = poll_chain(chains[ci], &alive[ci])) != MH_OK) continue;
-      any = any || alive[ci];
+    for (int i = 0; i < n; ++i) {
+      const int ci = which[i];
+      if (!alive[i] || rcs[ci] != MH_OK) continue;
+      if (step < n_steps && poll && (rcs[ci] = poll_chain(chains[ci], &alive[i])) != MH_OK) continue;
+      any = any || alive[i];
     }
     if (!any) break;
   }
 }
-// Replaying a ~110-node graph costs ~0.4 ms of HOST time on ROCm 7.2, so every chain gets a launcher thread of its own (the chains are
-// independent); option decode_launch_threads = 0: one launcher for all (slower on the host side; the same kernels and arguments)
-static int launch_chains(const Chain* chains, int used, int total_steps, int poll_every, bool poll, const char* who) {
+// Replaying a ~110-node graph costs ~0.4 ms of HOST time on ROCm 7.2, so every running chain gets a launcher thread of its own (the
+// chains are independent; the first runs on the calling thread); option decode_launch_threads = 0: one launcher for all, their bursts
+// interleaved (slower on the host side; the same kernels and arguments).  which: the chains that run -- all of a uniform call, those
+// with a live slot of a session.  -> the call's status, the failed chain named by its index
+static int launch_chains(const Chain* chains, const int* which, int n, int n_steps, int poll_every, bool poll, const char* who,
+                         int* replays = nullptr) {
   int rcs[kMaxChains] = {};
-  if (used <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
-    run_chains(chains, used, total_steps, poll_every, poll, rcs);
+  if (n <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
+    run_chains(chains, which, n, n_steps, poll_every, poll, rcs, replays);
   } else {
     std::vector<std::thread> th;
     const MhOptionSet* set = current_option_set();   // thread-local in the caller: re-installed in every launcher
-    for (int ci = 1; ci < used; ++ci)
-      th.emplace_back([&, ci, set] { OptionScope sc(set); run_chains(&chains[ci], 1, total_steps, poll_every, poll, &rcs[ci]); });
-    run_chains(&chains[0], 1, total_steps, poll_every, poll, &rcs[0]);
+    for (int i = 1; i < n; ++i)
+      th.emplace_back([&, i, set] { OptionScope sc(set); run_chains(chains, which + i, 1, n_steps, poll_every, poll, rcs, replays); });
+    run_chains(chains, which, 1, n_steps, poll_every, poll, rcs, replays);
     for (auto& t : th) t.join();
   }
   int rc = MH_OK;
-  for (int ci = 0; ci < used; ++ci)
+  for (int i = 0; i < n; ++i) {
+    const int ci = which[i];
     if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
     else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
+  }
   return rc;
 }
 
@@ -2031,11 +2055,30 @@ static int check_decode_call(const MhT5Config* c, const MhT5Weights* w, const Mh
   return MH_OK;
 }
 
+// The row settings of mh_t5_generate_rows (one entry per: "returned row") and of mh_t5_slots_open ("slot")
+static int check_row_set(const MhRowSampling* rows, const uint8_t* eos_tables, int n_eos_sets, const char* per, const char* who) {
+  MH_REQUIRE(rows && eos_tables, "%s: null argument (rows: one MhRowSampling per %s; eos_tables: [n_eos_sets][vocab_out])", who, per);
+  MH_REQUIRE(n_eos_sets >= 1, "%s: n_eos_sets %d must be >= 1", who, n_eos_sets);
+  return MH_OK;
+}
+
 static int check_generate_args(const GenerateArgs& a) {
   const bool ptrs_ok = a.cross_kv && a.prompt && (a.eos_table || a.rowset) && a.tokens && a.n_steps_out && a.workspace;
   MH_TRY(check_decode_call(a.c, a.w, a.sp, a.B, ptrs_ok, a.stream, &a.P, a.rowset != nullptr, a.who));
   MH_REQUIRE(a.workspace_bytes >= mh_t5_decode_workspace_bytes(a.c, a.B), "%s: workspace too small", a.who);
   return check_arch2_weights(a.c, a.w, a.who);
+}
+
+// The first row of the e4m3 shadow of the self-attention cache, and of its scales, at row b0 of a B-row batch (the b0 offsets of the
+// bf16 caches); the same over the packed e4m3 copy of the cross K/V of kvB rows
+static void self8_rows(const MhT5Config* c, int B, int b0, void* self8, DecBuffers* bf) {
+  const long row = (long)b0 * c->n_heads * c->tgt_len;
+  bf->self8 = (uint8_t*)self8 + row * 64;
+  bf->self8_scales = reinterpret_cast<float*>((uint8_t*)self8 + self_kv8_layout(c, B).scales_offset) + row;
+}
+static void cross8_rows(const MhT5Config* c, int kvB, int b0, const void* kv8, StepCall* k) {
+  k->kv8 = (const char*)kv8 + (long)b0 * c->n_heads * c->src_len * 64;
+  k->kv8_scales = reinterpret_cast<const float*>((const char*)kv8 + cross_kv8_layout(c, kvB).scales_offset) + (long)b0 * c->n_heads;
 }
 
 // Chain ci of the call as a StepCall: rows [ci rows_per, + Bc) of every buffer, of the e4m3 copies and of the sampler's view
@@ -2061,17 +2104,11 @@ static void chain_call(const GenerateArgs& a, const DecodeLayout& ly, int ci, in
   bf.logits = all.logits + (long)b0 * V;
   bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
   bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
-  if (self8) {   // the chain's first row of the shadow and of its scales (the same b0 offsets as the bf16 caches)
-    bf.self8 = self8 + (long)b0 * inner * c->tgt_len;
-    bf.self8_scales = reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset) + (long)b0 * H * c->tgt_len;
-  }
+  if (self8) self8_rows(c, B, b0, self8, &bf);
   bf.finished = all.finished + b0;
   bf.finish_col = all.finish_col; bf.last_ts = all.last_ts;
   bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
-  if (sp->cross_kv_fp8) {   // the chain's first row of the packed e4m3 copy and of its scales
-    k->kv8 = (const char*)sp->cross_kv_fp8 + (long)b0 * H * c->src_len * 64;
-    k->kv8_scales = reinterpret_cast<const float*>((const char*)sp->cross_kv_fp8 + cross_kv8_layout(c, k->kvB).scales_offset) + (long)b0 * H;
-  }
+  if (sp->cross_kv_fp8) cross8_rows(c, k->kvB, b0, sp->cross_kv_fp8, k);
   SampleP& smp = k->smp;
   smp.logits = bf.logits; smp.ldl = V; smp.V = V; smp.tokens = a.tokens; smp.max_length = sp->max_length;
   smp.forced = a.forced; smp.eos_table = a.eos_table; smp.finished = all.finished; smp.finish_col = all.finish_col;
@@ -2085,6 +2122,15 @@ static void chain_call(const GenerateArgs& a, const DecodeLayout& ly, int ci, in
     smp.prompt_mask = a.prompt_mask;
   }
 }
+// The batch cut into n_chains blocks of rows_per rows: calls[0 .. used), -> used (a late block may be empty: B = 5 over 4 chains)
+static int chain_calls(const GenerateArgs& a, const DecodeLayout& ly, int n_chains, int rows_per, uint8_t* self8, StepCall* calls) {
+  int used = 0;
+  for (; used < n_chains; ++used) {
+    chain_call(a, ly, used, rows_per, self8, &calls[used]);
+    if (calls[used].Bc <= 0) break;
+  }
+  return used;
+}
 
 static int generate_impl(const GenerateArgs& a) {
   MH_TRY(check_generate_args(a));
@@ -2097,13 +2143,9 @@ static int generate_impl(const GenerateArgs& a) {
   // a CFG pair spans both halves of the batch and the (batch-wide) conditional temperature reads row 0's history: one chain
   const int n_chains = (cfg || (sp->n_cond > 0 && !sp->cond_per_row)) ? 1 : pick_chains(B);
   const int rows_per = ceil_div(B, n_chains);
-  int dev = 0;   // the device that owns the caller's stream (not whatever happens to be current)
-  if (hipStreamGetDevice(s, &dev) != hipSuccess) { (void)hipGetLastError(); if (hipGetDevice(&dev) != hipSuccess) return check_launch("hipGetDevice"); }
-  struct DeviceGuard {   // streams / events of the pool are created under the stream's device; restored on every return path
-    int prev = -1;
-    explicit DeviceGuard(int want) { if (hipGetDevice(&prev) == hipSuccess && prev != want) (void)hipSetDevice(want); else prev = -1; }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  } device_guard(dev);
+  int dev = 0;
+  MH_TRY(stream_device(s, &dev));
+  DeviceGuard device_guard(dev);
   DevicePool* dp = device_pool(dev);
   std::lock_guard<std::mutex> pool_guard(dp->mu);
   ChainPool& g_pool = dp->pool;
@@ -2128,26 +2170,19 @@ static int generate_impl(const GenerateArgs& a) {
   // the shadow: the prompt positions the batched prefill wrote (they attended each other through the bf16 cache) are quantised in
   // one pass before the first token step; every token step appends its own row
   uint8_t* self8 = (uint8_t*)a.self_kv_fp8;
-  if (self8 && start_pos > 0) {
-    const long n_slabs = (long)B * c->n_heads;
-    hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
-                       (const bf16_t*)ly.bf.self_k, (const bf16_t*)ly.bf.self_v, self8,
-                       reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)start_pos, (long)c->tgt_len, n_slabs * c->tgt_len);
-    MH_TRY(check_launch("self_kv_quant_rows_kernel"));
-  }
+  if (self8 && start_pos > 0) MH_TRY(launch_self_kv_quant_rows(c, B, ly.bf, self8, B, start_pos, s));
   if (hipEventRecord(g_pool.fork, s) != hipSuccess) return check_launch("fork record");
 
-  int used = 0, rc = MH_OK;
-  for (int ci = 0; ci < n_chains && rc == MH_OK; ++ci) {
-    StepCall call;
-    chain_call(a, ly, ci, rows_per, self8, &call);
-    if (call.Bc <= 0) break;
-    ++used;
-    rc = start_chain(call, start_pos, g_pool.fork, a.who, &chains[ci]);
+  StepCall calls[kMaxChains];
+  const int used = chain_calls(a, ly, n_chains, rows_per, self8, calls);
+  int rc = MH_OK, which[kMaxChains];   // every chain of the call runs
+  for (int ci = 0; ci < used && rc == MH_OK; ++ci) {
+    which[ci] = ci;
+    rc = start_chain(calls[ci], start_pos, g_pool.fork, a.who, &chains[ci]);
   }
 
   const int total_steps = sp->max_length - 1 - start_pos;   // positions start_pos .. max_length-2 are fed
-  if (rc == MH_OK) rc = launch_chains(chains, used, total_steps, a.poll_every <= 0 ? 16 : a.poll_every, !a.forced, a.who);
+  if (rc == MH_OK) rc = launch_chains(chains, which, used, total_steps, a.poll_every <= 0 ? 16 : a.poll_every, !a.forced, a.who);
   // join the chains back into the caller's stream
   for (int ci = 0; ci < used; ++ci) {
     (void)hipEventRecord(g_pool.join[ci], chains[ci].stream);
@@ -2208,8 +2243,7 @@ extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, co
   mh::OptionScope option_scope(c ? c->options : nullptr);
   (void)eos_table;   // ignored: every row names its set of eos_tables
   MH_TRY(check_cfg(c, "mh_t5_generate_rows"));
-  MH_REQUIRE(rows && eos_tables, "mh_t5_generate_rows: null argument (rows: one MhRowSampling per returned row; eos_tables: [n_eos_sets][vocab_out])");
-  MH_REQUIRE(n_eos_sets >= 1, "mh_t5_generate_rows: n_eos_sets %d must be >= 1", n_eos_sets);
+  MH_TRY(mh::check_row_set(rows, eos_tables, n_eos_sets, "returned row", "mh_t5_generate_rows"));
   MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "mh_t5_generate_rows: the e4m3 self-attention cache needs bf16 storage");
   const mh::RowSetP rowset{rows, eos_tables, n_eos_sets};
   return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
@@ -2257,11 +2291,6 @@ struct SlotSession {
   }
   int chain_of(int slot) const { return slot / rows_per; }
 };
-struct SlotDeviceGuard {
-  int prev = -1;
-  explicit SlotDeviceGuard(int want) { if (hipGetDevice(&prev) == hipSuccess && prev != want) (void)hipSetDevice(want); else prev = -1; }
-  ~SlotDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 // the slot buffers behind the decode layout of S rows, then the prompt prefill of ONE row (an admission prefills one window)
 static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession* ss) {
   const DecodeLayout ly = decode_layout(c, S, base);
@@ -2275,20 +2304,6 @@ static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession*
     ss->prefill_base = (char*)base + ly.end + ar.off; ss->prefill_bytes = pre;
   }
   return ly.end + ar.off + pre;
-}
-// up to n_steps replays of one chain, a poll every poll_every (none behind the last burst): stops when no row of the chain runs
-static void slots_run_chain(const Chain& ch, int n_steps, int poll_every, int* rc, int* steps) {
-  for (int step = 0; step < n_steps && *rc == MH_OK;) {
-    const int burst = n_steps - step < poll_every ? n_steps - step : poll_every;
-    for (int i = 0; i < burst && *rc == MH_OK; ++i) {
-      if (hipGraphLaunch(ch.exec, ch.stream) != hipSuccess) *rc = MH_ERR_LAUNCH;
-      else ++*steps;
-    }
-    step += burst;
-    bool running = true;
-    if (step < n_steps && *rc == MH_OK) *rc = poll_chain(ch, &running);
-    if (!running) break;
-  }
 }
 }  // namespace mh
 
@@ -2309,8 +2324,7 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   MH_REQUIRE(handle, "%s: null argument (handle)", who);
   *handle = nullptr;
   MH_REQUIRE(S >= 1 && S <= 64, "%s: %d slots not in [1, 64]", who, S);
-  MH_REQUIRE(rows && eos_tables, "%s: null argument (rows: one MhRowSampling per slot; eos_tables: [n_eos_sets][vocab_out])", who);
-  MH_REQUIRE(n_eos_sets >= 1, "%s: n_eos_sets %d must be >= 1", who, n_eos_sets);
+  MH_TRY(check_row_set(rows, eos_tables, n_eos_sets, "slot", who));
   MH_REQUIRE(sp, "%s: null argument (sp)", who);
   MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
   MH_REQUIRE(!forced, "%s: teacher forcing (forced ids) has no slot form", who);
@@ -2323,8 +2337,8 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   MH_TRY(check_arch2_weights(c, w, who));
   hipStream_t s = (hipStream_t)stream;
   int dev = 0;
-  if (hipStreamGetDevice(s, &dev) != hipSuccess) { (void)hipGetLastError(); if (hipGetDevice(&dev) != hipSuccess) return check_launch("hipGetDevice"); }
-  SlotDeviceGuard device_guard(dev);
+  MH_TRY(stream_device(s, &dev));
+  DeviceGuard device_guard(dev);
   std::unique_ptr<SlotSession> ss(new SlotSession());
   ss->c = c; ss->w = w; ss->S = S; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
   ss->cross_kv = (char*)cross_kv_slots; ss->tokens = tokens;
@@ -2345,11 +2359,9 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   const RowSetP rowset{rows, eos_tables, n_eos_sets};
   GenerateArgs a{c, w, cross_kv_slots, S, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
                  workspace_bytes, poll_every, stream, nullptr, &rowset, who};
-  int used = 0;
+  ss->n_chains = chain_calls(a, ss->ly, ss->n_chains, ss->rows_per, nullptr, ss->calls);   // prompt_mask: the slot mask rows, stride max_length (call.P)
   for (int ci = 0; ci < ss->n_chains; ++ci) {
     StepCall& call = ss->calls[ci];
-    chain_call(a, ss->ly, ci, ss->rows_per, nullptr, &call);   // prompt_mask: the slot mask rows, stride max_length (call.P)
-    if (call.Bc <= 0) break;
     call.slot_pos = ss->pos; call.slot_plen = ss->plen;
     Chain& ch = ss->chains[ci];
     if (hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking) != hipSuccess ||
@@ -2358,9 +2370,7 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
     ch.st = call.bf.st;
     if (hipStreamWaitEvent(ch.stream, ss->freed[0], 0) != hipSuccess) return check_launch("slot stream wait");   // behind the memsets
     MH_TRY(chain_step_graph(call, who, &ch));
-    ++used;
   }
-  ss->n_chains = used;
   if (hipStreamSynchronize(s) != hipSuccess) return check_launch("slot open");
   *handle = ss.release();
   return MH_OK;
@@ -2377,7 +2387,7 @@ extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_ro
   MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
   MH_REQUIRE(!ss->live[slot], "%s: slot %d is live (release it first)", who, slot);
   MH_REQUIRE(P >= 1 && P < ss->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
-  SlotDeviceGuard device_guard(ss->dev);
+  DeviceGuard device_guard(ss->dev);
   const MhT5Config* c = ss->c;
   const int ci = ss->chain_of(slot), es = es_of(c->dtype), H = c->n_heads, inner = H * 64;
   hipStream_t as = ss->admit_stream;
@@ -2423,14 +2433,13 @@ extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out,
   MH_REQUIRE(ss, "%s: null handle", who);
   OptionScope option_scope(ss->c->options);
   MH_REQUIRE(n_steps >= 0 && finished_out && length_out, "%s: bad argument", who);
-  SlotDeviceGuard device_guard(ss->dev);
-  int rcs[kMaxChains] = {}, steps[kMaxChains] = {};
+  DeviceGuard device_guard(ss->dev);
+  int steps[kMaxChains] = {}, which[kMaxChains], n_run = 0;   // which: the chains with a live slot run
   bool runs[kMaxChains] = {};
-  int n_run = 0;
   for (int b = 0; b < ss->S; ++b) if (ss->live[b]) runs[ss->chain_of(b)] = true;
   for (int ci = 0; ci < ss->n_chains; ++ci) {
     if (!runs[ci]) continue;
-    ++n_run;
+    which[n_run++] = ci;
     // The fused tail's hand-off counters only ever grow inside a call, and a launch takes its base as a multiple of its grid: a
     // session has no dec_init_kernel between its steps, so they start every run at zero (the chain is idle here: the last run
     // ended with its poll) and cannot wrap however long the session lives.  tail_err stays: a timed-out session stays reported.
@@ -2441,30 +2450,8 @@ extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out,
       ss->pending[ci] = false;
     }
   }
-  if (n_steps > 0) {
-    if (n_run <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
-      // (one launcher: the chains' bursts one after the other -- poll_every replays are enqueued far faster than they run)
-      for (int ci = 0; ci < ss->n_chains; ++ci)
-        if (runs[ci]) slots_run_chain(ss->chains[ci], n_steps, ss->poll_every, &rcs[ci], &steps[ci]);
-    } else {
-      std::vector<std::thread> th;
-      const MhOptionSet* set = current_option_set();
-      int first = -1;
-      for (int ci = 0; ci < ss->n_chains; ++ci) {
-        if (!runs[ci]) continue;
-        if (first < 0) { first = ci; continue; }
-        th.emplace_back([&, ci, set] { OptionScope sc(set); slots_run_chain(ss->chains[ci], n_steps, ss->poll_every, &rcs[ci], &steps[ci]); });
-      }
-      slots_run_chain(ss->chains[first], n_steps, ss->poll_every, &rcs[first], &steps[first]);
-      for (auto& t : th) t.join();
-    }
-  }
-  int rc = MH_OK, total = 0;
-  for (int ci = 0; ci < ss->n_chains; ++ci) {
-    total += steps[ci];
-    if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
-    else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
-  }
+  int rc = n_steps > 0 ? launch_chains(ss->chains, which, n_run, n_steps, ss->poll_every, true, who, steps) : MH_OK, total = 0;
+  for (int ci = 0; ci < ss->n_chains; ++ci) total += steps[ci];
   // one poll per chain: its rows' flags, finish columns and positions, and the bounded hand-offs' last word
   for (int ci = 0; ci < ss->n_chains; ++ci) {
     const int b0 = ci * ss->rows_per, n = ss->calls[ci].Bc;
@@ -2494,7 +2481,7 @@ extern "C" int mh_t5_slots_release(void* handle, int slot) {
   MH_REQUIRE(ss, "%s: null handle", who);
   MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
   MH_REQUIRE(ss->live[slot], "%s: slot %d is idle", who, slot);
-  SlotDeviceGuard device_guard(ss->dev);
+  DeviceGuard device_guard(ss->dev);
   const int ci = ss->chain_of(slot);
   hipStream_t cs = ss->chains[ci].stream;
   if (ss->pending[ci]) {   // released before a step saw it: still behind its own admission
@@ -2513,7 +2500,7 @@ extern "C" int mh_t5_slots_close(void* handle) {
   using namespace mh;
   SlotSession* ss = (SlotSession*)handle;
   if (!ss) return MH_OK;
-  SlotDeviceGuard device_guard(ss->dev);
+  DeviceGuard device_guard(ss->dev);
   delete ss;   // joins the chains, then releases the graph references (the cross-call cache keeps the graphs it owns)
   return check_launch("slot close");
 }
@@ -2756,11 +2743,8 @@ static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cros
   k.bf = decode_layout(c, B, workspace).bf;
   k.bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
   k.origin = origin;
-  if (shadow) {   // the whole batch is one chain: the shadow's first row and its scales (chain_call's derivation at b0 = 0)
-    k.bf.self8 = (uint8_t*)self_kv_fp8;
-    k.bf.self8_scales = reinterpret_cast<float*>((uint8_t*)self_kv_fp8 + self_kv8_layout(c, B).scales_offset);
-  }
-  if (fp8) { k.kv8 = cross_kv_fp8; k.kv8_scales = (const float*)((const char*)cross_kv_fp8 + cross_kv8_layout(c, k.kvB).scales_offset); }
+  if (shadow) self8_rows(c, B, 0, self_kv_fp8, &k.bf);   // the whole batch is one chain
+  if (fp8) cross8_rows(c, k.kvB, 0, cross_kv_fp8, &k);
   const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
   const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
   return dispatch_dtype(c->dtype, [&](auto t) {
@@ -2904,13 +2888,7 @@ extern "C" int mh_t5_self_kv_fp8_fill(const MhT5Config* c, int B, int n_rows, in
   MH_REQUIRE(B % n_rows == 0, "mh_t5_self_kv_fp8_fill: %d rows are not whole groups over %d prompts", B, n_rows);
   MH_REQUIRE(n_pos >= 1 && n_pos < c->tgt_len, "mh_t5_self_kv_fp8_fill: %d positions outside the cache (tgt_len %d)", n_pos, c->tgt_len);
   MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_self_kv_fp8_fill: workspace too small");
-  const DecodeLayout ly = decode_layout(c, B, workspace);
-  const long n_slabs = (long)n_rows * c->n_heads, plane_rows = (long)B * c->n_heads * c->tgt_len;
-  uint8_t* self8 = (uint8_t*)self_kv_fp8;
-  hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * n_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0,
-                     (hipStream_t)stream, (const bf16_t*)ly.bf.self_k, (const bf16_t*)ly.bf.self_v, self8,
-                     reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)n_pos, (long)c->tgt_len, plane_rows);
-  return check_launch("self_kv_quant_rows_kernel");
+  return launch_self_kv_quant_rows(c, B, decode_layout(c, B, workspace).bf, (uint8_t*)self_kv_fp8, n_rows, n_pos, (hipStream_t)stream);
 }
 
 // positions 0 .. n_pos-1 of Bp prompts through the batched prefill (prefill_prompt: HF's one forward over the prompt) into cache rows

@@ -6,6 +6,7 @@ its own row entry.  Rows are batch-invariant in this engine, so a slot row must 
 column it produced, after every step, and its token ids when it retires.  The models are those of the tiny goldens
 (tests/golden/t5_tiny.npz, vw_test.npz, hfw_test.npz: seeded weights) at their own sizes; the T5 one gets 160 target positions so
 that a row can pass the 128-key iteration of the self-attention's key loop."""
+import contextlib
 import ctypes as C
 
 import pytest
@@ -248,23 +249,109 @@ def test_t5_sampled_slots_draw_what_the_uniform_call_draws(dtype):
 
 
 # ---- 3: two chains -------------------------------------------------------------------------------------------------------------------
-def test_17_slots_are_two_chains_with_refills_in_both():
-    """S = 17: chains of 9 + 8 rows.  22 windows; the first retirements are the last row of chain 0 (slot 8) and slots of chain 1."""
+@contextlib.contextmanager
+def _launch_threads(eng, value):
+    """the engine option decode_launch_threads for the block: 1 (the default) = a launcher thread per chain, 0 = one thread feeds all"""
+    eng.options["decode_launch_threads"] = value
+    try:
+        yield
+    finally:
+        eng.options.clear("decode_launch_threads")
+
+
+@pytest.mark.parametrize("launch_threads", [1, 0], ids=["launch_threads_1", "launch_threads_0"])
+def test_17_slots_are_two_chains_with_refills_in_both(launch_threads):
+    """S = 17: chains of 9 + 8 rows.  22 windows; the first retirements are the last row of chain 0 (slot 8) and slots of chain 1.
+    With one launcher thread per chain and with one for both: a chain's replay count depends only on its own polls, so the session
+    counts the same replays -- one per `run(1)` and chain that holds a live slot."""
     m, tok, n_samples = _t5_model(torch.float32)
     assert m.engine.lib.mh_t5_decode_chains_cfg(C.byref(m.engine.packed.cfg), 17) == 2
     kv = _cross_kv(m, n_samples, 4)
-    caps = {8: 6, 16: 8, 12: 10, 3: 12}                                   # slot of the first round -> a short cap
-    wins = []
-    for i in range(22):
-        P = (1, 2, 5, 3)[i % 4]
-        cap = P + caps.get(i, 14 + i % 5) if i < 17 else P + 4 + i % 3
-        wins.append(_Window(i % 4, _prompt(tok, P, seed=50 + i), _gk(T5_TGT, max_length=cap), eos=(i % 2 == 0)))
-    refs = [_uniform(m, tok, kv, w, T5_TGT) for w in wins]
-    history, timeline, stats = _run_inflight(m, tok, kv, wins, 17, T5_TGT, refs, dump=False)
+    if "case17" not in _CACHE:
+        caps = {8: 6, 16: 8, 12: 10, 3: 12}                               # slot of the first round -> a short cap
+        wins = []
+        for i in range(22):
+            P = (1, 2, 5, 3)[i % 4]
+            cap = P + caps.get(i, 14 + i % 5) if i < 17 else P + 4 + i % 3
+            wins.append(_Window(i % 4, _prompt(tok, P, seed=50 + i), _gk(T5_TGT, max_length=cap), eos=(i % 2 == 0)))
+        _CACHE["case17"] = (wins, [_uniform(m, tok, kv, w, T5_TGT) for w in wins])
+    wins, refs = _CACHE["case17"]
+    with _launch_threads(m.engine, launch_threads):
+        assert m.engine.lib.mh_t5_decode_chains_cfg(C.byref(m.engine.packed.cfg), 17) == 2
+        history, timeline, stats = _run_inflight(m, tok, kv, wins, 17, T5_TGT, refs, dump=False)
     refilled = [s for s in range(17) if len(history[s]) > 1]
     assert any(s < 9 for s in refilled) and any(s >= 9 for s in refilled), f"refills in one chain only: {history}"
     assert 8 in refilled or 16 in refilled, f"no refill in a chain's last row: {history}"
     assert stats["admissions"] == 22
+    chain_of = {i: s // 9 for s in range(17) for i in history[s]}
+    want_steps = sum(len({chain_of[i] for i, _ in live}) for live in timeline)
+    assert any(len({chain_of[i] for i, _ in live}) == 2 for live in timeline), "no run with a live slot in both chains"
+    assert stats["steps"] == want_steps, (launch_threads, stats, want_steps)
+    seen = _CACHE.setdefault("steps17", {})
+    seen[launch_threads] = stats["steps"]
+    assert len(set(seen.values())) == 1, f"the replay count depends on decode_launch_threads: {seen}"
+
+
+# ---- 3b: the uniform call over two chains, one launcher thread per chain and one for both -----------------------------------------------
+def _two_chain_case(sample):
+    """B = 18 through the row-settings entry: rows 0..8 (chain 0) capped near 30 columns, rows 9..17 (chain 1) near 10, no EOS set
+    -> (windows, their B = 1 uniform calls)"""
+    m, tok, n_samples = _t5_model(torch.float32)
+    kv = _cross_kv(m, n_samples, 4)
+    key = ("two_chains", sample)
+    if key not in _CACHE:
+        wins = []
+        for i in range(18):
+            gk = _gk(T5_TGT, max_length=(28 + i % 5) if i < 9 else (9 + i % 3), temperature=1.0 + 0.05 * (i % 3))
+            if sample:
+                gk.update(do_sample=True, top_p=0.9, seed=4321, seed_call_index=i)
+            wins.append(_Window(i % 4, _prompt(tok, 3, seed=80 + i), gk))
+        _CACHE[key] = (wins, [_uniform(m, tok, kv, w, T5_TGT) for w in wins])
+    return (m, tok, kv) + _CACHE[key]
+
+
+@pytest.mark.parametrize("sample", [False, True], ids=["greedy", "sampled"])
+def test_uniform_call_two_chains_one_launcher_or_two(sample):
+    """`mh_t5_generate_rows`, B = 18 = chains of 9 + 9 rows, poll_every = 4: chain 1 (caps near 10) stops at a poll long before chain 0
+    (caps near 30).  Under the engine option decode_launch_threads = 1 (a launcher thread per chain) and = 0 (one thread feeds both,
+    burst by burst) the ids and the returned column count are the same bits, and every row's ids are its B = 1 uniform call's."""
+    from mapperatorinator_amd import _lib
+    m, tok, kv, wins, refs = _two_chain_case(sample)
+    eng = m.engine
+    B = len(wins)
+    assert eng.lib.mh_t5_decode_chains_cfg(C.byref(eng.packed.cfg), B) == 2
+    entries = [_row_of(tok, w, T5_TGT) for w in wins]
+    sp = entries[0][0]
+    sp.max_length = T5_TGT
+    rows = (_lib.MhRowSampling * B)()
+    for b, (_, row, _) in enumerate(entries):
+        C.memmove(C.byref(rows, b * C.sizeof(row)), C.byref(row), C.sizeof(row))
+        rows[b].eos_set = b
+    tables = torch.stack([e[2] for e in entries])
+    prompt = torch.stack([w.prompt for w in wins]).to(eng.device, torch.int32)
+    kv_rows = kv[:, :, [w.kv_row for w in wins]].contiguous()
+    got = {}
+    for launch_threads in (1, 0):
+        with _launch_threads(eng, launch_threads):
+            assert eng.lib.mh_t5_decode_chains_cfg(C.byref(eng.packed.cfg), B) == 2
+            eng._enter()
+            with eng.on_stream():
+                tokens, n_out, _ = eng.decode(kv_rows, prompt, None, None, sp, poll_every=4, row_sampling=(sp, rows, tables))
+            eng._leave()
+            eng.synchronize()
+        got[launch_threads] = (tokens.cpu(), int(n_out.item()))
+    assert got[0][1] == got[1][1], f"returned columns: {got[1][1]} with a launcher per chain, {got[0][1]} with one"
+    assert torch.equal(got[0][0], got[1][0]), "the ids depend on decode_launch_threads"
+    lengths = [int(ids.shape[0]) for ids, _ in refs]
+    assert max(lengths[9:]) + 12 < min(lengths[:9]), lengths           # chain 1 is done at least three polls before chain 0
+    if sample:
+        greedy = _two_chain_case(False)[4]
+        assert any(not torch.equal(a[0], b[0]) for a, b in zip(refs, greedy)), "the sampled case must differ from the greedy one"
+    for launch_threads, (tokens, n_cols) in got.items():
+        assert n_cols == max(lengths), (launch_threads, n_cols, lengths)
+        for b, (ids, _) in enumerate(refs):
+            assert torch.equal(tokens[b, :lengths[b]].to(torch.int64), ids), \
+                f"decode_launch_threads = {launch_threads}: row {b} differs from its uniform call\n{tokens[b].tolist()}\n{ids.tolist()}"
 
 
 # ---- 4 / 5: the Whisper families ----------------------------------------------------------------------------------------------------
