@@ -680,7 +680,8 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
  *   step; the caller reads tokens[slot] before it admits the next window there.
  * mh_t5_slots_close: joins the chains and the admissions, releases the graph references, frees the session.
  * Ordering is by events alone (release -> admit -> first step): nothing on the device spins or waits for another launch.  One host
- * thread per session.  Not built: guidance pairs, beams, the e4m3 caches, teacher forcing, several rows per admission. */
+ * thread per session.  Not built: guidance pairs, beams, teacher forcing, several rows per admission; the e4m3 caches are a switch
+ * of the session (mh_t5_slots_open_kv8 below), not of this entry and not of a window. */
 int64_t mh_t5_slots_workspace_bytes(const MhT5Config* cfg, int S);
 int mh_t5_slots_open(const MhT5Config* cfg, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
                      const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
@@ -691,6 +692,39 @@ int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const in
 int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out, int32_t* length_out, int32_t* steps_out);
 int mh_t5_slots_release(void* handle, int slot);
 int mh_t5_slots_close(void* handle);
+
+/* In-flight slots over the e4m3 K/V caches (additive at ABI 11: one symbol; the session stays an opaque handle, no struct changes
+ * layout; a library without it is an older 11).  The argument list of mh_t5_slots_open, and the other mh_t5_slots_* entries serve the
+ * session as they are.  The caches belong to the SESSION -- allocated once for all S slots, captured in every chain's step graph
+ * (both pointers are in its key: a kv8 session and a plain one never share a graph) -- so no window can choose them.
+ *   sp->cross_kv_fp8  non-NULL: the caller-owned e4m3 copy of the slots' cross K/V, mh_t5_cross_kv_fp8_bytes(cfg, S) bytes in the
+ *                     layout of mh_t5_quantize_cross_kv(B = S).  It need not be initialised: every admission quantises its window's
+ *                     compact row into row `slot` (bytes and scales equal mh_t5_quantize_cross_kv(B = 1) of that row; no other row is
+ *                     written), and the token steps stream that row.
+ *   self_kv_fp8       non-NULL: the caller-owned shadow of the self-attention cache, mh_t5_self_kv_fp8_bytes(cfg, S) bytes in the
+ *                     layout of mh_t5_generate_skv8(B = S).  It need not be initialised: an admission quantises positions 0 .. P-2 of
+ *                     the slot's prefilled cache rows into the same places (nothing under option decode_prefill = 0), every token
+ *                     step appends its own row, and a row attends positions below its own only.
+ *   cross_kv_slots    may be NULL where sp->cross_kv_fp8 is given: then the session holds no bf16 copy of the slots' cross K/V at all
+ *                     (the admission's B = 1 prefill reads the caller's compact row).
+ *   Either copy or both.  With neither, the entry is mh_t5_slots_open.
+ * What a slot computes: the batch-1 call mh_t5_generate_rows(B = 1, the window's unpadded prompt and mask, rows[slot]) with the same
+ *   modes -- sp->cross_kv_fp8 = mh_t5_quantize_cross_kv(B = 1) of the window's row and / or a shadow of its own -- token ids and rows
+ *   of logits_dump, bit for bit; and the slot's rows of both copies hold, below the row's length, the bytes and scales of that call's.
+ * Kernels: the self-attention in its F8 slot form (dec_slot_self_attn_kernel<.., F8>: keys below the row's own position from shadow
+ *   row `slot` with their scales, its own key / value at storage precision, appended to the shadow by the same workgroup; an idle slot
+ *   returns before any store), the cross-attention's e4m3 form as it is (row-independent), one row quantiser per admission.
+ * Refused with MH_ERR_ARG and a message before any device call: fp32 storage with either copy, guidance, forced ids, n_cond > 0
+ *   without cond_per_row, S outside [1, 64], cross_kv_slots == NULL without sp->cross_kv_fp8, and whatever mh_t5_generate_rows /
+ *   mh_t5_generate_skv8 refuse.  mh_t5_slots_admit on such a session, on its admission stream, in this order: the bf16 copy into the
+ *   slot (where a bf16 slot buffer exists), the row quantiser, prompt and mask, the B = 1 prefill, the shadow's prompt rows, the
+ *   one-row init -- the position stays the last word an admission writes.
+ * Memory: the bf16 slot copy is n_dec * 2 * S * H * L * 64 * 2 bytes, the e4m3 one half of that plus 4 bytes per (plane, slot, head);
+ *   the shadow adds n_dec * 2 * S * H * tgt_len * 68 bytes beside the bf16 cache, which stays (the prefill and every append write it). */
+int mh_t5_slots_open_kv8(const MhT5Config* cfg, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                         const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                         const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                         void* stream, void** handle);
 
 /* (ABI 10) One beam-search step between two decoder positions as ONE kernel (csrc/beam.hip).  Replaces the per-step body of HF
  * `GenerationMixin._beam_search` (third-party, transformers >= 4.50's vectorised form) as the reference reaches it with

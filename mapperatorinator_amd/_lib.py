@@ -201,6 +201,9 @@ SYMBOLS = {
     "mh_t5_slots_workspace_bytes": (I64, [C.POINTER(MhT5Config), I]),
     "mh_t5_slots_open": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), I, C.POINTER(MhSampling), VP, VP, I, VP, VP, VP, VP, VP,
                              VP, I64, I, VP, C.POINTER(VP)]),
+    # ... over the session's e4m3 copies (sp->cross_kv_fp8 / self_kv_fp8: S-row buffers of the caller's; the same argument list)
+    "mh_t5_slots_open_kv8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), I, C.POINTER(MhSampling), VP, VP, I, VP, VP, VP, VP, VP,
+                                 VP, I64, I, VP, C.POINTER(VP)]),
     "mh_t5_slots_admit": (I, [VP, I, VP, VP, VP, I, VP]),
     "mh_t5_slots_run": (I, [VP, I, VP, VP, C.POINTER(I)]),
     "mh_t5_slots_release": (I, [VP, I]),

@@ -1103,6 +1103,10 @@ struct SelfKv8IdxP : SelfKv8P {
 struct SelfSlotP {
   const int* slot_pos;
 };
+// ... or both (F8 with SLOT, mh_t5_slots_open_kv8): row b attends shadow row b below its own position and appends there
+struct SelfKv8SlotP : SelfKv8P {
+  const int* slot_pos;
+};
 constexpr int kSelfIdxMaxTgt = 2560;   // table entries of one row staged in LDS (the released tgt_seq_len)
 
 // merge the NW waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
@@ -1385,11 +1389,14 @@ void dec_cross_attn_q_kernel(const float* h_, const float* lnw_, const void* W_,
 // can write a cache row that an admission is filling (the admission makes the entry non-negative last, and the chain waits for the
 // admission's event before the step that first sees it).  Everything else is the plain form of that row at that position: bias row,
 // RoPE row, j_first, the key-loop split, the new key merged last, the order of every sum -- the bits of a batch-1 call at *pos =
-// slot_pos[b].  The prompt mask is [rows][P] with P the stride of the slot's mask buffer (ones behind the row's own prompt).  Plain
-// bf16 / fp32 caches only: no F8, no IDX.
+// slot_pos[b].  The prompt mask is [rows][P] with P the stride of the slot's mask buffer (ones behind the row's own prompt).  No IDX.
+// F8 with SLOT (mh_t5_slots_open_kv8): the F8 row of the uniform call at the row's own position -- keys < slot_pos[b] from shadow row b
+// with their scales, the new key / value at storage precision, appended by waves 1 / 2 to shadow row b at slot_pos[b]; an idle slot
+// returns before the append too.  Every key below the position was written by this window's admission or by its own earlier steps,
+// so what an earlier window (or nobody) left in the row is never read.
 // The flag is on the kernel's BODY; the two kernels below are its entry points.  dec_self_attn_qkv_kernel keeps its six template
 // arguments -- its instantiations are a pinned list (tests/test_beam_self_kv_fp8_cpu.py) with pinned instruction bytes
-// (tools/device_code_diff.py) -- and the slot form is dec_slot_self_attn_kernel<T, KC, WH, LN>.
+// (tools/device_code_diff.py) -- and the slot form is dec_slot_self_attn_kernel<T, KC, WH, LN[, F8]>.
 template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false, bool IDX = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))   // 16 waves = 4 per SIMD: the whole 128-register budget
 void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_, const int* pos_,
@@ -1401,12 +1408,12 @@ void dec_self_attn_qkv_kernel(const float* h_, const float* lnw_, const void* W_
 #include "decode_self_attn_body.hpp"
 }
 // the slot form (SLOT above): the same arguments, the positions of the chain's rows behind them
-// (F8 / IDX / SLOT are template parameters only so that the body's `if constexpr` branches stay dependent: never given)
+// (IDX / SLOT are template parameters only so that the body's `if constexpr` branches stay dependent: never given)
 template <typename T, int KC, bool WH = false, bool LN = false, bool F8 = false, bool IDX = false, bool SLOT = true>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void dec_slot_self_attn_kernel(const float* h_, const float* lnw_, const void* W_, const int* pos_, const void* kc_, const void* vc_,
-                               int H_, int d_, SelfAttnP p, HeadProjP hp, typename std::conditional<SLOT, SelfSlotP, NoSelfKv8P>::type f8) {
-  static_assert(SLOT && !F8 && !IDX, "the slot form");
+                               int H_, int d_, SelfAttnP p, HeadProjP hp, typename std::conditional<F8, SelfKv8SlotP, SelfSlotP>::type f8) {
+  static_assert(SLOT && !IDX, "the slot form");
 #include "decode_self_attn_body.hpp"
 }
 

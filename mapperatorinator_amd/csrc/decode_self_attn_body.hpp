@@ -2,9 +2,9 @@
 // dec_slot_self_attn_kernel, which differ in the constant SLOT alone.  (A shared __device__ function -- inlined, arguments by value or
 // by reference -- compiled 112 to 142 of the 144 existing instantiations to other instruction bytes; the text does not.)  In scope where
 // it is included: T, KC, WH, LN, F8, IDX, SLOT; the kernel arguments h_, lnw_, W_, pos_, kc_, vc_, H_, d_, p, hp and f8 (the trailing
-// argument: the shadow rows, the index table, both, the slot positions, or nothing).
+// argument: the shadow rows, the index table, both, the slot positions, the shadow rows with the slot positions, or nothing).
   static_assert(!F8 || sizeof(T) == 2, "the e4m3 shadow cache is made of bf16 rows");
-  static_assert(!SLOT || (!F8 && !IDX), "the slot form reads the plain caches only");
+  static_assert(!SLOT || !IDX, "the slot form has no index table");
   hp.h = h_; hp.ln_w = lnw_; hp.W = W_; hp.ldh = d_; hp.ldw = d_; hp.d = d_;
   p.pos = pos_; p.kc = kc_; p.vc = vc_; p.H = H_;
   const int inner = H_ * 64;
@@ -47,6 +47,7 @@
     pos = f8.slot_pos[b];
     // an idle slot (the whole workgroup: the entry is one word): nothing is stored, no barrier was reached.  (An entry past the
     // cache cannot come from the sampler or the admission; it is refused here, so no content of the array can store out of bounds)
+    // F8: the append to the shadow is behind this return as well
     if (pos < 0 || pos >= p.tgt_len) return;
   } else {
     pos = *p.pos;

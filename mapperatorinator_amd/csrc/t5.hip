@@ -1245,13 +1245,22 @@ int launch_self_qkv(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inne
                          dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, cache);
     });
   };
-  if (slot_pos) {   // slot_pos != NULL: the SLOT instantiation, every row at its own position (mh_t5_slots_*): the plain caches only
-    MH_REQUIRE(!origin && !f8, "decode: the slot form of the self-attention has no e4m3 and no indexed cache");
-    const dec::SelfSlotP sl{slot_pos};
-    dispatch_attn_form(sa.rope, hp.ln_b, [&](auto wh, auto ln) {
-      hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, decltype(wh)::value, decltype(ln)::value>), dim3(sa.B * sa.H), dim3(1024), 0, s,
-                         MH_SELF_LEAD_ARGS, sa, hp, sl);
-    });
+  if (slot_pos) {   // slot_pos != NULL: the SLOT instantiation, every row at its own position (mh_t5_slots_*); with f8 as well, the
+                    // F8 + SLOT one: every row over its own shadow row (mh_t5_slots_open_kv8)
+    MH_REQUIRE(!origin, "decode: the slot form of the self-attention has no indexed cache");
+    auto slot = [&](auto f8c, const auto& cache) {
+      dispatch_attn_form(sa.rope, hp.ln_b, [&](auto wh, auto ln) {
+        hipLaunchKernelGGL((dec::dec_slot_self_attn_kernel<T, KC, decltype(wh)::value, decltype(ln)::value, decltype(f8c)::value>),
+                           dim3(sa.B * sa.H), dim3(1024), 0, s, MH_SELF_LEAD_ARGS, sa, hp, cache);
+      });
+    };
+    if (!f8) {
+      slot(std::false_type{}, dec::SelfSlotP{slot_pos});
+    } else if constexpr (sizeof(T) == 2) {
+      dec::SelfKv8SlotP sl8{};
+      sl8.k8 = f8->k8; sl8.v8 = f8->v8; sl8.ks = f8->ks; sl8.vs = f8->vs; sl8.slot_pos = slot_pos;
+      slot(std::true_type{}, sl8);
+    } else { set_error("decode: the e4m3 self-attention cache needs bf16 storage"); return MH_ERR_ARG; }
   } else if (origin) {   // with f8 as well: the shadow rows and their scales through the table (mh_t5_step_indexed_skv8)
     MH_REQUIRE(sa.tgt_len <= dec::kSelfIdxMaxTgt, "decode: the indexed self-attention stages at most %d table entries (tgt_len %d)",
                dec::kSelfIdxMaxTgt, sa.tgt_len);
@@ -1731,6 +1740,47 @@ __global__ __launch_bounds__(256) void kv_quant_fp8_kernel(const bf16_t* src, ui
     d8[i] = make_uint2((uint32_t)o0, (uint32_t)o1);
   }
 }
+// The same for ONE row of an S-row copy (mh_t5_slots_admit over a session of mh_t5_slots_open_kv8): workgroup (plane, h) of a window's
+// compact cross K/V [n_dec][2][1][H][L][64] -> unit plane * S H + slot H + h of cross_kv8_layout(c, S), bytes and scale alike.  A
+// kernel of its own (kv_quant_fp8_kernel keeps its instruction bytes) with the statements of the one above in their order: the bytes
+// and scales mh_t5_quantize_cross_kv(B = 1) makes of that row (pinned by tests/test_gpu_inflight_kv8.py).  No other row is written.
+__global__ __launch_bounds__(256) void kv_quant_fp8_row_kernel(const bf16_t* src, uint8_t* dst, float* scales, int L, int H, int S, int slot) {
+  __shared__ float red[4];
+  const long plane = blockIdx.x / H, h = blockIdx.x % H;
+  const long unit = (plane * S + slot) * H + h;
+  const uint4* s16 = reinterpret_cast<const uint4*>(src + (long)blockIdx.x * L * 64);
+  const int n16 = L * 8;
+  float mx = 0.f;
+  for (int i = threadIdx.x; i < n16; i += 256) {
+    const uint4 v = s16[i];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      mx = fmaxf(mx, fabsf(__uint_as_float(w[j] << 16)));
+      mx = fmaxf(mx, fabsf(__uint_as_float(w[j] & 0xffff0000u)));
+    }
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float scale = mx > 0.f ? mx / 448.0f : 1.0f;
+  const float inv = 1.0f / scale;
+  if (threadIdx.x == 0) scales[unit] = scale;
+  uint2* d8 = reinterpret_cast<uint2*>(dst + unit * L * 64);
+  for (int i = threadIdx.x; i < n16; i += 256) {
+    const uint4 v = s16[i];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(w[j] << 16) * inv; f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u) * inv; }
+    int o0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    o0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], o0, true);
+    int o1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    o1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], o1, true);
+    d8[i] = make_uint2((uint32_t)o0, (uint32_t)o1);
+  }
+}
 
 extern "C" int64_t mh_t5_cross_kv_fp8_bytes(const MhT5Config* c, int B) {
   mh::OptionScope option_scope(c ? c->options : nullptr);
@@ -2093,7 +2143,7 @@ static void chain_call(const GenerateArgs& a, const DecodeLayout& ly, int ci, in
   step_call_init(k, c, a.w);
   k->Bc = (b0 + rows_per <= B) ? rows_per : B - b0;
   k->Bfull = B; k->kvB = cfg ? B / 2 : B; k->P = P; k->with_sampler = 1;
-  k->cross_kv = (const char*)a.cross_kv + (long)b0 * H * c->src_len * 64 * es;
+  k->cross_kv = a.cross_kv ? (const char*)a.cross_kv + (long)b0 * H * c->src_len * 64 * es : nullptr;   // (NULL: a kv8 slot session without one)
   k->prompt_mask = a.prompt_mask ? a.prompt_mask + (long)b0 * P : nullptr;
   if (a.rowset) { k->has_rows = 1; k->rows.rows = a.rowset->rows; k->rows.eos_tables = a.rowset->eos_tables; k->rows.n_eos_sets = a.rowset->n_eos_sets; }
   DecBuffers& bf = k->bf;
@@ -2271,7 +2321,8 @@ struct SlotSession {
   DecodeLayout ly{};
   int32_t* pos = nullptr; int32_t* plen = nullptr; uint8_t* mask = nullptr;   // [S], [S], [S][max_length]
   char* prefill_base = nullptr; int64_t prefill_bytes = 0;
-  char* cross_kv = nullptr; int32_t* tokens = nullptr;
+  char* cross_kv = nullptr; int32_t* tokens = nullptr;   // cross_kv: the bf16 / fp32 slot copy, NULL where the steps stream cross8 alone
+  uint8_t* cross8 = nullptr; uint8_t* self8 = nullptr;   // mh_t5_slots_open_kv8: the caller's S-row e4m3 copies, or NULL
   Chain chains[kMaxChains];
   StepCall calls[kMaxChains];
   hipStream_t admit_stream = nullptr;
@@ -2313,13 +2364,14 @@ extern "C" int64_t mh_t5_slots_workspace_bytes(const MhT5Config* c, int S) {
   return mh::slots_layout(c, S, nullptr, nullptr);
 }
 
-extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
-                                const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
-                                const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
-                                void* stream, void** handle) {
-  using namespace mh;
+namespace mh {
+// mh_t5_slots_open (kv8 = false: the e4m3 caches are refused) and mh_t5_slots_open_kv8 (kv8 = true: sp->cross_kv_fp8 / self_kv_fp8 are
+// the session's S-row copies, filled row by row by the admissions and the token steps)
+static int slots_open_impl(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                           const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                           const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                           void* stream, void** handle, bool kv8, const char* who) {
   OptionScope option_scope(c ? c->options : nullptr);
-  const char* who = "mh_t5_slots_open";
   MH_TRY(check_cfg(c, who));
   MH_REQUIRE(handle, "%s: null argument (handle)", who);
   *handle = nullptr;
@@ -2328,11 +2380,18 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   MH_REQUIRE(sp, "%s: null argument (sp)", who);
   MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
   MH_REQUIRE(!forced, "%s: teacher forcing (forced ids) has no slot form", who);
-  MH_REQUIRE(!sp->cross_kv_fp8, "%s: the e4m3 copy of the cross K/V (cross_kv_fp8) has no slot form", who);
-  MH_REQUIRE(!self_kv_fp8, "%s: the e4m3 shadow of the self-attention cache has no slot form", who);
+  if (!kv8) {
+    MH_REQUIRE(!sp->cross_kv_fp8, "%s: the e4m3 copy of the cross K/V (cross_kv_fp8) has no slot form", who);
+    MH_REQUIRE(!self_kv_fp8, "%s: the e4m3 shadow of the self-attention cache has no slot form", who);
+  } else {
+    MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
+    MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "%s: the e4m3 self-attention cache needs bf16 storage", who);
+    MH_REQUIRE(cross_kv_slots || sp->cross_kv_fp8,
+               "%s: null argument (cross_kv_slots may be NULL only where sp->cross_kv_fp8 is the slots' e4m3 copy)", who);
+  }
   MH_REQUIRE(sp->n_cond == 0 || sp->cond_per_row, "%s: conditional temperature rules need cond_per_row = 1 (every slot is a window of its own)", who);
   // whatever mh_t5_generate_rows refuses of a configuration and its settings (the prompt length is each admission's)
-  MH_TRY(check_decode_call(c, w, sp, S, cross_kv_slots && tokens && workspace, stream, nullptr, true, who));
+  MH_TRY(check_decode_call(c, w, sp, S, (cross_kv_slots || (kv8 && sp->cross_kv_fp8)) && tokens && workspace, stream, nullptr, true, who));
   MH_REQUIRE(workspace_bytes >= slots_layout(c, S, nullptr, nullptr), "%s: workspace too small (mh_t5_slots_workspace_bytes)", who);
   MH_TRY(check_arch2_weights(c, w, who));
   hipStream_t s = (hipStream_t)stream;
@@ -2342,6 +2401,7 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   std::unique_ptr<SlotSession> ss(new SlotSession());
   ss->c = c; ss->w = w; ss->S = S; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
   ss->cross_kv = (char*)cross_kv_slots; ss->tokens = tokens;
+  ss->cross8 = (uint8_t*)sp->cross_kv_fp8; ss->self8 = (uint8_t*)self_kv_fp8;   // (both NULL behind mh_t5_slots_open)
   slots_layout(c, S, workspace, ss.get());
   ss->n_chains = pick_chains(S);
   ss->rows_per = ceil_div(S, ss->n_chains);
@@ -2358,8 +2418,10 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   }
   const RowSetP rowset{rows, eos_tables, n_eos_sets};
   GenerateArgs a{c, w, cross_kv_slots, S, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
-                 workspace_bytes, poll_every, stream, nullptr, &rowset, who};
-  ss->n_chains = chain_calls(a, ss->ly, ss->n_chains, ss->rows_per, nullptr, ss->calls);   // prompt_mask: the slot mask rows, stride max_length (call.P)
+                 workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, who};
+  // prompt_mask: the slot mask rows, stride max_length (call.P); the chains' rows of both e4m3 copies (both pointers are in the key
+  // of the step graph: a kv8 session and a plain one never share a graph)
+  ss->n_chains = chain_calls(a, ss->ly, ss->n_chains, ss->rows_per, ss->self8, ss->calls);
   for (int ci = 0; ci < ss->n_chains; ++ci) {
     StepCall& call = ss->calls[ci];
     call.slot_pos = ss->pos; call.slot_plen = ss->plen;
@@ -2374,6 +2436,25 @@ extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S
   if (hipStreamSynchronize(s) != hipSuccess) return check_launch("slot open");
   *handle = ss.release();
   return MH_OK;
+}
+}  // namespace mh
+
+extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                                const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                                const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                                void* stream, void** handle) {
+  return mh::slots_open_impl(c, w, S, sp, rows, eos_tables, n_eos_sets, cross_kv_slots, tokens, logits_dump, forced, self_kv_fp8, workspace,
+                             workspace_bytes, poll_every, stream, handle, false, "mh_t5_slots_open");
+}
+
+extern "C" int mh_t5_slots_open_kv8(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                                    const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                                    const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                                    void* stream, void** handle) {
+  // with neither copy this is mh_t5_slots_open (which then refuses a NULL cross_kv_slots as ever)
+  const bool kv8 = (sp && sp->cross_kv_fp8) || self_kv_fp8;
+  return mh::slots_open_impl(c, w, S, sp, rows, eos_tables, n_eos_sets, cross_kv_slots, tokens, logits_dump, forced, self_kv_fp8, workspace,
+                             workspace_bytes, poll_every, stream, handle, kv8, "mh_t5_slots_open_kv8");
 }
 
 extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
@@ -2399,9 +2480,14 @@ extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_ro
   }
   // the window's compact cross K/V [n_dec][2][1][H][L][64] -> row `slot` of [n_dec][2][S][H][L][64]
   const size_t row_bytes = (size_t)H * c->src_len * 64 * es;
-  if (hipMemcpy2DAsync(ss->cross_kv + (size_t)slot * row_bytes, (size_t)ss->S * row_bytes, cross_kv_row, row_bytes, row_bytes,
-                       (size_t)c->n_dec_layers * 2, hipMemcpyDeviceToDevice, as) != hipSuccess)
+  if (ss->cross_kv && hipMemcpy2DAsync(ss->cross_kv + (size_t)slot * row_bytes, (size_t)ss->S * row_bytes, cross_kv_row, row_bytes, row_bytes,
+                                       (size_t)c->n_dec_layers * 2, hipMemcpyDeviceToDevice, as) != hipSuccess)
     return check_launch("admit cross K/V copy");
+  if (ss->cross8) {   // ... and, quantised, -> row `slot` of the S-row e4m3 copy (bytes and scales; no other row is touched)
+    hipLaunchKernelGGL(kv_quant_fp8_row_kernel, dim3(c->n_dec_layers * 2 * H), dim3(256), 0, as, (const bf16_t*)cross_kv_row, ss->cross8,
+                       reinterpret_cast<float*>(ss->cross8 + cross_kv8_layout(c, ss->S).scales_offset), c->src_len, H, ss->S, slot);
+    MH_TRY(check_launch("kv_quant_fp8_row_kernel"));
+  }
   int32_t* trow = ss->tokens + (long)slot * ss->max_length;
   uint8_t* mrow = ss->mask + (long)slot * ss->max_length;
   if (hipMemcpyAsync(trow, prompt, (size_t)P * 4, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit prompt copy");
@@ -2415,6 +2501,15 @@ extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_ro
     MH_TRY(prefill_prompt(c, ss->w, cross_kv_row, 1, 1, prompt, prompt_mask, P, P - 1, (char*)ss->ly.bf.self_k + cache_row,
                           (char*)ss->ly.bf.self_v + cache_row, pb, as, ss->S));
     start_pos = P - 1;
+    if (ss->self8) {   // the prefilled positions 0 .. P-2 of the slot's cache rows -> the same places of the S-row shadow, every layer,
+                       // k and v (the pass a uniform call makes after its prefill); nothing else of the shadow is written
+      const long row0 = (long)slot * H * c->tgt_len, plane_rows = (long)ss->S * H * c->tgt_len;
+      hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)(((long)H * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, as,
+                         (const bf16_t*)ss->ly.bf.self_k + row0 * 64, (const bf16_t*)ss->ly.bf.self_v + row0 * 64, ss->self8 + row0 * 64,
+                         reinterpret_cast<float*>(ss->self8 + self_kv8_layout(c, ss->S).scales_offset) + row0, (long)H, (long)start_pos,
+                         (long)c->tgt_len, plane_rows);
+      MH_TRY(check_launch("self_kv_quant_rows_kernel"));
+    }
   }
   const SampleP& smp = ss->calls[ci].smp;
   if (c->dtype == MH_BF16) hipLaunchKernelGGL(dec_slot_init_kernel<bf16_t>, dim3(1), dim3(256), 0, as, smp, slot, P, start_pos, ss->pos, ss->plen);

@@ -56,9 +56,14 @@ def _left_pad(rows, pad_id: int, dtype):
 
 class SequentialWindowScheduler:
     def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32, merge_kwargs: bool = False,
-                 inflight: bool = False, inflight_steps: int = 16):
+                 inflight: bool = False, inflight_steps: int = 16, inflight_kv_fp8: Optional[str] = None):
         if decode_batch > 64 or decode_batch < 1:
             raise ValueError("decode_batch must be in [1, 64] (32 at most when windows run under classifier-free guidance)")
+        if inflight_kv_fp8 not in self._INFLIGHT_KV_FP8:
+            raise ValueError(f"inflight_kv_fp8={inflight_kv_fp8!r}: expected None, 'cross', 'self' or 'both'")
+        if inflight_kv_fp8 is not None and not inflight:
+            raise ValueError(f"inflight_kv_fp8={inflight_kv_fp8!r} is a switch of the slot session: it needs inflight=True (a wave takes "
+                             "cross_kv_fp8 / self_kv_fp8 from its generate_kwargs)")
         self.model, self.tokenizer = model, tokenizer
         self.engine = model.engine
         self.encode_batch, self.decode_batch = int(encode_batch), int(decode_batch)
@@ -72,6 +77,11 @@ class SequentialWindowScheduler:
         # admitted as soon as its window w was delivered, into whatever slot is idle, while the other slots keep stepping;
         # `inflight_steps` token steps run between two looks at the slots.  See `_run_inflight`.
         self.inflight, self.inflight_steps = bool(inflight), max(1, int(inflight_steps))
+        # inflight_kv_fp8 (off by default): the e4m3 caches of the slot SESSION (T5Engine.open_slots(cross_kv_fp8=, self_kv_fp8=)): the
+        # copies are allocated once for all slots and captured in the chains' step graphs, so they are chosen here, where the session
+        # is chosen, and not by a job or a window.  fp32 storage is refused now, before anything is encoded.
+        self.inflight_kv_fp8 = dict(zip(("cross_kv_fp8", "self_kv_fp8"), self._INFLIGHT_KV_FP8[inflight_kv_fp8]))
+        DecodeModes.of(self.inflight_kv_fp8, getattr(self.engine, "dtype", None))
 
     # ---- stage 1: everything that depends on the audio only ------------------------------------------------
     @torch.no_grad()
@@ -198,6 +208,7 @@ class SequentialWindowScheduler:
                 self._decode_group(jobs, kvs, w, rows[a:a + step], pad_id, merged=True)
 
     # ---- stage 2, in flight: slots instead of waves ----------------------------------------------------------------------------
+    _INFLIGHT_KV_FP8 = {None: (False, False), "cross": (True, False), "self": (False, True), "both": (True, True)}
     _INFLIGHT_REFUSED = (("num_beams", lambda gk: int(gk.get("num_beams", 1) or 1) > 1, "beam search"),
                          ("cfg_scale", lambda gk: float(gk.get("cfg_scale", 1.0)) > 1.0, "classifier-free guidance"),
                          ("cross_kv_fp8", lambda gk: bool(gk.get("cross_kv_fp8", False)), "the e4m3 copy of the cross K/V"),
@@ -209,7 +220,8 @@ class SequentialWindowScheduler:
         for name, on, words in self._INFLIGHT_REFUSED:
             if on(gk):
                 raise ValueError(f"inflight: {what} asks for {words} ({name}={gk.get(name)!r}), which has no slot form: "
-                                 "run it with inflight=False")
+                                 "run it with inflight=False"
+                                 + (" (the e4m3 caches of a slot session are the scheduler's switch: inflight_kv_fp8)" if name.endswith("_kv_fp8") else ""))
 
     def _inflight_row(self, probe: list, gk: dict, sp0=None):
         """One window's kwargs -> (per-call settings, its row entry, its EOS table), built TOGETHER with the session's probe list so
@@ -232,8 +244,8 @@ class SequentialWindowScheduler:
         through `on_result` (per song strictly in order; across songs in no order), into the lowest idle slot, songs first come first
         served; every row decodes under its own kwargs (`build_row_sampling`), as the default policy's batch-1 call for that window
         would: explicit seeds with this scheduler's own call counter, RNG row 0, no left padding (so no redo path).  The per-call
-        settings (`row_call_key`) must agree over all jobs; beams, guidance, the fp8 caches and injected samplers are refused --
-        both before anything is encoded."""
+        settings (`row_call_key`) must agree over all jobs; beams, guidance, the fp8 caches as a job's or a window's kwargs (they
+        are the session's: `inflight_kv_fp8`) and injected samplers are refused -- both before anything is encoded."""
         eng, tok = self.engine, self.tokenizer
         keys = set()
         for n, j in enumerate(jobs):
@@ -269,7 +281,8 @@ class SequentialWindowScheduler:
                     probe.append(entry)
         sp0 = build_row_sampling(tok, probe, self.model.config.max_target_positions)[0]
         sp0.max_length = int(self.model.config.max_target_positions)
-        slots = eng.open_slots(S, sp0)
+        # (a switch at its default is not passed: engines written against the narrower signature keep working)
+        slots = eng.open_slots(S, sp0, **{k: True for k, on in self.inflight_kv_fp8.items() if on})
         occupant = [None] * S                       # slot -> (job, window, ask, admitted at)
         ready = list(range(len(jobs)))              # songs whose next window may enter, first come first served
         next_w = [0] * len(jobs)

@@ -498,14 +498,19 @@ class T5Engine:
             _lib.check(self.lib.mh_t5_generate(*args), "mh_t5_generate")
         return tokens, n_out, logits
 
-    def open_slots(self, S: int, sampling: _lib.MhSampling, dump_logits: bool = False, poll_every: int = 16) -> "DecodeSlots":
+    def open_slots(self, S: int, sampling: _lib.MhSampling, dump_logits: bool = False, poll_every: int = 16,
+                   cross_kv_fp8: bool = False, self_kv_fp8: bool = False) -> "DecodeSlots":
         """In-flight decode (`mh_t5_slots_*`, contract in include/mapperhip.h): S slots, every slot a row that decodes a window of
         its own; a finished row's place goes to the next window while its neighbours keep stepping.  `sampling`: the per-call
         settings (`server.build_row_sampling(...)[0]`; `max_length` = the longest window the session can hold).  Returns a
-        `DecodeSlots` with `admit`, `run`, `take` and `close`.  Greedy and sampled rows, per-row settings; no guidance, beams,
-        e4m3 caches or teacher forcing (refused by the library).  One session per engine at a time: its buffers live in this
-        engine's workspaces like the row-settings ones, so their pointers -- part of the step graph's key -- do not move."""
-        return DecodeSlots(self, int(S), sampling, dump_logits, poll_every)
+        `DecodeSlots` with `admit`, `run`, `take` and `close`.  Greedy and sampled rows, per-row settings; no guidance, beams
+        or teacher forcing (refused by the library).  One session per engine at a time: its buffers live in this
+        engine's workspaces like the row-settings ones, so their pointers -- part of the step graph's key -- do not move.
+        `cross_kv_fp8` / `self_kv_fp8`: switches of the SESSION (`mh_t5_slots_open_kv8`; bf16 storage only): the token steps stream
+        an S-row e4m3 copy of the slots' cross K/V, which every admission fills for its slot -- the session then holds no bf16 copy
+        of it at all -- and / or attend an S-row e4m3 shadow of the self-attention cache.  A slot then computes what the batch-1
+        `decode` computes under the same switches, bit for bit."""
+        return DecodeSlots(self, int(S), sampling, dump_logits, poll_every, cross_kv_fp8, self_kv_fp8)
 
     def quantize_kv_rows(self, rows: torch.Tensor):
         """`mh_quantize_kv_rows`: bf16 (..., 64) on the device -> (e4m3 bytes uint8 (..., 64), fp32 scales (...)), the row form of the
@@ -628,11 +633,13 @@ class DecodeSlots:
     A slot computes what `T5Engine.decode(row_sampling=...)` computes for the window alone (B = 1, its unpadded prompt, its own
     row entry), bit for bit.  `stats`: admissions and graph replays so far."""
 
-    def __init__(self, engine: "T5Engine", S: int, sampling: _lib.MhSampling, dump_logits: bool, poll_every: int):
+    def __init__(self, engine: "T5Engine", S: int, sampling: _lib.MhSampling, dump_logits: bool, poll_every: int,
+                 cross_kv_fp8: bool = False, self_kv_fp8: bool = False):
         if not 1 <= S <= 64:
             raise ValueError(f"open_slots: {S} slots not in [1, 64]")
         if getattr(engine, "_slot_session", None) is not None:
             raise RuntimeError("open_slots: this engine has an open slot session (its buffers are the engine's): close it first")
+        self.modes = DecodeModes.of(dict(cross_kv_fp8=cross_kv_fp8, self_kv_fp8=self_kv_fp8), engine.dtype)   # (the storage refusals)
         self.engine, self.S, self.sampling = engine, S, sampling
         self._handle = C.c_void_p()
         p = engine.packed
@@ -651,7 +658,15 @@ class DecodeSlots:
         self._eos_d = engine._workspace("slot_eos_tables", 64 * p.vocab_out)
         self._rows_d.zero_()
         self._eos_d.zero_()
-        self.cross_kv = engine._workspace("slot_cross_kv", d.n_dec_layers * 2 * S * d.n_heads * p.src_len * 64 * es)
+        # the slots' cross K/V: the bf16 / fp32 copy, or -- cross_kv_fp8 -- the e4m3 one alone (no token step would read the other);
+        # the e4m3 shadow of the self-attention cache.  Neither e4m3 buffer is initialised: the admissions and the steps fill them
+        self.cross_kv = self.cross_kv8 = self.self_kv8 = None
+        if self.modes.cross_kv_fp8:
+            self.cross_kv8 = engine._workspace("slot_cross_kv8", lib.mh_t5_cross_kv_fp8_bytes(C.byref(p.cfg), S))
+        else:
+            self.cross_kv = engine._workspace("slot_cross_kv", d.n_dec_layers * 2 * S * d.n_heads * p.src_len * 64 * es)
+        if self.modes.self_kv_fp8:
+            self.self_kv8 = engine._workspace("slot_skv8", lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), S))
         self.tokens = engine._workspace("slot_tokens", 64 * p.tgt_len * 4)[:S * maxlen * 4].view(torch.int32).view(S, maxlen)
         self.logits = None
         if dump_logits:
@@ -664,14 +679,18 @@ class DecodeSlots:
         self._finished = [False] * S
         self.live = [False] * S
         self.stats = dict(admissions=0, steps=0, runs=0)
+        kv8 = self.cross_kv8 is not None or self.self_kv8 is not None
+        entry = "mh_t5_slots_open_kv8" if kv8 else "mh_t5_slots_open"        # the new entry only when a switch is on
+        sampling.cross_kv_fp8 = _lib.ptr(self.cross_kv8)
         engine._enter()
         try:
-            _lib.check(lib.mh_t5_slots_open(C.byref(p.cfg), C.byref(p.w), S, C.byref(sampling), self._rows_d.data_ptr(),
-                                            self._eos_d.data_ptr(), 64, self.cross_kv.data_ptr(), self.tokens.data_ptr(),
-                                            _lib.ptr(self.logits), None, None, ws.data_ptr(), ws.numel(), int(poll_every), engine._s(),
-                                            C.byref(self._handle)), "mh_t5_slots_open")
+            _lib.check(getattr(lib, entry)(C.byref(p.cfg), C.byref(p.w), S, C.byref(sampling), self._rows_d.data_ptr(),
+                                           self._eos_d.data_ptr(), 64, _lib.ptr(self.cross_kv), self.tokens.data_ptr(),
+                                           _lib.ptr(self.logits), None, _lib.ptr(self.self_kv8), ws.data_ptr(), ws.numel(), int(poll_every),
+                                           engine._s(), C.byref(self._handle)), entry)
         finally:
             engine._leave()
+            sampling.cross_kv_fp8 = None      # (the session has read it: the caller's settings stay those of a plain call)
         engine._slot_session = self
 
     def admit(self, slot: int, cross_kv_row: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
