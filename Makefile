@@ -4,7 +4,8 @@ ARCH ?= gfx950
 CSRC := mapperatorinator_amd/csrc
 OBJDIR := build/obj
 LIB := mapperatorinator_amd/lib/libmapperhip.so
-SRCS := $(CSRC)/api.hip $(CSRC)/gemm.hip $(CSRC)/mx8.hip $(CSRC)/norm.hip $(CSRC)/attention.hip $(CSRC)/mel.hip $(CSRC)/conv.hip $(CSRC)/t5.hip $(CSRC)/beam.hip $(CSRC)/dit.hip $(CSRC)/slider.hip $(CSRC)/score.hip
+SRCS := $(CSRC)/api.hip $(CSRC)/gemm.hip $(CSRC)/mx8.hip $(CSRC)/norm.hip $(CSRC)/attention.hip $(CSRC)/mel.hip $(CSRC)/conv.hip \
+	$(CSRC)/t5_encode.hip $(CSRC)/t5.hip $(CSRC)/t5_generate.hip $(CSRC)/t5_stepwise.hip $(CSRC)/beam.hip $(CSRC)/dit.hip $(CSRC)/slider.hip $(CSRC)/score.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/mapperhip.h
 # -amdgpu-kernarg-preload-count: leading scalar kernel arguments arrive in SGPRs with the wave launch (gfx950 firmware)
@@ -44,9 +45,13 @@ prof: $(PROF_LIB)
 variant:
 	@mkdir -p build/var_$(NAME)
 	for f in $(SRCS); do b=$$(basename $$f .hip); x=; if [ $$b = attention ]; then x="$(EXTRA_attention)"; fi; $(HIPCC) $(HIPFLAGS) $$x $(DEFS) -c $$f -o build/var_$(NAME)/$$b.o & done; wait
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/var_$(NAME)/*.o -o mapperatorinator_amd/lib/libmapperhip_$(NAME).so
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(patsubst $(CSRC)/%.hip,build/var_$(NAME)/%.o,$(SRCS)) -o mapperatorinator_amd/lib/libmapperhip_$(NAME).so
 
 clean:
 	rm -rf build $(LIB) $(PROF_LIB)
 
-.PHONY: all clean prof variant
+# the units, one per line-separated word: tools/build_variant.sh takes its object list from here
+print-srcs:
+	@echo $(SRCS)
+
+.PHONY: all clean prof variant print-srcs

@@ -20,6 +20,7 @@
 #pragma once
 #include <type_traits>
 
+#include "decode_step.hpp"   // kSelfIdxMaxTgt, which the host entries check too
 #include "internal.hpp"
 
 namespace mh {
@@ -1107,7 +1108,6 @@ struct SelfSlotP {
 struct SelfKv8SlotP : SelfKv8P {
   const int* slot_pos;
 };
-constexpr int kSelfIdxMaxTgt = 2560;   // table entries of one row staged in LDS (the released tgt_seq_len)
 
 // merge the NW waves' partial (m, l, acc[64]) through LDS; threads 0..63 return the merged (m, l, a[d])
 template <typename T, int NW = 4>

@@ -1,457 +1,21 @@
-// osuT5 on MI355X: encoder stack, cross-attention K/V projection and the KV-cached AR decode loop.
-// Orchestration lives here (C++), so that the per-token loop never returns to Python: every decode
-// step is one hipGraph replay; the host only polls a 4-byte "rows still running" word.
+// osuT5 on MI355X: the token step of the KV-cached AR decode.  The ONE unit that instantiates the decode kernels
+// (decode_kernels.hpp), the sampler / init kernels and the e4m3 K/V quantisers.  It holds every launcher of them,
+// enqueue_step() -- one step of one chain, what a step graph captures -- the decode workspace layout and the measurement
+// hooks that live inside the step.  The other units reach it through decode_step.hpp: the batched passes are t5_encode.hip,
+// the generation loop and the slot session t5_generate.hip, the step-wise entries of beam search t5_stepwise.hip.
 //
 // Reference semantics reproduced (see include/mapperhip.h for the per-entry citations):
-//   HF T5Stack / T5Block / T5Attention / T5LayerFF (pre-norm residual blocks, shared layer-0 relative
-//   bias, no 1/sqrt(d) scaling, gated gelu_new FFN), HF GenerationMixin._sample under
-//   model_generate (osuT5/osuT5/inference/server.py:83-156) with the reference logits processors.
+//   HF T5Block / T5Attention / T5LayerFF and the Whisper family's decoder layers, one position at a time;
+//   HF GenerationMixin._sample's selection with the reference logits processors (dec_sample_kernel).
 #include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <vector>
 
 #include "decode_kernels.hpp"
-
-namespace mh {
-namespace {
-
-inline int es_of(int dtype) { return dtype == MH_BF16 ? 2 : 4; }
-
-int check_cfg(const MhT5Config* c, const char* who) {
-  MH_REQUIRE(c, "%s: null config", who);
-  MH_REQUIRE(c->d_kv == 64, "%s: d_kv must be 64 (got %d)", who, c->d_kv);
-  MH_REQUIRE(c->n_enc_layers <= MH_MAX_LAYERS && c->n_dec_layers <= MH_MAX_LAYERS, "%s: too many layers", who);
-  MH_REQUIRE(c->d_model % 32 == 0 && c->d_ff % 32 == 0, "%s: d_model/d_ff must be multiples of 32", who);
-  MH_REQUIRE(c->n_mels_pad % 32 == 0 && c->n_mels_pad >= c->n_mels, "%s: bad n_mels_pad", who);
-  MH_REQUIRE(c->dtype == MH_F32 || c->dtype == MH_BF16, "%s: bad dtype", who);
-  MH_REQUIRE(c->arch >= 0 && c->arch <= 2, "%s: arch %d is none of 0 (T5), 1 (VarWhisper / RoPEWhisper), 2 (HF Whisper)", who, c->arch);
-  MH_REQUIRE(c->dec_pos_from_mask == 0 || c->arch == 2, "%s: dec_pos_from_mask belongs to arch 2 (absolute decoder positions)", who);
-  if (c->arch >= 1) {
-    MH_REQUIRE(c->d_model == c->n_heads * 64, "%s: the Whisper family needs d_model = 64 heads", who);
-    MH_REQUIRE(c->in_frames >= 1 && c->src_len == (c->in_frames - 1) / 2 + 1, "%s: src_len must be the conv-strided in_frames", who);
-    MH_REQUIRE(c->attn_scale > 0.f, "%s: attn_scale must be positive", who);
-  }
-  MH_REQUIRE(c->enc_operand_dtype == 0 || c->enc_operand_dtype == MH_MX8, "%s: enc_operand_dtype must be 0 or MH_MX8", who);
-  if (c->enc_operand_dtype == MH_MX8)
-    MH_REQUIRE(c->dtype == MH_BF16 && c->arch == 0 && c->d_model % 128 == 0 && c->d_ff % 128 == 0,
-               "%s: MX-fp8 encoder operands need bf16 storage, the T5 backbone and d_model / d_ff multiples of 128", who);
-  return MH_OK;
-}
-// the token step's attention kernels project their own q (/ k / v) from the whole residual row: d_model = 128 KC, KC in 1..8
-// (mh_t5_generate, mh_t5_step, mh_t5_cross_attn_probe; the encoder, cross K/V and teacher-forced forward take any shape check_cfg does)
-int check_decode_shape(const MhT5Config* c, const char* who) {
-  MH_REQUIRE(c->d_model % 128 == 0 && c->d_model >= 128 && c->d_model <= 1024,
-             "%s: the decode step needs d_model a multiple of 128 in [128, 1024] (got %d)", who, c->d_model);
-  return MH_OK;
-}
-inline bool enc_mx(const MhT5Config* c) { return c->enc_operand_dtype == MH_MX8; }
-inline int64_t mx_operand_bytes(int64_t rows, int K) { return align256(rows * K) + align256(rows * mx8_scale_row_bytes(K)); }
-// the pre-norm of a block: T5LayerNorm / nn.RMSNorm (arch 0 / 1) or the affine nn.LayerNorm of HF Whisper (arch 2, bias != NULL there)
-inline int pre_norm(const MhT5Config* c, const float* x, const float* w, const float* b, void* y, int rows, int out_dtype, hipStream_t s) {
-  if (c->arch == 2) {
-    MH_REQUIRE(b, "arch 2 needs the LayerNorm biases (MhT5Weights.*_ln*_b)");
-    return layernorm(x, c->d_model, w, b, y, c->d_model, rows, c->d_model, c->eps, out_dtype, s);
-  }
-  return rmsnorm(x, c->d_model, w, y, c->d_model, rows, c->d_model, c->eps, out_dtype, s);
-}
-inline bool is_local_layer(const MhT5Config* c, int l) { return c->arch == 1 && c->local_every > 1 && c->local_window > 0 && l % c->local_every != 0; }
-
-#define MH_TRY(expr)              \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != MH_OK) return _rc; \
-  } while (0)
-
-// f(a value of the storage type): one call site for both instantiations of a kernel or launcher (`using T = decltype(t)`)
-template <typename F>
-auto dispatch_dtype(int dtype, F&& f) { return dtype == MH_BF16 ? f(bf16_t{}) : f(float{}); }
-// f(std::integral_constant<int, KC>) for d_model = 128 KC of the attention kernels that project their own q (/ k / v), KC in 1..7;
-// any other d_model runs KC = 8 (check_decode_shape guards the range)
-template <int KC = 1, typename F>
-int dispatch_kc(int d, F&& f) {
-  if constexpr (KC == 8) return f(std::integral_constant<int, 8>{});
-  else return d == 128 * KC ? f(std::integral_constant<int, KC>{}) : dispatch_kc<KC + 1>(d, f);
-}
-// THE form table.  A decode attention kernel exists in exactly three forms, (rotary / scaled scores, affine LayerNorm) =
-//   (false, false)  T5: bias-free projections behind an RMS norm, relative position bias, unscaled scores
-//   (true,  false)  rotary Whisper: biased fused projections, RoPE, scaled scores, optional window
-//   (true,  true)   HF Whisper (arch 2): the same behind an affine LayerNorm, identity rotary table
-// f(std::bool_constant, std::bool_constant) with one of these three pairs; (false, true) is no model and is never instantiated
-template <typename F>
-void dispatch_attn_form(bool rope_or_scaled, bool ln_b, F&& f) {
-  if (rope_or_scaled && ln_b) f(std::true_type{}, std::true_type{});
-  else if (rope_or_scaled) f(std::true_type{}, std::false_type{});
-  else f(std::false_type{}, std::false_type{});
-}
-int check_arch2_weights(const MhT5Config* c, const MhT5Weights* w, const char* who) {
-  MH_REQUIRE(c->arch != 2 || (w->dec_pos && w->dec_final_ln_b), "%s: arch 2 needs decoder.embed_positions and the LayerNorm biases", who);
-  return MH_OK;
-}
-
-// The packed e4m3 copies the token steps stream, laid out HERE and nowhere else: 2 n_dec_layers planes (layer, k | v) of `n` units of
-// `unit_bytes` e4m3 bytes, then -- 256-byte aligned -- one fp32 scale per unit, plane by plane
-struct Kv8Layout {
-  int64_t plane_bytes, plane_scales;   // one plane: its e4m3 bytes, its scales
-  int64_t scales_offset, total;        // bytes from the start of the copy to its scales, bytes of the whole copy
-  int64_t data(int l, int kv) const { return (int64_t)(l * 2 + kv) * plane_bytes; }     // byte offset of plane (l, kv)
-  int64_t scale(int l, int kv) const { return (int64_t)(l * 2 + kv) * plane_scales; }   // index of its first scale
-};
-inline Kv8Layout kv8_layout(const MhT5Config* c, int64_t n, int64_t unit_bytes) {
-  const int64_t planes = 2 * (int64_t)c->n_dec_layers, data = align256(planes * n * unit_bytes);
-  return {n * unit_bytes, n, data, data + align256(planes * n * 4)};
-}
-// cross K/V of kvB rows (mh_t5_quantize_cross_kv): a unit = one (row, head) slab of src_len x 64; the shadow of the self-attention
-// cache of B rows (mh_t5_generate_skv8): a unit = one cached row of 64 at (row, head, position)
-inline Kv8Layout cross_kv8_layout(const MhT5Config* c, int kvB) { return kv8_layout(c, (int64_t)kvB * c->n_heads, (int64_t)c->src_len * 64); }
-inline Kv8Layout self_kv8_layout(const MhT5Config* c, int B) { return kv8_layout(c, (int64_t)B * c->n_heads * c->tgt_len, 64); }
-
-}  // namespace
-}  // namespace mh
+#include "decode_step.hpp"
 
 using namespace mh;
-
-// ------------------------------------------------------------------------------------------------
-// encoder
-// ------------------------------------------------------------------------------------------------
-extern "C" int64_t mh_t5_encode_workspace_bytes(const MhT5Config* c, int B) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0) return -1;
-  const int64_t rows = (int64_t)B * c->src_len, es = es_of(c->dtype);
-  const int inner = c->n_heads * 64, Lpad = round_up(c->src_len, 64);
-  int64_t t = 0;
-  if (c->arch >= 1)   // front-end scratch + its output (storage type) in front of the layer buffers
-    t += align256(mh_whisper_frontend_workspace_bytes(B, c->in_frames, c->arch == 2 ? c->d_model : c->n_mels_pad, c->d_model, c->dtype)) +
-         align256(rows * c->d_model * es);
-  if (c->arch == 2)   // encoder_embedder output in front of conv1: fp32 accumulator rows + their storage-typed copy
-    t += align256((int64_t)B * c->in_frames * c->d_model * 4) + align256((int64_t)B * c->in_frames * c->d_model * es);
-  t += align256(rows * c->d_model * 4);                    // h
-  t += align256(rows * c->d_model * es);                   // n
-  t += align256(rows * 2 * inner * es);                    // qk
-  t += align256((int64_t)B * inner * Lpad * es);           // vt
-  t += align256(rows * inner * es);                        // attn
-  t += align256(rows * c->d_ff * es);                      // ff
-  if (c->enc_operand_dtype == MH_MX8)                      // MX-fp8 copy of the current GEMM's A operand (widest: d_ff columns)
-    t += mx_operand_bytes(rows, c->d_ff > c->d_model ? c->d_ff : c->d_model);
-  return t;
-}
-
-namespace mh {
-namespace {
-// fp32 residual stream <- storage-typed rows (the conv front-end's output)
-template <typename T>
-__global__ __launch_bounds__(256) void rows_to_f32_kernel(const T* __restrict__ x, float* __restrict__ h, long n) {
-  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i + 3 < n) {
-    *reinterpret_cast<float4*>(h + i) = make_float4(Elem<T>::to_f32(x[i]), Elem<T>::to_f32(x[i + 1]), Elem<T>::to_f32(x[i + 2]), Elem<T>::to_f32(x[i + 3]));
-  } else {
-    for (long j = i; j < n; ++j) h[j] = Elem<T>::to_f32(x[j]);
-  }
-}
-// storage-typed rows <- fp32 rows (arch 2: encoder_embedder's output becomes conv1's operand)
-template <typename T>
-__global__ __launch_bounds__(256) void f32_to_rows_kernel(const float* __restrict__ h, T* __restrict__ x, long n) {
-  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i + 3 < n) {
-    const float4 v = *reinterpret_cast<const float4*>(h + i);
-    x[i] = Elem<T>::from_f32(v.x); x[i + 1] = Elem<T>::from_f32(v.y); x[i + 2] = Elem<T>::from_f32(v.z); x[i + 3] = Elem<T>::from_f32(v.w);
-  } else {
-    for (long j = i; j < n; ++j) x[j] = Elem<T>::from_f32(h[j]);
-  }
-}
-// rotate-half RoPE in place on the q | k block of a QKV GEMM output (apply_rotary_pos_emb,
-// osuT5/osuT5/model/custom_transformers/modeling_varwhisper.py:229-258): row r = b * L + position, 2H head slots of 64
-// columns; one thread rotates 8 pairs (i, i + 32): two 16-byte (bf16) / four (fp32) accesses each way.
-// rope fp32 [L][64] = cos(32) | sin(32).
-template <typename T>
-__global__ __launch_bounds__(256) void rope_qk_kernel(T* __restrict__ qk, int ld, long rows, int L, int slots, const float* __restrict__ rope) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;       // (row, slot, chunk of 8 pairs)
-  const long total = rows * slots * 4;
-  if (idx >= total) return;
-  const int c = (int)(idx & 3);
-  const long rs = idx >> 2;
-  const int slot = (int)(rs % slots);
-  const long row = rs / slots;
-  const int pos = (int)(row % L);
-  T* x1 = qk + row * ld + slot * 64 + c * 8;
-  T* x2 = x1 + 32;
-  const float* cs = rope + (long)pos * 64 + c * 8;
-  float a[8], b[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { a[i] = Elem<T>::to_f32(x1[i]); b[i] = Elem<T>::to_f32(x2[i]); }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float co = cs[i], si = cs[32 + i];
-    x1[i] = Elem<T>::from_f32(a[i] * co - b[i] * si);
-    x2[i] = Elem<T>::from_f32(b[i] * co + a[i] * si);
-  }
-}
-
-// rotate-half RoPE in place on the cached keys of positions 0 .. np-1: kc [BH][tgt][64], one thread per (bh, pos, 8 pairs)
-template <typename T>
-__global__ __launch_bounds__(256) void rope_cache_kernel(T* __restrict__ kc, long BH, int tgt, int np, const float* __restrict__ rope) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= BH * np * 4) return;
-  const int c = (int)(idx & 3);
-  const long rp = idx >> 2;
-  const int pos = (int)(rp % np);
-  const long bh = rp / np;
-  T* x1 = kc + (bh * tgt + pos) * 64 + c * 8;
-  T* x2 = x1 + 32;
-  const float* cs = rope + (long)pos * 64 + c * 8;
-  float a[8], b[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { a[i] = Elem<T>::to_f32(x1[i]); b[i] = Elem<T>::to_f32(x2[i]); }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const float co = cs[i], si = cs[32 + i];
-    x1[i] = Elem<T>::from_f32(a[i] * co - b[i] * si);
-    x2[i] = Elem<T>::from_f32(b[i] * co + a[i] * si);
-  }
-}
-
-// h[b * L + t][:] = row_bias[b][:]  (the conditioning embedders' contribution, constant along a chunk's frames)
-__global__ __launch_bounds__(256) void fill_rows_kernel(float* __restrict__ h, const float* __restrict__ row_bias, int L, int d) {
-  const long row = blockIdx.x;
-  const float4* src = reinterpret_cast<const float4*>(row_bias + (row / L) * d);
-  float4* dst = reinterpret_cast<float4*>(h + row * d);
-  for (int i = threadIdx.x; i < d / 4; i += 256) dst[i] = src[i];
-}
-}  // namespace
-}  // namespace mh
-
-extern "C" int mh_t5_encode(const MhT5Config* c, const MhT5Weights* w, const void* mel, int B, void* enc_out,
-                            float* enc_out_f32, void* workspace, int64_t workspace_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return mh_t5_encode_cond(c, w, mel, B, nullptr, enc_out, enc_out_f32, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mh_t5_encode_cond(const MhT5Config* c, const MhT5Weights* w, const void* mel, int B, const float* row_bias,
-                                 void* enc_out, float* enc_out_f32, void* workspace, int64_t workspace_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_encode"));
-  MH_REQUIRE(w && mel && enc_out && workspace && B > 0, "mh_t5_encode: null argument");
-  MH_REQUIRE(workspace_bytes >= mh_t5_encode_workspace_bytes(c, B), "mh_t5_encode: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int L = c->src_len, d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff;
-  const int rows = B * L, es = es_of(c->dtype), Lpad = round_up(L, 64);
-  Arena ar(workspace, workspace_bytes);
-  if (c->arch >= 1) {
-    // ---- VarWhisperEncoder.forward (modeling_varwhisper.py:779-852) / RoPEWhisperEncoder.forward (modeling_ropewhisper.py:
-    // 1167-1278); arch 2: HF WhisperEncoder.forward behind the wrapper's encoder_embedder ---------------------------------
-    const bool hf = c->arch == 2;
-    MH_REQUIRE(hf || !row_bias, "mh_t5_encode: arch 1 takes its conditioning as conv1 input channels (mh_cond_channels), not as a row bias");
-    MH_REQUIRE(w->conv1_w && w->conv1_b && w->conv2_w && w->conv2_b, "mh_t5_encode: arch 1 / 2 need the conv front-end weights");
-    MH_REQUIRE(hf || w->enc_rope, "mh_t5_encode: arch 1 needs the rotary table");
-    MH_REQUIRE(!hf || (w->enc_embed_w && w->enc_pos && w->enc_final_ln_b), "mh_t5_encode: arch 2 needs encoder_embedder, embed_positions and the LayerNorm biases");
-    const int fe_C = hf ? d : c->n_mels_pad;
-    const int64_t fe_bytes = mh_whisper_frontend_workspace_bytes(B, c->in_frames, fe_C, d, c->dtype);
-    void* fe_ws = ar.take(fe_bytes);
-    void* x0 = ar.take((int64_t)rows * d * es);
-    const int64_t rows_in = (int64_t)B * c->in_frames;
-    float* hin = hf ? (float*)ar.take(rows_in * d * 4) : nullptr;
-    void* xin = hf ? ar.take(rows_in * d * es) : nullptr;
-    float* h = (float*)ar.take((int64_t)rows * d * 4);
-    void* n = ar.take((int64_t)rows * d * es);
-    void* qk = ar.take((int64_t)rows * 2 * inner * es);
-    void* vt = ar.take((int64_t)B * inner * Lpad * es);
-    void* attn = ar.take((int64_t)rows * inner * es);
-    void* ff = ar.take((int64_t)rows * dff * es);
-    MH_REQUIRE(ar.ok() && ff, "mh_t5_encode: arena overflow");
-    const void* fe_in = mel;
-    if (hf) {
-      // input_features = encoder_embedder([mel | cond]) (modeling_mapperatorinator.py:204-205,211): the T5 path's projection
-      // (row_bias = the conditioning columns' contribution incl. the bias), rounded to the storage type = conv1's operand
-      MH_REQUIRE(xin != nullptr, "mh_t5_encode: arena overflow");
-      MhGemm ge = MhGemm{};
-      ge.A = mel; ge.lda = c->n_mels_pad; ge.W = w->enc_embed_w; ge.ldw = c->n_mels_pad; ge.C = hin; ge.ldc = d;
-      ge.M = (int)rows_in; ge.N = d; ge.K = c->n_mels_pad; ge.bias = w->enc_embed_b; ge.dtype = c->dtype; ge.epilogue = MH_EPI_STORE_F32;
-      if (row_bias) {
-        hipLaunchKernelGGL(mh::fill_rows_kernel, dim3((unsigned)rows_in), dim3(256), 0, s, hin, row_bias, c->in_frames, d);
-        MH_TRY(check_launch("fill_rows_kernel"));
-        ge.bias = nullptr; ge.epilogue = MH_EPI_RESID;
-      }
-      MH_TRY(gemm(ge, s));
-      const long n_in = (long)rows_in * d;
-      if (c->dtype == MH_BF16) hipLaunchKernelGGL(mh::f32_to_rows_kernel<bf16_t>, dim3((unsigned)((n_in / 4 + 255) / 256 + 1)), dim3(256), 0, s, hin, (bf16_t*)xin, n_in);
-      else hipLaunchKernelGGL(mh::f32_to_rows_kernel<float>, dim3((unsigned)((n_in / 4 + 255) / 256 + 1)), dim3(256), 0, s, hin, (float*)xin, n_in);
-      MH_TRY(check_launch("f32_to_rows_kernel"));
-      fe_in = xin;
-    }
-    MH_TRY(mh_whisper_frontend(fe_in, B, c->in_frames, fe_C, w->conv1_w, w->conv1_b, w->conv2_w, w->conv2_b, hf ? w->enc_pos : nullptr, d, x0,
-                               fe_ws, fe_bytes, c->dtype, stream));
-    const long nel = (long)rows * d;
-    if (c->dtype == MH_BF16) hipLaunchKernelGGL(mh::rows_to_f32_kernel<bf16_t>, dim3((unsigned)((nel / 4 + 255) / 256 + 1)), dim3(256), 0, s, (const bf16_t*)x0, h, nel);
-    else hipLaunchKernelGGL(mh::rows_to_f32_kernel<float>, dim3((unsigned)((nel / 4 + 255) / 256 + 1)), dim3(256), 0, s, (const float*)x0, h, nel);
-    MH_TRY(check_launch("rows_to_f32_kernel"));
-    if (hipMemsetAsync(vt, 0, (size_t)B * inner * Lpad * es, s) != hipSuccess) return check_launch("memset vt");
-    MhGemm g;
-    for (int l = 0; l < c->n_enc_layers; ++l) {
-      const bool local = is_local_layer(c, l);
-      MH_TRY(pre_norm(c, h, w->enc_ln1[l], w->enc_ln1_b[l], n, rows, c->dtype, s));
-      g = MhGemm{};
-      g.A = n; g.lda = d; g.W = w->enc_qkv[l]; g.ldw = d; g.C = qk; g.ldc = 2 * inner; g.M = rows; g.N = 3 * inner;
-      g.K = d; g.bias = w->enc_qkv_b[l]; g.dtype = c->dtype; g.epilogue = MH_EPI_QKV_VT; g.C2 = vt; g.n_split = 2 * inner;
-      g.kv_B = B; g.kv_H = H; g.kv_L = L; g.kv_Lpad = Lpad;
-      MH_TRY(gemm(g, s));
-      if (!hf) {   // (HF Whisper: absolute positions were added by the front-end, no rotation)
-        const float* rope = (local && w->enc_rope_local) ? w->enc_rope_local : w->enc_rope;
-        const long work = (long)rows * 2 * H * 4;
-        if (c->dtype == MH_BF16) hipLaunchKernelGGL(mh::rope_qk_kernel<bf16_t>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, (bf16_t*)qk, 2 * inner, (long)rows, L, 2 * H, rope);
-        else hipLaunchKernelGGL(mh::rope_qk_kernel<float>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, (float*)qk, 2 * inner, (long)rows, L, 2 * H, rope);
-        MH_TRY(check_launch("rope_qk_kernel"));
-      }
-      MH_TRY(attention(qk, 2 * inner, inner, vt, Lpad, nullptr, attn, inner, B, L, H, c->attn_scale, local ? -c->local_window : 0, c->dtype, s));
-      g = MhGemm{};
-      g.A = attn; g.lda = inner; g.W = w->enc_o[l]; g.ldw = inner; g.C = h; g.ldc = d; g.M = rows; g.N = d; g.K = inner;
-      g.bias = w->enc_o_b[l]; g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
-      MH_TRY(gemm(g, s));
-      MH_TRY(pre_norm(c, h, w->enc_ln2[l], w->enc_ln2_b[l], n, rows, c->dtype, s));
-      MH_REQUIRE(w->enc_fc1_b[l] && w->enc_fc2_b[l], "mh_t5_encode: fc1 / fc2 carry biases in the Whisper family");
-      g = MhGemm{};
-      g.A = n; g.lda = d; g.W = w->enc_wi[l]; g.ldw = d; g.C = ff; g.ldc = dff; g.M = rows; g.N = dff; g.K = d;
-      g.bias = w->enc_fc1_b[l]; g.dtype = c->dtype; g.epilogue = MH_EPI_BIAS_GELU_ERF;
-      MH_TRY(gemm(g, s));
-      g = MhGemm{};
-      g.A = ff; g.lda = dff; g.W = w->enc_wo[l]; g.ldw = dff; g.C = h; g.ldc = d; g.M = rows; g.N = d; g.K = dff;
-      g.bias = w->enc_fc2_b[l]; g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
-      MH_TRY(gemm(g, s));
-    }
-    MH_TRY(pre_norm(c, h, w->enc_final_ln, w->enc_final_ln_b, enc_out, rows, c->dtype, s));
-    if (enc_out_f32) MH_TRY(pre_norm(c, h, w->enc_final_ln, w->enc_final_ln_b, enc_out_f32, rows, MH_F32, s));
-    return MH_OK;
-  }
-  float* h = (float*)ar.take((int64_t)rows * d * 4);
-  void* n = ar.take((int64_t)rows * d * es);
-  void* qk = ar.take((int64_t)rows * 2 * inner * es);
-  void* vt = ar.take((int64_t)B * inner * Lpad * es);
-  void* attn = ar.take((int64_t)rows * inner * es);
-  void* ff = ar.take((int64_t)rows * dff * es);
-  const bool mx = enc_mx(c);
-  const int kmax = dff > d ? dff : d;
-  uint8_t* xq = mx ? (uint8_t*)ar.take((int64_t)rows * kmax) : nullptr;                       // e4m3 bytes of the current A operand
-  uint8_t* xs = mx ? (uint8_t*)ar.take((int64_t)rows * mx8_scale_row_bytes(kmax)) : nullptr;  // its E8M0 scales
-  MH_REQUIRE(ar.ok() && ff && (!mx || xs), "mh_t5_encode: arena overflow");
-  if (mx) {
-    MH_REQUIRE(w->dec_ckv_all_mx && w->dec_ckv_all_mxs, "mh_t5_encode: enc_operand_dtype = MH_MX8 needs the MX-fp8 weight copies");
-    for (int l = 0; l < c->n_enc_layers; ++l)
-      MH_REQUIRE(w->enc_qkv_mx[l] && w->enc_qkv_mxs[l] && w->enc_o_mx[l] && w->enc_o_mxs[l] && w->enc_wi_mx[l] && w->enc_wi_mxs[l] &&
-                     w->enc_wo_mx[l] && w->enc_wo_mxs[l], "mh_t5_encode: enc_operand_dtype = MH_MX8 needs the MX-fp8 weight copies (layer %d)", l);
-  }
-  if (hipMemsetAsync(vt, 0, (size_t)B * inner * Lpad * es, s) != hipSuccess) return check_launch("memset vt");
-
-  MhGemm g;
-  // h = encoder_embedder(mel)      (modeling_mapperatorinator.py:195-196)
-  g = MhGemm{};
-  g.A = mel; g.lda = c->n_mels_pad; g.W = w->enc_embed_w; g.ldw = c->n_mels_pad; g.C = h; g.ldc = d;
-  g.M = rows; g.N = d; g.K = c->n_mels_pad; g.bias = w->enc_embed_b; g.dtype = c->dtype; g.epilogue = MH_EPI_STORE_F32;
-  if (row_bias) {
-    // conditioning: [mel | cond] @ W^T + b = mel @ W[:, :n_mels]^T + (cond @ W[:, n_mels:]^T + b); the bracket is the
-    // caller's per-chunk row_bias [B, d] (it already contains b), laid under the mel product
-    MH_REQUIRE(d % 4 == 0, "mh_t5_encode_cond: d_model must be a multiple of 4");
-    hipLaunchKernelGGL(mh::fill_rows_kernel, dim3(rows), dim3(256), 0, s, h, row_bias, L, d);
-    MH_TRY(check_launch("fill_rows_kernel"));
-    g.bias = nullptr; g.epilogue = MH_EPI_RESID;
-  }
-  MH_TRY(gemm(g, s));
-
-  // MX-fp8 operands (enc_operand_dtype = MH_MX8): the A operand of each projection is the e4m3 + E8M0 copy in xq / xs -- written
-  // by the RMSNorm itself (the bf16 rounding of the storage mode applied first, so the quantiser sees what the bf16 path multiplies),
-  // or by a pass over the bf16 buffer the attention / the gated GELU wrote
-  auto operand = [&](MhGemm& gg, const void* a_plain, int K, const void* w_plain, const uint8_t* w_mx, const uint8_t* w_mxs) {
-    if (mx) { gg.A = xq; gg.lda = K; gg.a_scale = xs; gg.W = w_mx; gg.ldw = K; gg.w_scale = w_mxs; gg.dtype = MH_MX8; }
-    else { gg.A = a_plain; gg.lda = K; gg.W = w_plain; gg.ldw = K; gg.dtype = c->dtype; }
-  };
-  for (int l = 0; l < c->n_enc_layers; ++l) {
-    if (mx) MH_TRY(rmsnorm_mx8(h, d, w->enc_ln1[l], rows, d, c->eps, MH_BF16, xq, d, xs, s));
-    else MH_TRY(rmsnorm(h, d, w->enc_ln1[l], n, d, rows, d, c->eps, c->dtype, s));
-    g = MhGemm{};
-    operand(g, n, d, w->enc_qkv[l], w->enc_qkv_mx[l], w->enc_qkv_mxs[l]);
-    g.C = qk; g.ldc = 2 * inner; g.M = rows; g.N = 3 * inner;
-    g.K = d; g.epilogue = MH_EPI_QKV_VT; g.C2 = vt; g.n_split = 2 * inner; g.kv_B = B; g.kv_H = H;
-    g.kv_L = L; g.kv_Lpad = Lpad;
-    MH_TRY(gemm(g, s));
-    MH_TRY(attention(qk, 2 * inner, inner, vt, Lpad, w->enc_rel_bias, attn, inner, B, L, H, 1.0f, 0, c->dtype, s));
-    if (mx) MH_TRY(quantize_mx8(attn, inner, rows, inner, MH_BF16, xq, inner, xs, s));
-    g = MhGemm{};
-    operand(g, attn, inner, w->enc_o[l], w->enc_o_mx[l], w->enc_o_mxs[l]);
-    g.C = h; g.ldc = d; g.M = rows; g.N = d; g.K = inner; g.epilogue = MH_EPI_RESID;
-    MH_TRY(gemm(g, s));
-    if (mx) MH_TRY(rmsnorm_mx8(h, d, w->enc_ln2[l], rows, d, c->eps, MH_BF16, xq, d, xs, s));
-    else MH_TRY(rmsnorm(h, d, w->enc_ln2[l], n, d, rows, d, c->eps, c->dtype, s));
-    g = MhGemm{};
-    operand(g, n, d, w->enc_wi[l], w->enc_wi_mx[l], w->enc_wi_mxs[l]);
-    g.C = ff; g.ldc = dff; g.M = rows; g.N = 2 * dff; g.K = d; g.epilogue = MH_EPI_GEGLU;
-    // MX mode: the gated GELU leaves the GEMM as the MX-fp8 operand of wo (the bytes mh_quantize_mx8 would make of the bf16
-    // hidden) -- into the second operand buffer: xq / xs still hold this GEMM's own A operand
-    const bool mx_fused = mx && dff % 128 == 0;
-    uint8_t* xq2 = reinterpret_cast<uint8_t*>(ff);                 // (the bf16 hidden is not written then: its buffer holds the MX image)
-    uint8_t* xs2 = xq2 + (int64_t)rows * dff;
-    if (mx_fused) {
-      if (dff % 512) MH_REQUIRE(hipMemsetAsync(xs2, 0, (size_t)rows * mx8_scale_row_bytes(dff), s) == hipSuccess, "mh_t5_encode: scale reset failed");
-      g.mx_out = xq2; g.mx_out_scales = xs2; g.ldc = dff;
-    }
-    MH_TRY(gemm(g, s));
-    if (mx && !mx_fused) MH_TRY(quantize_mx8(ff, dff, rows, dff, MH_BF16, xq, dff, xs, s));
-    g = MhGemm{};
-    operand(g, ff, dff, w->enc_wo[l], w->enc_wo_mx[l], w->enc_wo_mxs[l]);
-    if (mx_fused) { g.A = xq2; g.a_scale = xs2; }
-    g.C = h; g.ldc = d; g.M = rows; g.N = d; g.K = dff; g.epilogue = MH_EPI_RESID;
-    MH_TRY(gemm(g, s));
-  }
-  MH_TRY(rmsnorm(h, d, w->enc_final_ln, enc_out, d, rows, d, c->eps, c->dtype, s));
-  if (enc_out_f32) MH_TRY(rmsnorm(h, d, w->enc_final_ln, enc_out_f32, d, rows, d, c->eps, MH_F32, s));
-  return MH_OK;
-}
-
-extern "C" int64_t mh_t5_cross_kv_workspace_bytes(const MhT5Config* c, int B) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0) return -1;
-  return c->enc_operand_dtype == MH_MX8 ? mx_operand_bytes((int64_t)B * c->src_len, c->d_model) : 0;
-}
-
-extern "C" int mh_t5_cross_kv_ws(const MhT5Config* c, const MhT5Weights* w, const void* enc_out, int B, void* cross_kv, void* workspace,
-                                 int64_t workspace_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_cross_kv"));
-  MH_REQUIRE(w && enc_out && cross_kv && B > 0, "mh_t5_cross_kv: null argument");
-  if (!enc_mx(c)) return mh_t5_cross_kv(c, w, enc_out, B, cross_kv, stream);
-  MH_REQUIRE(workspace && workspace_bytes >= mh_t5_cross_kv_workspace_bytes(c, B), "mh_t5_cross_kv_ws: workspace too small");
-  MH_REQUIRE(w->dec_ckv_all_mx && w->dec_ckv_all_mxs, "mh_t5_cross_kv_ws: enc_operand_dtype = MH_MX8 needs dec_ckv_all_mx / _mxs");
-  hipStream_t s = (hipStream_t)stream;
-  const int inner = c->n_heads * 64, d = c->d_model, rows = B * c->src_len;
-  Arena ar(workspace, workspace_bytes);
-  uint8_t* xq = (uint8_t*)ar.take((int64_t)rows * d);
-  uint8_t* xs = (uint8_t*)ar.take((int64_t)rows * mx8_scale_row_bytes(d));
-  MH_REQUIRE(ar.ok() && xs, "mh_t5_cross_kv_ws: arena overflow");
-  MH_TRY(quantize_mx8(enc_out, d, rows, d, MH_BF16, xq, d, xs, s));
-  MhGemm g = MhGemm{};
-  g.A = xq; g.lda = d; g.a_scale = xs; g.W = w->dec_ckv_all_mx; g.ldw = d; g.w_scale = w->dec_ckv_all_mxs; g.C = cross_kv; g.ldc = 0;
-  g.M = rows; g.N = c->n_dec_layers * 2 * inner; g.K = d; g.dtype = MH_MX8;
-  g.epilogue = MH_EPI_KV_SCATTER; g.kv_B = B; g.kv_H = c->n_heads; g.kv_L = c->src_len;
-  return gemm(g, s);
-}
-
-extern "C" int mh_t5_cross_kv(const MhT5Config* c, const MhT5Weights* w, const void* enc_out, int B, void* cross_kv,
-                              void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_cross_kv"));
-  MH_REQUIRE(w && enc_out && cross_kv && B > 0, "mh_t5_cross_kv: null argument");
-  MH_REQUIRE(!enc_mx(c), "mh_t5_cross_kv: enc_operand_dtype = MH_MX8 needs scratch for the quantised encoder output: call mh_t5_cross_kv_ws");
-  const int inner = c->n_heads * 64;
-  MhGemm g = MhGemm{};
-  g.A = enc_out; g.lda = c->d_model; g.W = w->dec_ckv_all; g.ldw = c->d_model; g.C = cross_kv; g.ldc = 0;
-  g.M = B * c->src_len; g.N = c->n_dec_layers * 2 * inner; g.K = c->d_model; g.dtype = c->dtype;
-  g.bias = c->arch >= 1 ? w->dec_ckv_b_all : nullptr;
-  g.epilogue = MH_EPI_KV_SCATTER; g.kv_B = B; g.kv_H = c->n_heads; g.kv_L = c->src_len;
-  return gemm(g, (hipStream_t)stream);
-}
 
 // ------------------------------------------------------------------------------------------------
 // decode
@@ -459,43 +23,6 @@ extern "C" int mh_t5_cross_kv(const MhT5Config* c, const MhT5Weights* w, const v
 namespace mh {
 namespace {
 
-struct DecState {       // device-resident control block
-  int pos;              // index of the token being fed this step
-  int n_running;        // rows not yet finished (written by the sampler)
-  int tail_err;         // != 0: a hand-off of dec_tail_kernel gave up (bounded wait); read by the host right after n_running
-  int ticket;           // arrival counter of the sampler's workgroups (the last one advances `pos`)
-  unsigned rng_row0;    // MhSampling.rng_row0 and .seed of the running call: written by dec_init_kernel and read from here by
-  unsigned long long seed;   // the sampler, so that the replayed step graph does not carry them (they change call by call)
-  // dec_tail_kernel's hand-off counters, one 128-byte line per layer parity: zeroed by dec_init_kernel, then only ever added to
-  alignas(128) unsigned tail_cnt[2][32];
-};
-
-struct SampleP {
-  const float* logits; int ldl; int V;
-  int32_t* tokens; int max_length;    // [B, max_length]
-  const int32_t* forced;
-  const uint8_t* eos_table;
-  uint8_t* finished;                  // [B]
-  int32_t* finish_col;                // [B]
-  int32_t* last_ts_val;               // [B] value of the last TIME_SHIFT after the last SOS, -1 if none
-  float* logits_dump;                 // [max_length][R][V] or null   (R = returned rows: B, or B/2 with CFG)
-  float* proc;                        // [R][V] processed scores of this step (read back by the sampling passes)
-  float* hist_scores;                 // [2][R][V] scores entering LookbackBias at this / the previous step
-  const void* dec_embed; float* h; int d;
-  // arch 2 (HF Whisper): decoder.embed_positions fp32 [tgt_len][d] added to the token embedding (NULL otherwise); pos_off [B] =
-  // masked prompt columns of each row when MhT5Config.dec_pos_from_mask (written by dec_init_kernel), NULL = cache positions
-  const float* dec_pos; int32_t* pos_off; const uint8_t* prompt_mask;
-  MhSampling sp;
-  DecState* st;
-  int B, P;                           // B = rows of the WHOLE batch
-  int b0;                             // first global row of this chain; logits / h / ss are chain-local
-  int pair;                           // CFG: distance between the negative-prompt row g and its prompt row g + pair
-                                      //      (= B/2, single chain); 0 = no guidance
-  int chain_rows;                     // rows of this chain (both halves under CFG)
-};
-
-// dec_sample_kernel's trailing argument: the row settings of mh_t5_generate_rows (the ROWS instantiations), or nothing
-struct RowSetP { const MhRowSampling* rows; const uint8_t* eos_tables; int n_eos_sets; };
 struct NoRowSetP {};
 // ... or those of an in-flight decode (the SLOT instantiation, mh_t5_slots_*): the row settings, and what is the row's own there instead
 // of the call's -- pos [S]: the position slot b is fed at this step (negative: the slot is idle), advanced by the row's own workgroup;
@@ -1120,8 +647,6 @@ int skinny_resid(const dec::SkinnyP& p, hipStream_t s) {
   return p.bias ? skinny<T, dec::PRO_PLAIN, dec::SK_RESID, true>(p, s) : skinny<T, dec::PRO_PLAIN, dec::SK_RESID>(p, s);
 }
 
-constexpr int kMaxChains = 8;
-
 // ---- the three-GEMV tail of a layer as one launch (option decode_fused_tail; dec::dec_tail_kernel) ---------------------
 std::atomic<long> g_tail_launches{0};   // dec_tail_kernel nodes enqueued (captured or launched) by this process: mh_t5_decode_tail_launches
 template <typename T> int gemv_waves(int K) { return K / (4 * (16 / (int)sizeof(T))) > 4 * dec::kGemvCH ? 8 : 4; }   // launch_skinny's rule
@@ -1188,23 +713,7 @@ int launch_tail(dec::TailP p, DecState* st, int layer, int n_chains, hipStream_t
   return launch_tail_mf<T, 2, PROWI, EPIWI, BIAS>(p, s);
 }
 
-struct DecBuffers {
-  float* h; void* attn; void* ff; float* logits; int chain;
-  void* self_k; void* self_v;  // [n_dec][B][H][tgt][64]
-  uint8_t* finished; int32_t* finish_col; int32_t* last_ts; DecState* st;
-  // the caller's e4m3 shadow of the self-attention cache (mh_t5_generate_skv8), else NULL: e4m3 [n_dec][2][B][H][tgt][64] and its
-  // fp32 scales [n_dec][2][B][H][tgt].  Non-NULL selects the F8 self-attention kernel (and, being part of this struct, is part of
-  // the step graph's cache key)
-  uint8_t* self8; float* self8_scales;
-};
-
-// The decode workspace of B rows (mh_t5_decode_workspace_bytes): the one description of its slabs, read by mh_t5_generate,
-// mh_t5_step, mh_t5_cross_attn_probe and mh_t5_reorder_cache.  base == NULL: sizes only (every pointer NULL).
-struct DecodeLayout {
-  DecBuffers bf;                      // the whole batch; bf.st = the first of kMaxChains states, align256(sizeof(DecState)) apart
-  int32_t* pos_off; float* proc; float* hist_scores;
-  int64_t end;                        // the batched prompt prefill's region starts here
-};
+}  // namespace
 DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
   const int64_t es = es_of(c->dtype), inner = (int64_t)c->n_heads * 64, V = c->vocab_out;
   const int64_t cache = (int64_t)c->n_dec_layers * B * inner * c->tgt_len * es;
@@ -1226,6 +735,7 @@ DecodeLayout decode_layout(const MhT5Config* c, int B, void* base) {
   ly.end = ar.off;
   return ly;
 }
+namespace {
 
 // attention kernels that project their own q (/ k / v): see decode_kernels.hpp.  d_model = 128 KC, KC in 1..8
 // (check_decode_shape).
@@ -1307,30 +817,12 @@ int launch_cross_q_d(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStr
 struct DecodeTiming { unsigned long long* buf = nullptr; int ring = 0; };
 DecodeTiming g_timing;
 
-// Everything ONE enqueue of a token step depends on: enqueue_step() reads this and option(), nothing else, and step_graph_key() makes
-// a step graph's cache key of exactly this -- a new input of the step is a new field here and so cannot be missing from the key.  Made by
-// step_call_init() (zero bytes, padding included), then assigned field by field.  Every pointer is at the chain's first row.
-struct StepCall {
-  const MhT5Config* c; const MhT5Weights* w;
-  const void* cross_kv;                  // kvB rows per (layer, k | v) slab: B/2 under CFG (a pair shares its encoder output, row b
-  int Bc, Bfull, kvB;                    // reads K/V row b % kvB); Bc = rows of this chain, Bfull = of the whole batch
-  const uint8_t* prompt_mask; int P;
-  DecBuffers bf;
-  SampleP smp;                           // (all zero without the sampler)
-  const void* kv8; const float* kv8_scales;   // the e4m3 copy of cross_kv and its scales (mh_t5_quantize_cross_kv), or NULL
-  int with_sampler;                      // 0: the step ends with the logits (mh_t5_step: the host selects)
-  int kv_group;                          // > 1: rows are (chunk, beam) pairs and row b reads cross K/V row b / kv_group
-  int has_rows; RowSetP rows;            // has_rows: the sampler reads its settings per returned row (mh_t5_generate_rows)
-  unsigned long long* timing_buf; int timing_ring;   // the timing hook as it stood when the call was built
-  const uint8_t* origin;                 // beam search by index (mh_t5_step_indexed): uint8 [Bfull][tgt_len], else NULL
-  int32_t* slot_pos; const int32_t* slot_plen;   // in-flight decode (mh_t5_slots_*): the positions and prompt lengths of all Bfull slots
-                                                 // (global row index; the SLOT kernels), else NULL.  Needs has_rows.
-};
-static_assert(std::is_trivially_copyable<StepCall>::value, "StepCall is keyed by its bytes");
+}  // namespace
 void step_call_init(StepCall* k, const MhT5Config* c, const MhT5Weights* w) {
   memset(k, 0, sizeof(*k));
   k->c = c; k->w = w; k->timing_buf = g_timing.buf; k->timing_ring = g_timing.ring;
 }
+namespace {
 
 // The operands of a layer's GEMVs, each described ONCE: the three launches behind the cross-attention and the fused tail (TailP) read
 // the same.  resid_gemv: h += A W^T (+ bias), A [Bc, K]: the output projection of either attention (o_gemv), the FFN's wo / fc2 (ffn_out)
@@ -1471,236 +963,34 @@ __global__ __launch_bounds__(256) void step_embed_kernel(const int32_t* ids, con
   const float* pe = dec_pos ? dec_pos + (long)(pos - s_off > 0 ? pos - s_off : 0) * d : nullptr;
   for (int i = threadIdx.x; i < d; i += 256) h[(long)b * d + i] = Elem<T>::to_f32(e[i]) + (pe ? pe[i] : 0.f);
 }
-// cache rows [l][b][h][0 .. n_pos) <- [l][src[b]][h][..]: gather into `tmp`, then copy back (in place would read rows that
-// were already overwritten); one workgroup per (k|v, layer, row, head)
-template <typename T>
-__global__ __launch_bounds__(256) void cache_gather_kernel(const T* kc, const T* vc, T* tmp, const int32_t* src, int B, int H, int tgt,
-                                                          int n_pos, long layer_stride) {
-  const int h = blockIdx.x % H, b = (blockIdx.x / H) % B, l = (blockIdx.x / H / B) % (int)gridDim.y, kv = blockIdx.z;
-  const T* from = (kv ? vc : kc) + (long)blockIdx.y * layer_stride + ((long)src[b] * H + h) * tgt * 64;
-  T* to = tmp + ((((long)kv * gridDim.y + blockIdx.y) * B + b) * H + h) * (long)n_pos * 64;
-  (void)l;
-  const uint4* f4 = reinterpret_cast<const uint4*>(from);
-  uint4* t4 = reinterpret_cast<uint4*>(to);
-  const int n16 = n_pos * 64 * (int)sizeof(T) / 16;
-  for (int i = threadIdx.x; i < n16; i += 256) t4[i] = f4[i];
-}
-template <typename T>
-__global__ __launch_bounds__(256) void cache_scatter_kernel(T* kc, T* vc, const T* tmp, int B, int H, int tgt, int n_pos, long layer_stride) {
-  const int h = blockIdx.x % H, b = (blockIdx.x / H) % B, kv = blockIdx.z;
-  T* to = (kv ? vc : kc) + (long)blockIdx.y * layer_stride + ((long)b * H + h) * tgt * 64;
-  const T* from = tmp + ((((long)kv * gridDim.y + blockIdx.y) * B + b) * H + h) * (long)n_pos * 64;
-  const uint4* f4 = reinterpret_cast<const uint4*>(from);
-  uint4* t4 = reinterpret_cast<uint4*>(to);
-  const int n16 = n_pos * 64 * (int)sizeof(T) / 16;
-  for (int i = threadIdx.x; i < n16; i += 256) t4[i] = f4[i];
-}
-
-// rows r = b*np + i  <-  dec_embed[prompt[b][i]]   (fp32 residual stream of the prompt prefill)
-template <typename T>
-__global__ __launch_bounds__(256) void prefill_embed_kernel(const int32_t* __restrict__ prompt, int P, int np,
-                                                           const T* __restrict__ emb, int d, float* __restrict__ h,
-                                                           const float* __restrict__ dec_pos, const uint8_t* __restrict__ pos_mask) {
-  // dec_pos (arch 2): + decoder.embed_positions[position of column i]; pos_mask != NULL (dec_pos_from_mask): minus the row's masked columns
-  const int r = blockIdx.x, b = r / np, i = r - b * np;
-  __shared__ int s_off;
-  if (threadIdx.x == 0) {
-    int off = 0;
-    if (dec_pos && pos_mask)
-      for (int k = 0; k < P; ++k) off += pos_mask[(long)b * P + k] == 0;
-    s_off = off;
-  }
-  __syncthreads();
-  const T* e = emb + (long)prompt[(long)b * P + i] * d;
-  const float* pe = dec_pos ? dec_pos + (long)(i - s_off > 0 ? i - s_off : 0) * d : nullptr;
-  for (int k = threadIdx.x; k < d; k += 256) h[(long)r * d + k] = Elem<T>::to_f32(e[k]) + (pe ? pe[k] : 0.f);
-}
-
-struct PrefillBuf {
-  float* h; void* n; void* q; void* attn; void* ff; void* vt; void* cross_vt;
-  int np_pad, Lpad;
-};
-
-int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64_t size, PrefillBuf* out) {
-  Arena ar(base, size);
-  const int64_t es = es_of(c->dtype), rows = (int64_t)B * np_max, inner = c->n_heads * 64;
-  PrefillBuf t;
-  t.np_pad = round_up(np_max, 64);
-  t.Lpad = round_up(c->src_len, 64);
-  t.h = (float*)ar.take(rows * c->d_model * 4);
-  t.n = ar.take(rows * c->d_model * es);
-  t.q = ar.take(rows * inner * es);
-  t.attn = ar.take(rows * inner * es);
-  t.ff = ar.take(rows * c->d_ff * es);
-  t.vt = ar.take((int64_t)B * inner * t.np_pad * es);
-  t.cross_vt = ar.take((int64_t)c->n_dec_layers * B * inner * t.Lpad * es);
-  if (out) *out = t;
-  return ar.off;
-}
-
-// Batched prompt prefill: positions 0 .. P-2 of every row go through the decoder stack at once (MFMA GEMMs +
-// flash attention), filling the self-attention K/V caches exactly as P-1 single-token steps would
-// (HF prefill: SURVEY.md appendix A.1).  Position P-1 is left to the per-token loop, which also produces the
-// first sampled token.  Left-pad keys are masked, left-pad query rows produce unused garbage, as in HF.
-int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kvB, const int32_t* prompt,
-                   const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s,
-                   int cache_rows = 0) {
-  // P = row stride of `prompt` / `prompt_mask`, np <= P = positions that go through the stack
-  // cache_rows: rows of the caches self_k / self_v point into (their layer stride); 0 = B.  More than B (mh_t5_step_prefill): the
-  // B prompts fill cache rows 0 .. B-1 of every layer
-  if (cache_rows <= 0) cache_rows = B;
-  const int rows = B * np;
-  const int d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff, L = c->src_len, tgt = c->tgt_len;
-  const int es = es_of(c->dtype);
-  const int np_pad = round_up(np, 64);
-  // arch 1 (VarWhisperDecoderLayer, modeling_varwhisper.py:633-741) through the same batched form: biased projections,
-  // rotate-half RoPE on q and on the cached keys, scores / 8 without a relative bias, fc1 -> gelu(erf) -> fc2.  A local
-  // (windowed) layer takes its own rotary table and the causal attention gets the band |k - q| <= local_window on top -- the
-  // keys the token-by-token step attends (decode_kernels.hpp `window`).
-  // arch 2 (HF WhisperDecoderLayer): the same with affine LayerNorms, absolute positions added to the embedding, no rotation
-  const bool wh = c->arch >= 1, hf = c->arch == 2;
-  if (wh && !hf) MH_REQUIRE(w->dec_rope != nullptr, "prefill: the Whisper family needs its rotary table");
-  MH_TRY(check_arch2_weights(c, w, "prefill"));
-  const float* dpos = hf ? w->dec_pos : nullptr;
-  const uint8_t* pmask = (hf && c->dec_pos_from_mask) ? prompt_mask : nullptr;
-  MH_TRY(dispatch_dtype(c->dtype, [&](auto t) {
-    hipLaunchKernelGGL(prefill_embed_kernel<decltype(t)>, dim3(rows), dim3(256), 0, s, prompt, P, np, (const decltype(t)*)w->dec_embed, d, pb.h, dpos, pmask);
-    return check_launch("prefill_embed_kernel");
-  }));
-  if (hipMemsetAsync(pb.vt, 0, (size_t)B * inner * np_pad * es, s) != hipSuccess) return check_launch("memset prefill vt");
-  if (hipMemsetAsync(pb.cross_vt, 0, (size_t)c->n_dec_layers * kvB * inner * pb.Lpad * es, s) != hipSuccess)
-    return check_launch("memset cross vt");
-  const long kv_layer = (long)kvB * H * L * 64;   // elements per (layer, k|v) slab of cross_kv (kvB = B/2 under CFG)
-  for (int l = 0; l < c->n_dec_layers; ++l)
-    MH_TRY(transpose_v((const char*)cross_kv + (long)(l * 2 + 1) * kv_layer * es, (long)H * L * 64, (long)L * 64, L,
-                       (char*)pb.cross_vt + (long)l * kvB * inner * pb.Lpad * es, pb.Lpad, kvB, H, c->dtype, s));
-  MhGemm g;
-  for (int l = 0; l < c->n_dec_layers; ++l) {
-    char* kc = (char*)self_k + (long)l * cache_rows * H * tgt * 64 * es;
-    char* vc = (char*)self_v + (long)l * cache_rows * H * tgt * 64 * es;
-    // self attention over the prompt
-    MH_TRY(pre_norm(c, pb.h, w->dec_ln1[l], w->dec_ln1_b[l], pb.n, rows, c->dtype, s));
-    g = MhGemm{};
-    g.A = pb.n; g.lda = d; g.W = w->dec_qkv[l]; g.ldw = d; g.C = pb.q; g.ldc = inner; g.M = rows; g.N = 3 * inner; g.K = d;
-    g.dtype = c->dtype; g.epilogue = MH_EPI_QKV_CACHE; g.n_split = inner; g.C2 = kc; g.C3 = vc; g.C4 = pb.vt; g.kv_B = B;
-    g.kv_H = H; g.kv_L = np; g.kv_Lpad = np_pad; g.cache_len = tgt;
-    if (wh) g.bias = w->dec_qkv_b[l];
-    MH_TRY(gemm(g, s));
-    const bool local = is_local_layer(c, l);
-    if (wh && !hf) {   // rotate-half RoPE on q (all prompt positions) and on the keys just cached; position = column of the padded prompt
-      const long wq = (long)rows * H * 4, wk = (long)B * H * np * 4;
-      const float* rope = (local && w->dec_rope_local) ? w->dec_rope_local : w->dec_rope;
-      MH_TRY(dispatch_dtype(c->dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL(mh::rope_qk_kernel<T>, dim3((unsigned)((wq + 255) / 256)), dim3(256), 0, s, (T*)pb.q, inner, (long)rows, np, H, rope);
-        hipLaunchKernelGGL(mh::rope_cache_kernel<T>, dim3((unsigned)((wk + 255) / 256)), dim3(256), 0, s, (T*)kc, (long)B * H, tgt, np, rope);
-        return check_launch("rope (prefill)");
-      }));
-    }
-    AttnArgs a{};
-    a.q = pb.q; a.q_rs = (long)inner * es; a.q_bs = (long)np * inner * es;
-    a.k = kc; a.k_rs = 64L * es; a.k_hs = (long)tgt * 64 * es; a.k_bs = (long)H * tgt * 64 * es;
-    a.vt = pb.vt; a.Lkpad = np_pad; a.vt_hs = 64L * np_pad * es; a.vt_bs = (long)H * 64 * np_pad * es;
-    if (!wh) { a.bias = w->dec_rel_bias; a.bias_hs = tgt; a.bias_center = 0; a.bias_sign = -1; a.bias_min = 0; a.bias_max = tgt - 1; }
-    a.key_mask = prompt_mask; a.mask_ld = P; a.mask_len = np;
-    a.out = pb.attn; a.out_rs = (long)inner * es; a.out_bs = (long)np * inner * es;
-    a.Lq = np; a.Lk = np; a.scale = wh ? c->attn_scale : 1.0f; a.band = local ? -c->local_window : 0; a.causal = 1; a.q_pos0 = 0;
-    MH_TRY(attention_general(a, B, H, c->dtype, s));
-    g = MhGemm{};
-    g.A = pb.attn; g.lda = inner; g.W = w->dec_o[l]; g.ldw = inner; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = inner;
-    g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
-    if (wh) g.bias = w->dec_o_b[l];
-    MH_TRY(gemm(g, s));
-    // cross attention of every prompt position over the encoder keys
-    MH_TRY(pre_norm(c, pb.h, w->dec_ln2[l], w->dec_ln2_b[l], pb.n, rows, c->dtype, s));
-    g = MhGemm{};
-    g.A = pb.n; g.lda = d; g.W = w->dec_cq[l]; g.ldw = d; g.C = pb.q; g.ldc = inner; g.M = rows; g.N = inner; g.K = d;
-    g.dtype = c->dtype; g.epilogue = MH_EPI_STORE;
-    if (wh) g.bias = w->dec_cq_b[l];
-    MH_TRY(gemm(g, s));
-    for (int b0 = 0; b0 < B; b0 += kvB) {   // under CFG both halves of the batch attend to the same kvB encoder rows
-      a = AttnArgs{};
-      a.q = (char*)pb.q + (long)b0 * np * inner * es; a.q_rs = (long)inner * es; a.q_bs = (long)np * inner * es;
-      a.k = (const char*)cross_kv + (long)(l * 2 + 0) * kv_layer * es; a.k_rs = 64L * es; a.k_hs = (long)L * 64 * es;
-      a.k_bs = (long)H * L * 64 * es;
-      a.vt = (char*)pb.cross_vt + (long)l * kvB * inner * pb.Lpad * es; a.Lkpad = pb.Lpad; a.vt_hs = 64L * pb.Lpad * es;
-      a.vt_bs = (long)H * 64 * pb.Lpad * es;
-      a.out = (char*)pb.attn + (long)b0 * np * inner * es; a.out_rs = (long)inner * es; a.out_bs = (long)np * inner * es;
-      a.Lq = np; a.Lk = L; a.scale = wh ? c->attn_scale : 1.0f;
-      MH_TRY(attention_general(a, kvB, H, c->dtype, s));
-    }
-    g = MhGemm{};
-    g.A = pb.attn; g.lda = inner; g.W = w->dec_co[l]; g.ldw = inner; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = inner;
-    g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
-    if (wh) g.bias = w->dec_co_b[l];
-    MH_TRY(gemm(g, s));
-    // feed forward
-    MH_TRY(pre_norm(c, pb.h, w->dec_ln3[l], w->dec_ln3_b[l], pb.n, rows, c->dtype, s));
-    g = MhGemm{};
-    g.A = pb.n; g.lda = d; g.W = w->dec_wi[l]; g.ldw = d; g.C = pb.ff; g.ldc = dff; g.M = rows; g.K = d;
-    g.dtype = c->dtype;
-    if (wh) { g.N = dff; g.epilogue = MH_EPI_BIAS_GELU_ERF; g.bias = w->dec_fc1_b[l]; }     // fc1 -> gelu(erf) (modeling_varwhisper.py:633-741)
-    else { g.N = 2 * dff; g.epilogue = MH_EPI_GEGLU; }
-    MH_TRY(gemm(g, s));
-    g = MhGemm{};
-    g.A = pb.ff; g.lda = dff; g.W = w->dec_wo[l]; g.ldw = dff; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = dff;
-    g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
-    if (wh) g.bias = w->dec_fc2_b[l];
-    MH_TRY(gemm(g, s));
-  }
-  return MH_OK;
-}
-
-// Independent rows => independent "chains": the batch is cut into contiguous blocks of rows and every
-// block runs its own captured decode step on its own stream.  A decode step is ~110 dependent, mostly
-// tiny kernels (each costs a few microseconds of dispatch + drain whatever its size), so one chain leaves
-// the GPU idle most of the time; several chains overlap one another's dispatch gaps and let the
-// HBM-bound cross-attention of one chain run under the latency-bound GEMVs of the others.  Results do not
-// depend on the chain count (every kernel is batch-invariant by construction).
-int pick_chains(int B) {
-  int n = B >= 16 ? 2 : 1;   // measured on MI355X (B=32, base): 1 -> 26.7k, 2 -> 28.0k, 4 -> 17.6k tok/s (host graph-launch bound)
-  if (option(OPT_DECODE_CHAINS) >= 1) n = (int)option(OPT_DECODE_CHAINS);
-  if (n > kMaxChains) n = kMaxChains;
-  if (n > B) n = B;
-  return n;
-}
-
-struct ChainPool {   // extra streams + fork/join events of ONE device, created on first use under that device
-  hipStream_t streams[kMaxChains] = {};
-  hipEvent_t fork = nullptr, join[kMaxChains] = {};
-  bool ready = false;
-  int init() {
-    if (ready) return MH_OK;
-    if (hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) return check_launch("event create");
-    for (int i = 0; i < kMaxChains; ++i) {
-      if (hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&join[i], hipEventDisableTiming) != hipSuccess)
-        return check_launch("chain stream create");
-    }
-    ready = true;
-    return MH_OK;
-  }
-};
-// one pool per device; mh_t5_generate holds the pool's mutex for the whole call, so two engines (or two host
-// threads) decoding on the same GPU take turns instead of sharing fork / join events
-struct DevicePool { ChainPool pool; std::mutex mu; };
-DevicePool* device_pool(int dev) {
-  static std::mutex table_mu;
-  static std::map<int, DevicePool*> table;
-  std::lock_guard<std::mutex> g(table_mu);
-  auto it = table.find(dev);
-  if (it == table.end()) it = table.emplace(dev, new DevicePool()).first;
-  return it->second;
-}
-
 }  // namespace
-}  // namespace mh
-
-extern "C" int64_t mh_t5_decode_workspace_bytes(const MhT5Config* c, int B) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0) return -1;
-  return decode_layout(c, B, nullptr).end + prefill_layout(c, B, c->tgt_len - 1, nullptr, 0, nullptr);   // + batched prompt prefill
+// ---- the token step's launches for the host units (contracts in decode_step.hpp) -----------------------------------------
+int enqueue_step(const StepCall& k, hipStream_t s) {
+  return dispatch_dtype(k.c->dtype, [&](auto t) { return enqueue_step<decltype(t)>(k, s); });
 }
+int launch_dec_init(int dtype, const SampleP& smp, int chain_rows, int start_pos, hipStream_t s) {
+  if (dtype == MH_BF16) hipLaunchKernelGGL(dec_init_kernel<bf16_t>, dim3(chain_rows), dim3(256), 0, s, smp, chain_rows, start_pos);
+  else hipLaunchKernelGGL(dec_init_kernel<float>, dim3(chain_rows), dim3(256), 0, s, smp, chain_rows, start_pos);
+  return check_launch("dec_init_kernel");
+}
+int launch_dec_slot_init(int dtype, const SampleP& smp, int slot, int P, int start_pos, int32_t* slot_pos, int32_t* slot_plen, hipStream_t s) {
+  if (dtype == MH_BF16) hipLaunchKernelGGL(dec_slot_init_kernel<bf16_t>, dim3(1), dim3(256), 0, s, smp, slot, P, start_pos, slot_pos, slot_plen);
+  else hipLaunchKernelGGL(dec_slot_init_kernel<float>, dim3(1), dim3(256), 0, s, smp, slot, P, start_pos, slot_pos, slot_plen);
+  return check_launch("dec_slot_init_kernel");
+}
+int launch_dec_finalize(const int32_t* finish_col, int B, int32_t* n_steps_out, hipStream_t s) {
+  hipLaunchKernelGGL(dec_finalize_kernel, dim3(1), dim3(64), 0, s, finish_col, B, n_steps_out);
+  return check_launch("dec_finalize_kernel");
+}
+int launch_step_embed(int dtype, const int32_t* ids, const void* dec_embed, int d, float* h, DecState* st, int pos, const float* dec_pos,
+                      const uint8_t* prompt_mask, int P, int B, hipStream_t s) {
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(step_embed_kernel<T>, dim3(B), dim3(256), 0, s, ids, (const T*)dec_embed, d, h, st, pos, dec_pos, prompt_mask, P);
+    return check_launch("step_embed_kernel");
+  });
+}
+}  // namespace mh
 
 // ---- e4m3 copy of the cross-attention K / V -------------------------------------------------------------------------
 // one workgroup per (layer, k|v, row, head) slab of L x 64 bf16: absolute maximum, then x / scale -> OCP e4m3
@@ -1818,15 +1108,30 @@ __global__ __launch_bounds__(256) void self_kv_quant_rows_kernel(const bf16_t* s
   mh::dec::quant_row64(x, q + (y * plane_rows + row) * 64, scales + y * plane_rows + row);
 }
 
-// positions 0 .. n_pos-1 of cache rows 0 .. n_rows-1 of a B-row batch's bf16 self-attention caches -> the B-row shadow self8, every
-// layer, k and v
-static int launch_self_kv_quant_rows(const MhT5Config* c, int B, const DecBuffers& bf, uint8_t* self8, int n_rows, int n_pos, hipStream_t s) {
+namespace mh {
+int launch_self_kv_quant_rows(const MhT5Config* c, int B, const DecBuffers& bf, uint8_t* self8, int n_rows, int n_pos, hipStream_t s) {
   const long n_slabs = (long)n_rows * c->n_heads, plane_rows = (long)B * c->n_heads * c->tgt_len;
   hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)((n_slabs * n_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
                      (const bf16_t*)bf.self_k, (const bf16_t*)bf.self_v, self8,
                      reinterpret_cast<float*>(self8 + self_kv8_layout(c, B).scales_offset), n_slabs, (long)n_pos, (long)c->tgt_len, plane_rows);
   return check_launch("self_kv_quant_rows_kernel");
 }
+int launch_self_kv_quant_slot(const MhT5Config* c, int S, const DecBuffers& bf, uint8_t* self8, int slot, int n_pos, hipStream_t s) {
+  const int H = c->n_heads;
+  const long row0 = (long)slot * H * c->tgt_len, plane_rows = (long)S * H * c->tgt_len;
+  hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)(((long)H * n_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, s,
+                     (const bf16_t*)bf.self_k + row0 * 64, (const bf16_t*)bf.self_v + row0 * 64, self8 + row0 * 64,
+                     reinterpret_cast<float*>(self8 + self_kv8_layout(c, S).scales_offset) + row0, (long)H, (long)n_pos,
+                     (long)c->tgt_len, plane_rows);
+  return check_launch("self_kv_quant_rows_kernel");
+}
+int launch_cross_kv_quant_row(const MhT5Config* c, int S, const void* cross_kv_row, uint8_t* cross8, int slot, hipStream_t s) {
+  const int H = c->n_heads;
+  hipLaunchKernelGGL(kv_quant_fp8_row_kernel, dim3(c->n_dec_layers * 2 * H), dim3(256), 0, s, (const bf16_t*)cross_kv_row, cross8,
+                     reinterpret_cast<float*>(cross8 + cross_kv8_layout(c, S).scales_offset), c->src_len, H, S, slot);
+  return check_launch("kv_quant_fp8_row_kernel");
+}
+}  // namespace mh
 
 extern "C" int mh_quantize_kv_rows(const void* x_bf16, int64_t n_rows, void* q, float* scales, void* stream) {
   MH_REQUIRE(x_bf16 && q && scales, "mh_quantize_kv_rows: null argument");
@@ -1848,869 +1153,6 @@ extern "C" int64_t mh_t5_self_kv_fp8_bytes(const MhT5Config* c, int B) {
   if (!c || B <= 0) return -1;
   if (c->dtype != MH_BF16) { mh::set_error("mh_t5_self_kv_fp8_bytes: the e4m3 self-attention cache needs bf16 storage"); return -1; }
   return self_kv8_layout(c, B).total;
-}
-
-extern "C" int mh_t5_decode_self_cache(const MhT5Config* c, int B, void* workspace, void** k, void** v) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_decode_self_cache"));
-  MH_REQUIRE(workspace && k && v && B > 0, "mh_t5_decode_self_cache: null argument");
-  const mh::DecodeLayout ly = mh::decode_layout(c, B, workspace);
-  *k = ly.bf.self_k;
-  *v = ly.bf.self_v;
-  return MH_OK;
-}
-
-namespace mh {
-// ------------------------------------------------------------------------------------------------
-// Instantiated step graphs kept ACROSS mh_t5_generate calls.  A chain's step graph bakes in nothing but addresses, sizes, the
-// sampling struct and the kernel choice (the position and every per-call state live in device memory), so a later call
-// whose inputs are byte-for-byte the same description -- the normal case of an engine that decodes window after window out
-// of the same workspace with the same prompt length -- replays the graph of the earlier one instead of capturing and
-// instantiating ~75 nodes again.  The key comes from ONE place: step_graph_key() over the StepCall that enqueue_step() is given,
-// the only thing it reads besides the options -- so whatever a step depends on is in its key (exact compare: a spurious
-// difference costs a capture, never a wrong graph).  Small LRU; an entry in use by a concurrent call is never shared
-// (hipGraphExec objects are single-flight) nor evicted.  Option decode_graph_cache = 0 switches it off.
-struct StepGraphEntry {
-  std::vector<unsigned char> key;      // step_graph_key(StepCall)
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  uint64_t stamp = 0;
-  bool in_use = false;
-};
-constexpr size_t kStepGraphCacheMax = 16;
-static std::mutex g_step_graph_mu;
-static std::vector<StepGraphEntry*> g_step_graphs;
-static uint64_t g_step_graph_clock = 0;
-static std::atomic<long> g_step_graph_hits{0}, g_step_graph_misses{0};
-
-// The bytes of the StepCall, then what it depends on beyond them: *c without the address of its option set, *w, every option value,
-// the device, the storage type.  Scrubbed, here and nowhere else: the addresses of c and w (their contents follow); seed and rng_row0
-// (they reach the sampler through DecState, not through the graph); under the row form what that sampler reads per row instead.
-static std::vector<unsigned char> step_graph_key(const StepCall& call) {
-  std::vector<unsigned char> key;
-  auto put = [&key](const void* p, size_t n) { key.insert(key.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
-  StepCall k;
-  memcpy(&k, &call, sizeof(k));
-  k.c = nullptr; k.w = nullptr;
-  MhSampling& sp = k.smp.sp;
-  sp.seed = 0; sp.rng_row0 = 0;
-  if (k.has_rows) {
-    k.smp.eos_table = nullptr;
-    sp.cfg_scale = sp.cfg_scale > 1.0f ? 2.f : 1.f;   // (guidance on / off is the call's, the scale each pair's own)
-    sp.temperature = sp.top_p = sp.timeshift_bias = 0.f;
-    sp.top_k = sp.lookback_mask_end = 0;
-    for (int j = 0; j < 3; ++j) sp.cond_temp[j] = 0.f;
-  }
-  MhT5Config cc = *call.c;
-  cc.options = nullptr;
-  long opts[OPT_COUNT];
-  for (int o = 0; o < OPT_COUNT; ++o) opts[o] = option(o);
-  int dev_id = 0;
-  (void)hipGetDevice(&dev_id);
-  const int ids[2] = {dev_id, call.c->dtype == MH_BF16 ? 1 : 0};
-  put(&k, sizeof(k)); put(&cc, sizeof(cc)); put(call.w, sizeof(*call.w)); put(opts, sizeof(opts)); put(ids, sizeof(ids));
-  return key;
-}
-
-static StepGraphEntry* step_graph_acquire(const std::vector<unsigned char>& key) {
-  std::lock_guard<std::mutex> lk(g_step_graph_mu);
-  for (StepGraphEntry* e : g_step_graphs)
-    if (!e->in_use && e->key == key) {
-      e->in_use = true;
-      e->stamp = ++g_step_graph_clock;
-      return e;
-    }
-  return nullptr;
-}
-
-// takes ownership of graph / exec; returns the entry (in use) -- or nullptr when the cache is full of entries in use
-static StepGraphEntry* step_graph_insert(std::vector<unsigned char>&& key, hipGraph_t graph, hipGraphExec_t exec) {
-  std::lock_guard<std::mutex> lk(g_step_graph_mu);
-  while (g_step_graphs.size() >= kStepGraphCacheMax) {
-    int victim = -1;
-    for (size_t i = 0; i < g_step_graphs.size(); ++i)
-      if (!g_step_graphs[i]->in_use && (victim < 0 || g_step_graphs[i]->stamp < g_step_graphs[victim]->stamp)) victim = (int)i;
-    if (victim < 0) return nullptr;
-    StepGraphEntry* v = g_step_graphs[victim];
-    (void)hipGraphExecDestroy(v->exec);
-    (void)hipGraphDestroy(v->graph);
-    delete v;
-    g_step_graphs.erase(g_step_graphs.begin() + victim);
-  }
-  StepGraphEntry* e = new StepGraphEntry();
-  e->key = std::move(key);
-  e->graph = graph;
-  e->exec = exec;
-  e->in_use = true;
-  e->stamp = ++g_step_graph_clock;
-  g_step_graphs.push_back(e);
-  return e;
-}
-
-static void step_graph_release(StepGraphEntry* e) {
-  std::lock_guard<std::mutex> lk(g_step_graph_mu);
-  e->in_use = false;
-}
-
-// The device that owns the caller's stream (not whatever happens to be current)
-static int stream_device(hipStream_t s, int* dev) {
-  if (hipStreamGetDevice(s, dev) != hipSuccess) { (void)hipGetLastError(); if (hipGetDevice(dev) != hipSuccess) return check_launch("hipGetDevice"); }
-  return MH_OK;
-}
-// Streams, events and graphs of a call or a session are created under that device; the current one is restored on every return path
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int want) { if (hipGetDevice(&prev) == hipSuccess && prev != want) (void)hipSetDevice(want); else prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// A chain of the running call and the owner of its step graph: the cross-call cache (`cached`: handed back when the call ends) or the
-// call itself (destroyed with it, after the call's last synchronise)
-struct Chain {
-  hipStream_t stream = nullptr; DecState* st = nullptr;
-  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; StepGraphEntry* cached = nullptr;
-  Chain() = default;
-  Chain(const Chain&) = delete;
-  Chain& operator=(const Chain&) = delete;
-  ~Chain() {
-    if (cached) { step_graph_release(cached); return; }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-  }
-};
-
-// A chain enters the call on its own stream, behind the caller's work so far (`fork`): dec_init_kernel, then one step of the chain (every
-// kernel reads the position from device memory) as a graph for replay: an earlier call's, if its key is this one's, else captured now
-static int chain_step_graph(const StepCall& call, const char* who, Chain* ch);
-static int start_chain(const StepCall& call, int start_pos, hipEvent_t fork, const char* who, Chain* ch) {
-  hipStream_t cs = ch->stream;
-  ch->st = call.bf.st;
-  if (hipStreamWaitEvent(cs, fork, 0) != hipSuccess) return check_launch("fork wait");
-  if (call.c->dtype == MH_BF16) hipLaunchKernelGGL(dec_init_kernel<bf16_t>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
-  else hipLaunchKernelGGL(dec_init_kernel<float>, dim3(call.Bc), dim3(256), 0, cs, call.smp, call.Bc, start_pos);
-  MH_TRY(check_launch("dec_init_kernel"));
-  return chain_step_graph(call, who, ch);
-}
-// One step of the chain as a graph for replay on ch->stream: an earlier call's, if its key is this one's, else captured now
-static int chain_step_graph(const StepCall& call, const char* who, Chain* ch) {
-  hipStream_t cs = ch->stream;
-  std::vector<unsigned char> key;
-  if (option(OPT_DECODE_GRAPH_CACHE) != 0) {
-    key = step_graph_key(call);
-    if ((ch->cached = step_graph_acquire(key))) { ch->exec = ch->cached->exec; g_step_graph_hits.fetch_add(1); return MH_OK; }
-    g_step_graph_misses.fetch_add(1);
-  }
-  if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) return check_launch("begin capture");
-  const int rce = dispatch_dtype(call.c->dtype, [&](auto t) { return enqueue_step<decltype(t)>(call, cs); });
-  const hipError_t ce = hipStreamEndCapture(cs, &ch->graph);
-  if (rce != MH_OK) return rce;
-  if (ce != hipSuccess || !ch->graph) { set_error("%s: stream capture failed: %s", who, hipGetErrorString(ce)); return MH_ERR_LAUNCH; }
-  if (hipGraphInstantiate(&ch->exec, ch->graph, nullptr, nullptr, 0) != hipSuccess) return check_launch("graph instantiate");
-  if (!key.empty() && (ch->cached = step_graph_insert(std::move(key), ch->graph, ch->exec))) ch->graph = nullptr;   // the cache owns both now
-  return MH_OK;
-}
-
-// The host's look at a chain between two bursts of replays: DecState::n_running and ::tail_err in one 8-byte read
-static int poll_chain(const Chain& ch, bool* running) {
-  int word[2] = {1, 0};
-  if (hipMemcpyAsync(word, &ch.st->n_running, 8, hipMemcpyDeviceToHost, ch.stream) != hipSuccess ||
-      hipStreamSynchronize(ch.stream) != hipSuccess)
-    return MH_ERR_LAUNCH;
-  *running = word[0] != 0;
-  return word[1] != 0 ? MH_ERR_DECODE_TAIL_TIMEOUT : MH_OK;
-}
-
-// The one burst-and-poll loop, of a uniform call and of a slot session alike.  The launcher of chains which[0 .. n) from the calling
-// thread: bursts of poll_every replays each, interleaved, then a poll of each (none behind the last burst, none under teacher forcing:
-// poll = false).  A chain is left out once its rows are done or it failed (rcs[chain]); replays[chain], if given, counts its
-// hipGraphLaunch calls that succeeded.
-static void run_chains(const Chain* chains, const int* which, int n, int n_steps, int poll_every, bool poll, int* rcs, int* replays) {
-  bool alive[kMaxChains];
-  for (int i = 0; i < n; ++i) alive[i] = true;
-  for (int step = 0; step < n_steps;) {
-    const int burst = n_steps - step < poll_every ? n_steps - step : poll_every;
-    for (int r = 0; r < burst; ++r)
-      for (int i = 0; i < n; ++i) {
-        const int ci = which[i];
-        if (!alive[i] || rcs[ci] != MH_OK) continue;
-        if (hipGraphLaunch(chains[ci].exec, chains[ci].stream) != hipSuccess) rcs[ci] = MH_ERR_LAUNCH;
-        else if (replays) ++replays[ci];
-      }
-    step += burst;
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-      const int ci = which[i];
-      if (!alive[i] || rcs[ci] != MH_OK) continue;
-      if (step < n_steps && poll && (rcs[ci] = poll_chain(chains[ci], &alive[i])) != MH_OK) continue;
-      any = any || alive[i];
-    }
-    if (!any) break;
-  }
-}
-// Replaying a ~110-node graph costs ~0.4 ms of HOST time on ROCm 7.2, so every running chain gets a launcher thread of its own (the
-// chains are independent; the first runs on the calling thread); option decode_launch_threads = 0: one launcher for all, their bursts
-// interleaved (slower on the host side; the same kernels and arguments).  which: the chains that run -- all of a uniform call, those
-// with a live slot of a session.  -> the call's status, the failed chain named by its index
-static int launch_chains(const Chain* chains, const int* which, int n, int n_steps, int poll_every, bool poll, const char* who,
-                         int* replays = nullptr) {
-  int rcs[kMaxChains] = {};
-  if (n <= 1 || option(OPT_DECODE_LAUNCH_THREADS) == 0) {
-    run_chains(chains, which, n, n_steps, poll_every, poll, rcs, replays);
-  } else {
-    std::vector<std::thread> th;
-    const MhOptionSet* set = current_option_set();   // thread-local in the caller: re-installed in every launcher
-    for (int i = 1; i < n; ++i)
-      th.emplace_back([&, i, set] { OptionScope sc(set); run_chains(chains, which + i, 1, n_steps, poll_every, poll, rcs, replays); });
-    run_chains(chains, which, 1, n_steps, poll_every, poll, rcs, replays);
-    for (auto& t : th) t.join();
-  }
-  int rc = MH_OK;
-  for (int i = 0; i < n; ++i) {
-    const int ci = which[i];
-    if (rcs[ci] == MH_ERR_DECODE_TAIL_TIMEOUT) rc = mh_t5_decode_tail_status(1);
-    else if (rcs[ci] != MH_OK) { set_error("%s: graph launch / poll failed on chain %d: %s", who, ci, hipGetErrorString(hipGetLastError())); rc = rcs[ci]; }
-  }
-  return rc;
-}
-
-// What mh_t5_generate, mh_t5_generate_skv8 (self_kv_fp8: the caller's e4m3 shadow of the self-attention cache, else NULL) and
-// mh_t5_generate_rows (rowset: the sampler's settings per returned row, else NULL) were given; who: the entry, for error messages
-struct GenerateArgs {
-  const MhT5Config* c; const MhT5Weights* w; const void* cross_kv; int B; const int32_t* prompt; const uint8_t* prompt_mask; int P;
-  const uint8_t* eos_table; const MhSampling* sp; int32_t* tokens; int32_t* n_steps_out; float* logits_dump; const int32_t* forced;
-  void* workspace; int64_t workspace_bytes; int poll_every; void* stream; void* self_kv_fp8; const RowSetP* rowset; const char* who;
-};
-
-// What every entry that runs the sampled token step checks of its configuration and settings, in this order (ptrs_ok: the entry's own
-// pointer arguments are all there; P: the call's prompt length, or NULL where every row brings its own -- mh_t5_slots_admit checks it)
-static int check_decode_call(const MhT5Config* c, const MhT5Weights* w, const MhSampling* sp, int B, bool ptrs_ok, void* stream,
-                             const int* P, bool rows, const char* who) {
-  MH_TRY(check_cfg(c, who));
-  MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && sp && ptrs_ok, "%s: null argument", who);
-  MH_REQUIRE(stream != nullptr, "%s: needs a non-default stream (hipGraph capture)", who);
-  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64] (shard larger batches on the host)", who, B);
-  MH_REQUIRE(!P || (*P >= 1 && *P < sp->max_length), "%s: prompt length %d must be in [1, max_length)", who, P ? *P : 0);
-  MH_REQUIRE(sp->max_length >= 2, "%s: max_length %d must be >= 2", who, sp->max_length);
-  MH_REQUIRE(sp->max_length <= c->tgt_len, "%s: max_length %d exceeds tgt_len %d", who, sp->max_length, c->tgt_len);
-  MH_REQUIRE(rows || sp->temperature > 0.f, "%s: temperature must be > 0", who);
-  MH_REQUIRE(sp->n_sos >= 0 && sp->n_sos <= 16, "%s: too many sos ids", who);
-  MH_REQUIRE(!(sp->cfg_scale > 1.0f) || B % 2 == 0, "%s: classifier-free guidance needs an even batch (negative rows, then prompt rows)", who);
-  MH_REQUIRE(sp->n_cond >= 0 && sp->n_cond <= 3, "%s: n_cond %d not in [0, 3]", who, sp->n_cond);
-  for (int j = 0; j < sp->n_cond; ++j)
-    MH_REQUIRE((rows || sp->cond_temp[j] > 0.f) && sp->cond_offset[j] >= 1, "%s: bad conditional temperature rule %d", who, j);
-  MH_REQUIRE(sp->tok_flags || (sp->n_cond == 0 && !sp->lookback_types_first),
-             "%s: tok_flags is required by the conditional temperature / types_first lookback processors", who);
-  MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
-  return MH_OK;
-}
-
-// The row settings of mh_t5_generate_rows (one entry per: "returned row") and of mh_t5_slots_open ("slot")
-static int check_row_set(const MhRowSampling* rows, const uint8_t* eos_tables, int n_eos_sets, const char* per, const char* who) {
-  MH_REQUIRE(rows && eos_tables, "%s: null argument (rows: one MhRowSampling per %s; eos_tables: [n_eos_sets][vocab_out])", who, per);
-  MH_REQUIRE(n_eos_sets >= 1, "%s: n_eos_sets %d must be >= 1", who, n_eos_sets);
-  return MH_OK;
-}
-
-static int check_generate_args(const GenerateArgs& a) {
-  const bool ptrs_ok = a.cross_kv && a.prompt && (a.eos_table || a.rowset) && a.tokens && a.n_steps_out && a.workspace;
-  MH_TRY(check_decode_call(a.c, a.w, a.sp, a.B, ptrs_ok, a.stream, &a.P, a.rowset != nullptr, a.who));
-  MH_REQUIRE(a.workspace_bytes >= mh_t5_decode_workspace_bytes(a.c, a.B), "%s: workspace too small", a.who);
-  return check_arch2_weights(a.c, a.w, a.who);
-}
-
-// The first row of the e4m3 shadow of the self-attention cache, and of its scales, at row b0 of a B-row batch (the b0 offsets of the
-// bf16 caches); the same over the packed e4m3 copy of the cross K/V of kvB rows
-static void self8_rows(const MhT5Config* c, int B, int b0, void* self8, DecBuffers* bf) {
-  const long row = (long)b0 * c->n_heads * c->tgt_len;
-  bf->self8 = (uint8_t*)self8 + row * 64;
-  bf->self8_scales = reinterpret_cast<float*>((uint8_t*)self8 + self_kv8_layout(c, B).scales_offset) + row;
-}
-static void cross8_rows(const MhT5Config* c, int kvB, int b0, const void* kv8, StepCall* k) {
-  k->kv8 = (const char*)kv8 + (long)b0 * c->n_heads * c->src_len * 64;
-  k->kv8_scales = reinterpret_cast<const float*>((const char*)kv8 + cross_kv8_layout(c, kvB).scales_offset) + (long)b0 * c->n_heads;
-}
-
-// Chain ci of the call as a StepCall: rows [ci rows_per, + Bc) of every buffer, of the e4m3 copies and of the sampler's view
-// (Bc <= 0: the batch has no such chain).  self8: the shadow of the whole batch, or NULL.
-static void chain_call(const GenerateArgs& a, const DecodeLayout& ly, int ci, int rows_per, uint8_t* self8, StepCall* k) {
-  const MhT5Config* c = a.c;
-  const MhSampling* sp = a.sp;
-  const DecBuffers& all = ly.bf;
-  const int B = a.B, P = a.P, es = es_of(c->dtype), H = c->n_heads, inner = H * 64, d = c->d_model, V = c->vocab_out;
-  const bool cfg = sp->cfg_scale > 1.0f;
-  const int b0 = ci * rows_per;
-  step_call_init(k, c, a.w);
-  k->Bc = (b0 + rows_per <= B) ? rows_per : B - b0;
-  k->Bfull = B; k->kvB = cfg ? B / 2 : B; k->P = P; k->with_sampler = 1;
-  k->cross_kv = a.cross_kv ? (const char*)a.cross_kv + (long)b0 * H * c->src_len * 64 * es : nullptr;   // (NULL: a kv8 slot session without one)
-  k->prompt_mask = a.prompt_mask ? a.prompt_mask + (long)b0 * P : nullptr;
-  if (a.rowset) { k->has_rows = 1; k->rows.rows = a.rowset->rows; k->rows.eos_tables = a.rowset->eos_tables; k->rows.n_eos_sets = a.rowset->n_eos_sets; }
-  DecBuffers& bf = k->bf;
-  bf.chain = ci;
-  bf.h = all.h + (long)b0 * d;
-  bf.attn = (char*)all.attn + (long)b0 * inner * es;
-  bf.ff = (char*)all.ff + (long)b0 * c->d_ff * es;
-  bf.logits = all.logits + (long)b0 * V;
-  bf.self_k = (char*)all.self_k + (long)b0 * inner * c->tgt_len * es;
-  bf.self_v = (char*)all.self_v + (long)b0 * inner * c->tgt_len * es;
-  if (self8) self8_rows(c, B, b0, self8, &bf);
-  bf.finished = all.finished + b0;
-  bf.finish_col = all.finish_col; bf.last_ts = all.last_ts;
-  bf.st = (DecState*)((char*)all.st + (long)ci * align256(sizeof(DecState)));
-  if (sp->cross_kv_fp8) cross8_rows(c, k->kvB, b0, sp->cross_kv_fp8, k);
-  SampleP& smp = k->smp;
-  smp.logits = bf.logits; smp.ldl = V; smp.V = V; smp.tokens = a.tokens; smp.max_length = sp->max_length;
-  smp.forced = a.forced; smp.eos_table = a.eos_table; smp.finished = all.finished; smp.finish_col = all.finish_col;
-  smp.last_ts_val = all.last_ts; smp.logits_dump = a.logits_dump; smp.dec_embed = a.w->dec_embed; smp.h = bf.h;
-  smp.d = d; smp.st = bf.st; smp.B = B; smp.P = P; smp.b0 = b0;
-  memcpy(&smp.sp, sp, sizeof(*sp));
-  smp.proc = ly.proc; smp.hist_scores = ly.hist_scores; smp.pair = cfg ? B / 2 : 0; smp.chain_rows = k->Bc;
-  if (c->arch == 2) {
-    smp.dec_pos = a.w->dec_pos;
-    smp.pos_off = c->dec_pos_from_mask ? ly.pos_off : nullptr;
-    smp.prompt_mask = a.prompt_mask;
-  }
-}
-// The batch cut into n_chains blocks of rows_per rows: calls[0 .. used), -> used (a late block may be empty: B = 5 over 4 chains)
-static int chain_calls(const GenerateArgs& a, const DecodeLayout& ly, int n_chains, int rows_per, uint8_t* self8, StepCall* calls) {
-  int used = 0;
-  for (; used < n_chains; ++used) {
-    chain_call(a, ly, used, rows_per, self8, &calls[used]);
-    if (calls[used].Bc <= 0) break;
-  }
-  return used;
-}
-
-static int generate_impl(const GenerateArgs& a) {
-  MH_TRY(check_generate_args(a));
-  const MhT5Config* c = a.c;
-  const MhSampling* sp = a.sp;
-  const int B = a.B, P = a.P;
-  hipStream_t s = (hipStream_t)a.stream;
-  const bool cfg = sp->cfg_scale > 1.0f;
-  const DecodeLayout ly = decode_layout(c, B, a.workspace);
-  // a CFG pair spans both halves of the batch and the (batch-wide) conditional temperature reads row 0's history: one chain
-  const int n_chains = (cfg || (sp->n_cond > 0 && !sp->cond_per_row)) ? 1 : pick_chains(B);
-  const int rows_per = ceil_div(B, n_chains);
-  int dev = 0;
-  MH_TRY(stream_device(s, &dev));
-  DeviceGuard device_guard(dev);
-  DevicePool* dp = device_pool(dev);
-  std::lock_guard<std::mutex> pool_guard(dp->mu);
-  ChainPool& g_pool = dp->pool;
-  MH_TRY(g_pool.init());
-  Chain chains[kMaxChains];   // (their graphs are released / destroyed on every return path below)
-  for (int i = 0; i < kMaxChains; ++i) chains[i].stream = g_pool.streams[i];
-
-  // tokens[:, :P] = prompt; the remainder is produced by the sampler
-  if (hipMemcpy2DAsync(a.tokens, (size_t)sp->max_length * 4, a.prompt, (size_t)P * 4, (size_t)P * 4, B,
-                       hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return check_launch("prompt copy");
-  // batched prompt prefill (positions 0..P-2); MH_DECODE_PREFILL=0 feeds the prompt token by token instead
-  int start_pos = 0;
-  if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {
-    PrefillBuf pb;
-    prefill_layout(c, B, P - 1, (char*)a.workspace + ly.end, a.workspace_bytes - ly.end, &pb);
-    MH_REQUIRE(ly.end + prefill_layout(c, B, P - 1, nullptr, 0, nullptr) <= a.workspace_bytes,
-               "%s: workspace too small for the prompt prefill", a.who);
-    MH_TRY(prefill_prompt(c, a.w, a.cross_kv, B, cfg ? B / 2 : B, a.prompt, a.prompt_mask, P, P - 1, ly.bf.self_k, ly.bf.self_v, pb, s));
-    start_pos = P - 1;
-  }
-  // the shadow: the prompt positions the batched prefill wrote (they attended each other through the bf16 cache) are quantised in
-  // one pass before the first token step; every token step appends its own row
-  uint8_t* self8 = (uint8_t*)a.self_kv_fp8;
-  if (self8 && start_pos > 0) MH_TRY(launch_self_kv_quant_rows(c, B, ly.bf, self8, B, start_pos, s));
-  if (hipEventRecord(g_pool.fork, s) != hipSuccess) return check_launch("fork record");
-
-  StepCall calls[kMaxChains];
-  const int used = chain_calls(a, ly, n_chains, rows_per, self8, calls);
-  int rc = MH_OK, which[kMaxChains];   // every chain of the call runs
-  for (int ci = 0; ci < used && rc == MH_OK; ++ci) {
-    which[ci] = ci;
-    rc = start_chain(calls[ci], start_pos, g_pool.fork, a.who, &chains[ci]);
-  }
-
-  const int total_steps = sp->max_length - 1 - start_pos;   // positions start_pos .. max_length-2 are fed
-  if (rc == MH_OK) rc = launch_chains(chains, which, used, total_steps, a.poll_every <= 0 ? 16 : a.poll_every, !a.forced, a.who);
-  // join the chains back into the caller's stream
-  for (int ci = 0; ci < used; ++ci) {
-    (void)hipEventRecord(g_pool.join[ci], chains[ci].stream);
-    (void)hipStreamWaitEvent(s, g_pool.join[ci], 0);
-  }
-  if (rc == MH_OK) {
-    hipLaunchKernelGGL(dec_finalize_kernel, dim3(1), dim3(64), 0, s, ly.bf.finish_col, B, a.n_steps_out);
-    rc = check_launch("dec_finalize_kernel");
-  }
-  (void)hipStreamSynchronize(s);   // the graph objects must outlive their launches
-  if (rc == MH_OK && option(OPT_DECODE_FUSED_TAIL) != 0) {   // the chains are idle: their last word on the bounded hand-offs
-    for (int ci = 0; ci < used && rc == MH_OK; ++ci) {
-      int err = 0;
-      if (hipMemcpy(&err, &chains[ci].st->tail_err, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = check_launch("tail status");
-      else rc = mh_t5_decode_tail_status(err);
-    }
-  }
-  return rc;
-}
-}  // namespace mh
-
-extern "C" int mh_t5_step_graph_cache_stats(long* hits, long* misses, int reset) {
-  if (hits) *hits = mh::g_step_graph_hits.load();
-  if (misses) *misses = mh::g_step_graph_misses.load();
-  if (reset) { mh::g_step_graph_hits.store(0); mh::g_step_graph_misses.store(0); }
-  return MH_OK;
-}
-
-extern "C" int mh_t5_generate(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                              const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
-                              const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
-                              const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                              void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                        workspace_bytes, poll_every, stream, nullptr, nullptr, "mh_t5_generate"});
-}
-
-extern "C" int mh_t5_generate_skv8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                                   const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
-                                   const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
-                                   const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                                   void* stream, void* self_kv_fp8) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_generate_skv8"));
-  MH_REQUIRE(self_kv_fp8, "mh_t5_generate_skv8: null argument (self_kv_fp8: mh_t5_self_kv_fp8_bytes(cfg, B) bytes owned by the caller)");
-  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_generate_skv8: the e4m3 self-attention cache needs bf16 storage");
-  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, eos_table, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                        workspace_bytes, poll_every, stream, self_kv_fp8, nullptr, "mh_t5_generate_skv8"});
-}
-
-extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                                   const int32_t* prompt, const uint8_t* prompt_mask, int P, const uint8_t* eos_table,
-                                   const MhSampling* sp, int32_t* tokens, int32_t* n_steps_out, float* logits_dump,
-                                   const int32_t* forced, void* workspace, int64_t workspace_bytes, int poll_every,
-                                   void* stream, void* self_kv_fp8, const MhRowSampling* rows, const uint8_t* eos_tables,
-                                   int n_eos_sets) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  (void)eos_table;   // ignored: every row names its set of eos_tables
-  MH_TRY(check_cfg(c, "mh_t5_generate_rows"));
-  MH_TRY(mh::check_row_set(rows, eos_tables, n_eos_sets, "returned row", "mh_t5_generate_rows"));
-  MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "mh_t5_generate_rows: the e4m3 self-attention cache needs bf16 storage");
-  const mh::RowSetP rowset{rows, eos_tables, n_eos_sets};
-  return generate_impl({c, w, cross_kv, B, prompt, prompt_mask, P, nullptr, sp, tokens, n_steps_out, logits_dump, forced, workspace,
-                        workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, "mh_t5_generate_rows"});
-}
-
-// ------------------------------------------------------------------------------------------------
-// In-flight decode (mh_t5_slots_*; contract in include/mapperhip.h): S slots, every slot a row with a window of its own that enters
-// (admit) and leaves (release) while its neighbours keep stepping.  The chains are those of mh_t5_generate_rows over S rows -- the
-// same static row blocks, one DecState and one step graph each (the SLOT kernels: the key holds StepCall::slot_pos) -- on streams
-// the session owns; admissions run on a stream of their own.
-//
-// Why no step can write a cache row, a token or a state word that an admission is filling, and no admission one that a step reads:
-//   * an idle slot's position is negative: its self-attention workgroups return before they store, its sampler workgroup only
-//     arrives; the GEMVs, the tail and the cross-attention write the slot's rows of h / attn / ff / logits, which nothing reads;
-//   * release(slot) makes the position negative ON THE CHAIN'S STREAM, behind the slot's last step, and records freed[slot] there;
-//   * admit(slot) waits for freed[slot] on the admission stream before its first write, and the slot's position -- the one word that
-//     makes it live -- is the last thing its last kernel writes; then it records admitted[chain];
-//   * run() makes the chain's stream wait for admitted[chain] before the first step enqueued after the admission.
-// Events only: nothing on the device spins or waits for another launch.
-namespace mh {
-struct SlotSession {
-  const MhT5Config* c = nullptr; const MhT5Weights* w = nullptr;
-  int S = 0, n_chains = 0, rows_per = 0, dev = 0, max_length = 0, poll_every = 16;
-  DecodeLayout ly{};
-  int32_t* pos = nullptr; int32_t* plen = nullptr; uint8_t* mask = nullptr;   // [S], [S], [S][max_length]
-  char* prefill_base = nullptr; int64_t prefill_bytes = 0;
-  char* cross_kv = nullptr; int32_t* tokens = nullptr;   // cross_kv: the bf16 / fp32 slot copy, NULL where the steps stream cross8 alone
-  uint8_t* cross8 = nullptr; uint8_t* self8 = nullptr;   // mh_t5_slots_open_kv8: the caller's S-row e4m3 copies, or NULL
-  Chain chains[kMaxChains];
-  StepCall calls[kMaxChains];
-  hipStream_t admit_stream = nullptr;
-  hipEvent_t admitted[kMaxChains] = {}, freed[64] = {}, caller_ev = nullptr;
-  bool pending[kMaxChains] = {};    // an admission into the chain since its last step was enqueued
-  bool live[64] = {};               // admitted and not released
-  int32_t host_pos[64] = {}, host_col[64] = {}; uint8_t host_fin[64] = {};
-  ~SlotSession() {
-    // joins the chains and the admissions (a graph object must outlive its launches; the Chain members release theirs after this body)
-    if (admit_stream) { (void)hipStreamSynchronize(admit_stream); (void)hipStreamDestroy(admit_stream); }
-    for (int i = 0; i < kMaxChains; ++i) {
-      if (chains[i].stream) { (void)hipStreamSynchronize(chains[i].stream); (void)hipStreamDestroy(chains[i].stream); }
-      if (admitted[i]) (void)hipEventDestroy(admitted[i]);
-    }
-    for (int i = 0; i < 64; ++i) if (freed[i]) (void)hipEventDestroy(freed[i]);
-    if (caller_ev) (void)hipEventDestroy(caller_ev);
-  }
-  int chain_of(int slot) const { return slot / rows_per; }
-};
-// the slot buffers behind the decode layout of S rows, then the prompt prefill of ONE row (an admission prefills one window)
-static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession* ss) {
-  const DecodeLayout ly = decode_layout(c, S, base);
-  Arena ar(base ? (char*)base + ly.end : nullptr, INT64_MAX);
-  int32_t* pos = (int32_t*)ar.take((int64_t)S * 4);
-  int32_t* plen = (int32_t*)ar.take((int64_t)S * 4);
-  uint8_t* mask = (uint8_t*)ar.take((int64_t)S * c->tgt_len);
-  const int64_t pre = prefill_layout(c, 1, c->tgt_len - 1, nullptr, 0, nullptr);
-  if (ss) {
-    ss->ly = ly; ss->pos = pos; ss->plen = plen; ss->mask = mask;
-    ss->prefill_base = (char*)base + ly.end + ar.off; ss->prefill_bytes = pre;
-  }
-  return ly.end + ar.off + pre;
-}
-}  // namespace mh
-
-extern "C" int64_t mh_t5_slots_workspace_bytes(const MhT5Config* c, int S) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || S < 1 || S > 64) return -1;
-  return mh::slots_layout(c, S, nullptr, nullptr);
-}
-
-namespace mh {
-// mh_t5_slots_open (kv8 = false: the e4m3 caches are refused) and mh_t5_slots_open_kv8 (kv8 = true: sp->cross_kv_fp8 / self_kv_fp8 are
-// the session's S-row copies, filled row by row by the admissions and the token steps)
-static int slots_open_impl(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
-                           const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
-                           const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
-                           void* stream, void** handle, bool kv8, const char* who) {
-  OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, who));
-  MH_REQUIRE(handle, "%s: null argument (handle)", who);
-  *handle = nullptr;
-  MH_REQUIRE(S >= 1 && S <= 64, "%s: %d slots not in [1, 64]", who, S);
-  MH_TRY(check_row_set(rows, eos_tables, n_eos_sets, "slot", who));
-  MH_REQUIRE(sp, "%s: null argument (sp)", who);
-  MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
-  MH_REQUIRE(!forced, "%s: teacher forcing (forced ids) has no slot form", who);
-  if (!kv8) {
-    MH_REQUIRE(!sp->cross_kv_fp8, "%s: the e4m3 copy of the cross K/V (cross_kv_fp8) has no slot form", who);
-    MH_REQUIRE(!self_kv_fp8, "%s: the e4m3 shadow of the self-attention cache has no slot form", who);
-  } else {
-    MH_REQUIRE(!sp->cross_kv_fp8 || c->dtype == MH_BF16, "%s: cross_kv_fp8 needs bf16 storage", who);
-    MH_REQUIRE(!self_kv_fp8 || c->dtype == MH_BF16, "%s: the e4m3 self-attention cache needs bf16 storage", who);
-    MH_REQUIRE(cross_kv_slots || sp->cross_kv_fp8,
-               "%s: null argument (cross_kv_slots may be NULL only where sp->cross_kv_fp8 is the slots' e4m3 copy)", who);
-  }
-  MH_REQUIRE(sp->n_cond == 0 || sp->cond_per_row, "%s: conditional temperature rules need cond_per_row = 1 (every slot is a window of its own)", who);
-  // whatever mh_t5_generate_rows refuses of a configuration and its settings (the prompt length is each admission's)
-  MH_TRY(check_decode_call(c, w, sp, S, (cross_kv_slots || (kv8 && sp->cross_kv_fp8)) && tokens && workspace, stream, nullptr, true, who));
-  MH_REQUIRE(workspace_bytes >= slots_layout(c, S, nullptr, nullptr), "%s: workspace too small (mh_t5_slots_workspace_bytes)", who);
-  MH_TRY(check_arch2_weights(c, w, who));
-  hipStream_t s = (hipStream_t)stream;
-  int dev = 0;
-  MH_TRY(stream_device(s, &dev));
-  DeviceGuard device_guard(dev);
-  std::unique_ptr<SlotSession> ss(new SlotSession());
-  ss->c = c; ss->w = w; ss->S = S; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
-  ss->cross_kv = (char*)cross_kv_slots; ss->tokens = tokens;
-  ss->cross8 = (uint8_t*)sp->cross_kv_fp8; ss->self8 = (uint8_t*)self_kv_fp8;   // (both NULL behind mh_t5_slots_open)
-  slots_layout(c, S, workspace, ss.get());
-  ss->n_chains = pick_chains(S);
-  ss->rows_per = ceil_div(S, ss->n_chains);
-  // every slot idle: position -1, flag set (the recount of n_running counts clear flags); the chains' control blocks zero
-  if (hipMemsetAsync(ss->pos, 0xff, (size_t)S * 4, s) != hipSuccess || hipMemsetAsync(ss->plen, 0, (size_t)S * 4, s) != hipSuccess ||
-      hipMemsetAsync(ss->ly.bf.finished, 1, (size_t)S, s) != hipSuccess ||
-      hipMemsetAsync(ss->mask, 1, (size_t)S * sp->max_length, s) != hipSuccess ||
-      hipMemsetAsync(ss->ly.bf.st, 0, (size_t)align256(sizeof(DecState)) * kMaxChains, s) != hipSuccess)
-    return check_launch("slot state memset");
-  if (hipStreamCreateWithFlags(&ss->admit_stream, hipStreamNonBlocking) != hipSuccess) return check_launch("slot stream create");
-  for (int b = 0; b < S; ++b) {
-    if (hipEventCreateWithFlags(&ss->freed[b], hipEventDisableTiming) != hipSuccess) return check_launch("slot event create");
-    if (hipEventRecord(ss->freed[b], s) != hipSuccess) return check_launch("slot event record");
-  }
-  const RowSetP rowset{rows, eos_tables, n_eos_sets};
-  GenerateArgs a{c, w, cross_kv_slots, S, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
-                 workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, who};
-  // prompt_mask: the slot mask rows, stride max_length (call.P); the chains' rows of both e4m3 copies (both pointers are in the key
-  // of the step graph: a kv8 session and a plain one never share a graph)
-  ss->n_chains = chain_calls(a, ss->ly, ss->n_chains, ss->rows_per, ss->self8, ss->calls);
-  for (int ci = 0; ci < ss->n_chains; ++ci) {
-    StepCall& call = ss->calls[ci];
-    call.slot_pos = ss->pos; call.slot_plen = ss->plen;
-    Chain& ch = ss->chains[ci];
-    if (hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ss->admitted[ci], hipEventDisableTiming) != hipSuccess)
-      return check_launch("slot stream create");
-    ch.st = call.bf.st;
-    if (hipStreamWaitEvent(ch.stream, ss->freed[0], 0) != hipSuccess) return check_launch("slot stream wait");   // behind the memsets
-    MH_TRY(chain_step_graph(call, who, &ch));
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return check_launch("slot open");
-  *handle = ss.release();
-  return MH_OK;
-}
-}  // namespace mh
-
-extern "C" int mh_t5_slots_open(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
-                                const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
-                                const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
-                                void* stream, void** handle) {
-  return mh::slots_open_impl(c, w, S, sp, rows, eos_tables, n_eos_sets, cross_kv_slots, tokens, logits_dump, forced, self_kv_fp8, workspace,
-                             workspace_bytes, poll_every, stream, handle, false, "mh_t5_slots_open");
-}
-
-extern "C" int mh_t5_slots_open_kv8(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
-                                    const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
-                                    const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
-                                    void* stream, void** handle) {
-  // with neither copy this is mh_t5_slots_open (which then refuses a NULL cross_kv_slots as ever)
-  const bool kv8 = (sp && sp->cross_kv_fp8) || self_kv_fp8;
-  return mh::slots_open_impl(c, w, S, sp, rows, eos_tables, n_eos_sets, cross_kv_slots, tokens, logits_dump, forced, self_kv_fp8, workspace,
-                             workspace_bytes, poll_every, stream, handle, kv8, "mh_t5_slots_open_kv8");
-}
-
-extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
-                                 void* stream) {
-  using namespace mh;
-  SlotSession* ss = (SlotSession*)handle;
-  const char* who = "mh_t5_slots_admit";
-  MH_REQUIRE(ss, "%s: null handle", who);
-  OptionScope option_scope(ss->c->options);
-  MH_REQUIRE(cross_kv_row && prompt, "%s: null argument", who);
-  MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
-  MH_REQUIRE(!ss->live[slot], "%s: slot %d is live (release it first)", who, slot);
-  MH_REQUIRE(P >= 1 && P < ss->max_length, "%s: prompt length %d must be in [1, max_length)", who, P);
-  DeviceGuard device_guard(ss->dev);
-  const MhT5Config* c = ss->c;
-  const int ci = ss->chain_of(slot), es = es_of(c->dtype), H = c->n_heads, inner = H * 64;
-  hipStream_t as = ss->admit_stream;
-  if (hipStreamWaitEvent(as, ss->freed[slot], 0) != hipSuccess) return check_launch("admit wait");
-  if (stream) {   // the caller's stream wrote cross_kv_row / prompt / prompt_mask: the admission reads them behind that work
-    if (!ss->caller_ev && hipEventCreateWithFlags(&ss->caller_ev, hipEventDisableTiming) != hipSuccess) return check_launch("admit event create");
-    if (hipEventRecord(ss->caller_ev, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(as, ss->caller_ev, 0) != hipSuccess)
-      return check_launch("admit caller wait");
-  }
-  // the window's compact cross K/V [n_dec][2][1][H][L][64] -> row `slot` of [n_dec][2][S][H][L][64]
-  const size_t row_bytes = (size_t)H * c->src_len * 64 * es;
-  if (ss->cross_kv && hipMemcpy2DAsync(ss->cross_kv + (size_t)slot * row_bytes, (size_t)ss->S * row_bytes, cross_kv_row, row_bytes, row_bytes,
-                                       (size_t)c->n_dec_layers * 2, hipMemcpyDeviceToDevice, as) != hipSuccess)
-    return check_launch("admit cross K/V copy");
-  if (ss->cross8) {   // ... and, quantised, -> row `slot` of the S-row e4m3 copy (bytes and scales; no other row is touched)
-    hipLaunchKernelGGL(kv_quant_fp8_row_kernel, dim3(c->n_dec_layers * 2 * H), dim3(256), 0, as, (const bf16_t*)cross_kv_row, ss->cross8,
-                       reinterpret_cast<float*>(ss->cross8 + cross_kv8_layout(c, ss->S).scales_offset), c->src_len, H, ss->S, slot);
-    MH_TRY(check_launch("kv_quant_fp8_row_kernel"));
-  }
-  int32_t* trow = ss->tokens + (long)slot * ss->max_length;
-  uint8_t* mrow = ss->mask + (long)slot * ss->max_length;
-  if (hipMemcpyAsync(trow, prompt, (size_t)P * 4, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit prompt copy");
-  if (hipMemsetAsync(mrow, 1, (size_t)ss->max_length, as) != hipSuccess) return check_launch("admit mask set");
-  if (prompt_mask && hipMemcpyAsync(mrow, prompt_mask, (size_t)P, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit mask copy");
-  int start_pos = 0;
-  if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {   // positions 0 .. P-2 into the slot's cache rows: the B = 1 prefill of a uniform call
-    PrefillBuf pb;
-    prefill_layout(c, 1, P - 1, ss->prefill_base, ss->prefill_bytes, &pb);
-    const long cache_row = (long)slot * inner * c->tgt_len * es;
-    MH_TRY(prefill_prompt(c, ss->w, cross_kv_row, 1, 1, prompt, prompt_mask, P, P - 1, (char*)ss->ly.bf.self_k + cache_row,
-                          (char*)ss->ly.bf.self_v + cache_row, pb, as, ss->S));
-    start_pos = P - 1;
-    if (ss->self8) {   // the prefilled positions 0 .. P-2 of the slot's cache rows -> the same places of the S-row shadow, every layer,
-                       // k and v (the pass a uniform call makes after its prefill); nothing else of the shadow is written
-      const long row0 = (long)slot * H * c->tgt_len, plane_rows = (long)ss->S * H * c->tgt_len;
-      hipLaunchKernelGGL(self_kv_quant_rows_kernel, dim3((unsigned)(((long)H * start_pos + 3) / 4), 2 * c->n_dec_layers), dim3(256), 0, as,
-                         (const bf16_t*)ss->ly.bf.self_k + row0 * 64, (const bf16_t*)ss->ly.bf.self_v + row0 * 64, ss->self8 + row0 * 64,
-                         reinterpret_cast<float*>(ss->self8 + self_kv8_layout(c, ss->S).scales_offset) + row0, (long)H, (long)start_pos,
-                         (long)c->tgt_len, plane_rows);
-      MH_TRY(check_launch("self_kv_quant_rows_kernel"));
-    }
-  }
-  const SampleP& smp = ss->calls[ci].smp;
-  if (c->dtype == MH_BF16) hipLaunchKernelGGL(dec_slot_init_kernel<bf16_t>, dim3(1), dim3(256), 0, as, smp, slot, P, start_pos, ss->pos, ss->plen);
-  else hipLaunchKernelGGL(dec_slot_init_kernel<float>, dim3(1), dim3(256), 0, as, smp, slot, P, start_pos, ss->pos, ss->plen);
-  MH_TRY(check_launch("dec_slot_init_kernel"));
-  if (hipEventRecord(ss->admitted[ci], as) != hipSuccess) return check_launch("admit record");
-  ss->pending[ci] = true;
-  ss->live[slot] = true;
-  return MH_OK;
-}
-
-extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out, int32_t* length_out, int32_t* steps_out) {
-  using namespace mh;
-  SlotSession* ss = (SlotSession*)handle;
-  const char* who = "mh_t5_slots_run";
-  MH_REQUIRE(ss, "%s: null handle", who);
-  OptionScope option_scope(ss->c->options);
-  MH_REQUIRE(n_steps >= 0 && finished_out && length_out, "%s: bad argument", who);
-  DeviceGuard device_guard(ss->dev);
-  int steps[kMaxChains] = {}, which[kMaxChains], n_run = 0;   // which: the chains with a live slot run
-  bool runs[kMaxChains] = {};
-  for (int b = 0; b < ss->S; ++b) if (ss->live[b]) runs[ss->chain_of(b)] = true;
-  for (int ci = 0; ci < ss->n_chains; ++ci) {
-    if (!runs[ci]) continue;
-    which[n_run++] = ci;
-    // The fused tail's hand-off counters only ever grow inside a call, and a launch takes its base as a multiple of its grid: a
-    // session has no dec_init_kernel between its steps, so they start every run at zero (the chain is idle here: the last run
-    // ended with its poll) and cannot wrap however long the session lives.  tail_err stays: a timed-out session stays reported.
-    if (n_steps > 0 && hipMemsetAsync(ss->chains[ci].st->tail_cnt, 0, sizeof(ss->chains[ci].st->tail_cnt), ss->chains[ci].stream) != hipSuccess)
-      return check_launch("tail counter reset");
-    if (ss->pending[ci]) {   // the step that first sees the admitted slots live waits for their admissions
-      if (hipStreamWaitEvent(ss->chains[ci].stream, ss->admitted[ci], 0) != hipSuccess) return check_launch("admission wait");
-      ss->pending[ci] = false;
-    }
-  }
-  int rc = n_steps > 0 ? launch_chains(ss->chains, which, n_run, n_steps, ss->poll_every, true, who, steps) : MH_OK, total = 0;
-  for (int ci = 0; ci < ss->n_chains; ++ci) total += steps[ci];
-  // one poll per chain: its rows' flags, finish columns and positions, and the bounded hand-offs' last word
-  for (int ci = 0; ci < ss->n_chains; ++ci) {
-    const int b0 = ci * ss->rows_per, n = ss->calls[ci].Bc;
-    hipStream_t cs = ss->chains[ci].stream;
-    int word[2] = {0, 0};
-    if (hipMemcpyAsync(ss->host_fin + b0, ss->ly.bf.finished + b0, (size_t)n, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-        hipMemcpyAsync(ss->host_col + b0, ss->ly.bf.finish_col + b0, (size_t)n * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-        hipMemcpyAsync(ss->host_pos + b0, ss->pos + b0, (size_t)n * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-        hipMemcpyAsync(word, &ss->chains[ci].st->n_running, 8, hipMemcpyDeviceToHost, cs) != hipSuccess ||
-        hipStreamSynchronize(cs) != hipSuccess)
-      return check_launch("slot poll");
-    if (rc == MH_OK && word[1] != 0) rc = mh_t5_decode_tail_status(word[1]);
-  }
-  for (int b = 0; b < ss->S; ++b) {
-    const bool fin = ss->live[b] && ss->host_fin[b] != 0;
-    finished_out[b] = fin ? 1 : 0;
-    length_out[b] = !ss->live[b] ? 0 : (fin ? ss->host_col[b] + 1 : ss->host_pos[b] + 1);
-  }
-  if (steps_out) *steps_out = total;
-  return rc;
-}
-
-extern "C" int mh_t5_slots_release(void* handle, int slot) {
-  using namespace mh;
-  SlotSession* ss = (SlotSession*)handle;
-  const char* who = "mh_t5_slots_release";
-  MH_REQUIRE(ss, "%s: null handle", who);
-  MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
-  MH_REQUIRE(ss->live[slot], "%s: slot %d is idle", who, slot);
-  DeviceGuard device_guard(ss->dev);
-  const int ci = ss->chain_of(slot);
-  hipStream_t cs = ss->chains[ci].stream;
-  if (ss->pending[ci]) {   // released before a step saw it: still behind its own admission
-    if (hipStreamWaitEvent(cs, ss->admitted[ci], 0) != hipSuccess) return check_launch("admission wait");
-    ss->pending[ci] = false;
-  }
-  // on the chain's stream, behind the slot's last step: idle again (negative position, flag set), then the event an admission waits for
-  if (hipMemsetAsync(ss->pos + slot, 0xff, 4, cs) != hipSuccess || hipMemsetAsync(ss->ly.bf.finished + slot, 1, 1, cs) != hipSuccess ||
-      hipEventRecord(ss->freed[slot], cs) != hipSuccess)
-    return check_launch("slot release");
-  ss->live[slot] = false;
-  return MH_OK;
-}
-
-extern "C" int mh_t5_slots_close(void* handle) {
-  using namespace mh;
-  SlotSession* ss = (SlotSession*)handle;
-  if (!ss) return MH_OK;
-  DeviceGuard device_guard(ss->dev);
-  delete ss;   // joins the chains, then releases the graph references (the cross-call cache keeps the graphs it owns)
-  return check_launch("slot close");
-}
-
-// ------------------------------------------------------------------------------------------------
-// Teacher-forced decoder forward over whole sequences: the `Mapperatorinator.forward` seam (B2,
-// modeling_mapperatorinator.py:174-228) with `encoder_outputs` given -- every position of `ids` goes through the
-// decoder stack at once (the batched prefill path: MFMA GEMMs + flash attention, causal + key mask), then the
-// final RMSNorm and lm_head.  logits fp32 [B, T, V].
-extern "C" int64_t mh_t5_forward_workspace_bytes(const MhT5Config* c, int B, int T) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0 || T <= 0) return -1;
-  const int64_t es = es_of(c->dtype);
-  return mh::prefill_layout(c, B, T, nullptr, 0, nullptr) +
-         2 * mh::align256((int64_t)c->n_dec_layers * B * c->n_heads * 64 * c->tgt_len * es);
-}
-
-extern "C" int mh_t5_decoder_forward(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B,
-                                     const int32_t* ids, const uint8_t* mask, int T, float* logits, void* workspace,
-                                     int64_t workspace_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_decoder_forward"));
-  MH_REQUIRE(w && cross_kv && ids && logits && workspace, "mh_t5_decoder_forward: null argument");
-  MH_REQUIRE(B > 0 && T >= 1 && T <= c->tgt_len, "mh_t5_decoder_forward: T=%d not in [1, tgt_len=%d]", T, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_forward_workspace_bytes(c, B, T), "mh_t5_decoder_forward: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype);
-  const int64_t cache = align256((int64_t)c->n_dec_layers * B * c->n_heads * 64 * c->tgt_len * es);
-  char* self_k = (char*)workspace;
-  char* self_v = self_k + cache;
-  PrefillBuf pb;
-  prefill_layout(c, B, T, self_v + cache, workspace_bytes - 2 * cache, &pb);
-  MH_TRY(prefill_prompt(c, w, cross_kv, B, B, ids, mask, T, T, self_k, self_v, pb, s));
-  const int rows = B * T, d = c->d_model;
-  MH_TRY(pre_norm(c, pb.h, w->dec_final_ln, w->dec_final_ln_b, pb.n, rows, c->dtype, s));
-  MhGemm g{};
-  g.A = pb.n; g.lda = d; g.W = w->lm_head; g.ldw = d; g.C = logits; g.ldc = c->vocab_out; g.M = rows; g.N = c->vocab_out;
-  g.K = d; g.dtype = c->dtype; g.epilogue = MH_EPI_STORE_F32;
-  return gemm(g, s);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Teacher-forced scoring: the decoder stack exactly as mh_t5_decoder_forward runs it, then final norm -> lm_head -> row
-// statistics (score.hip) over the SCORED positions only, `score_block_rows` of them at a time through one fp32 logits scratch:
-// B*T*V logits never exist.  The scored positions are compacted on the device (row-major (b, t) order, no host round trip); the
-// LM-head GEMM of a block is planned as the whole [B*T, V] GEMM of the forward, so a position's logits -- and with them its
-// statistics -- are bit for bit those of mh_t5_decoder_forward + mh_score_rows.
-namespace mh {
-namespace {
-struct ScoreBuf { float* logits; float* hc; int32_t* map; int32_t* count; int C, ldv; };
-int64_t score_layout(const MhT5Config* c, int B, int T, void* base, int64_t size, ScoreBuf* out) {
-  Arena ar(base, size);
-  const int64_t rows = (int64_t)B * T;
-  long C = option(OPT_SCORE_BLOCK_ROWS);
-  C = C < 1 ? 1 : C;
-  ScoreBuf t;
-  t.C = (int)(C < rows ? C : rows);
-  // rows of the scratch start 16-byte aligned.  The forward stores its logits with ldc = V; the bf16 dispatch looks at ldc % 4
-  // (`vec_ok`, gemm.hip dispatch_tile) only in a conjunction with N % 4, and N = V in both calls, so the rounding cannot select
-  // another kernel than the forward's -- keep it that way (bit-equality with mh_t5_decoder_forward rests on the same kernel)
-  t.ldv = round_up(c->vocab_out, 4);
-  t.logits = (float*)ar.take((int64_t)t.C * t.ldv * 4);
-  t.hc = (float*)ar.take((int64_t)t.C * c->d_model * 4);
-  t.map = (int32_t*)ar.take(rows * 4);
-  t.count = (int32_t*)ar.take(4);
-  if (out) *out = t;
-  return ar.off;
-}
-}  // namespace
-}  // namespace mh
-
-extern "C" int64_t mh_t5_score_workspace_bytes(const MhT5Config* c, int B, int T) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0 || T <= 0) return -1;
-  return mh_t5_forward_workspace_bytes(c, B, T) + mh::score_layout(c, B, T, nullptr, 0, nullptr);
-}
-
-extern "C" int mh_t5_score(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, const int32_t* ids,
-                           const uint8_t* mask, int T, const int32_t* targets, int max_scored, float* surprisal, float* entropy,
-                           float* relative, float* logprob, int32_t* best_id, void* workspace, int64_t workspace_bytes,
-                           void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_score"));
-  MH_REQUIRE(w && cross_kv && ids && targets && surprisal && entropy && relative && logprob && best_id && workspace,
-             "mh_t5_score: null argument");
-  MH_REQUIRE(B > 0, "mh_t5_score: batch %d must be positive", B);
-  MH_REQUIRE(T >= 1 && T <= c->tgt_len, "mh_t5_score: T=%d not in [1, tgt_len=%d]", T, c->tgt_len);
-  MH_REQUIRE((int64_t)B * T <= INT32_MAX, "mh_t5_score: B*T = %lld positions exceed the int32 index range", (long long)B * T);
-  MH_REQUIRE(workspace_bytes >= mh_t5_score_workspace_bytes(c, B, T), "mh_t5_score: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int es = es_of(c->dtype);
-  const int64_t fwd = mh_t5_forward_workspace_bytes(c, B, T);
-  const int64_t cache = align256((int64_t)c->n_dec_layers * B * c->n_heads * 64 * c->tgt_len * es);
-  char* self_k = (char*)workspace;
-  char* self_v = self_k + cache;
-  PrefillBuf pb;
-  prefill_layout(c, B, T, self_v + cache, fwd - 2 * cache, &pb);
-  ScoreBuf sb;
-  score_layout(c, B, T, (char*)workspace + fwd, workspace_bytes - fwd, &sb);
-  MH_TRY(prefill_prompt(c, w, cross_kv, B, B, ids, mask, T, T, self_k, self_v, pb, s));
-  const int rows = B * T, d = c->d_model, V = c->vocab_out;
-  MH_TRY(score_compact(targets, rows, V, sb.map, sb.count, surprisal, entropy, relative, logprob, best_id, s));
-  const int cap = (max_scored >= 0 && max_scored < rows) ? max_scored : rows;   // negative: unknown, every position may be scored
-  for (int base = 0; base < cap; base += sb.C) {
-    // the block's hidden rows (zeros behind the end of the list) -> final norm (pb.n is free after the stack) -> logits -> statistics
-    MH_TRY(score_gather(pb.h, d, sb.map, sb.count, base, cap, sb.hc, sb.C, s));
-    MH_TRY(pre_norm(c, sb.hc, w->dec_final_ln, w->dec_final_ln_b, pb.n, sb.C, c->dtype, s));
-    MhGemm g{};
-    g.A = pb.n; g.lda = d; g.W = w->lm_head; g.ldw = d; g.C = sb.logits; g.ldc = sb.ldv; g.M = sb.C; g.N = V;
-    g.K = d; g.dtype = c->dtype; g.epilogue = MH_EPI_STORE_F32;
-    MH_TRY(gemm(g, s, false, rows));
-    MH_TRY(score_rows(sb.logits, sb.ldv, sb.C, V, targets, sb.map, sb.count, base, cap, surprisal, entropy, relative, logprob,
-                      best_id, s));
-  }
-  return MH_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2760,12 +1202,6 @@ extern "C" int mh_t5_decode_tail_status(int err_word) {
 // that option decode_fused_tail = 1 really took the fused path for its shape instead of the silent three-launch fall-back
 extern "C" long mh_t5_decode_tail_launches(void) { return mh::g_tail_launches.load(); }
 
-extern "C" int mh_t5_decode_chains(int B) { return B > 0 ? mh::pick_chains(B) : 0; }
-extern "C" int mh_t5_decode_chains_cfg(const MhT5Config* c, int B) {   // ... under the engine's option set
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return B > 0 ? mh::pick_chains(B) : 0;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Measurement hook for bench.py's roofline line: the dominant decode kernel (cross-attention over the
 // encoder keys) launched `reps` times back to back between two HIP events ON THE GIVEN STREAM, cycling
@@ -2805,204 +1241,4 @@ extern "C" int mh_t5_cross_attn_probe(const MhT5Config* c, const MhT5Weights* w,
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return rc;
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// Step-wise decode for host-driven search (beam search: HF `GenerationMixin._beam_search` drives the model one position at a
-// time and reorders its cache, osuT5/osuT5/inference/cache_utils.py:16-20).  The workspace is the one of mh_t5_generate
-// (mh_t5_decode_workspace_bytes) and holds the self-attention K/V caches between calls.
-// mh_t5_step (fp8 = false) and mh_t5_step_fp8
-static int step_impl(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, bool fp8, const void* cross_kv_fp8, int B,
-                     int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace,
-                     int64_t workspace_bytes, void* stream, const char* who,   // who: the entry the caller used (error messages)
-                     bool indexed = false, const uint8_t* origin = nullptr,
-                     bool shadow = false, void* self_kv_fp8 = nullptr) {   // shadow: mh_t5_step_indexed_skv8 (the caller's e4m3 self cache)
-  MH_TRY(check_cfg(c, who));
-  MH_TRY(check_decode_shape(c, who));
-  MH_REQUIRE(w && cross_kv && (cross_kv_fp8 || !fp8) && ids && logits && workspace && (origin || !indexed) && (self_kv_fp8 || !shadow),
-             "%s: null argument", who);
-  MH_REQUIRE(!shadow || c->dtype == MH_BF16, "%s: the e4m3 self-attention cache needs bf16 storage", who);
-  MH_REQUIRE(!indexed || c->tgt_len <= dec::kSelfIdxMaxTgt, "%s: the index table covers tgt_len <= %d (got %d)", who,
-             dec::kSelfIdxMaxTgt, c->tgt_len);
-  MH_REQUIRE(!fp8 || c->dtype == MH_BF16, "%s: the fp8 cross K/V copy needs bf16 storage", who);
-  MH_REQUIRE(B > 0 && B <= 64, "%s: batch %d not in [1, 64]", who, B);
-  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "%s: %d rows are not whole groups of %d", who, B, kv_group);
-  MH_REQUIRE(pos >= 0 && pos < c->tgt_len, "%s: position %d outside the cache (tgt_len %d)", who, pos, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "%s: workspace too small", who);
-  MH_TRY(check_arch2_weights(c, w, who));
-  hipStream_t s = (hipStream_t)stream;
-  StepCall k;
-  step_call_init(&k, c, w);
-  k.cross_kv = cross_kv; k.Bc = k.Bfull = B; k.kvB = B / kv_group; k.prompt_mask = prompt_mask; k.P = P; k.kv_group = kv_group;
-  k.bf = decode_layout(c, B, workspace).bf;
-  k.bf.logits = logits;   // (the host selects: the raw logits go straight to the caller)
-  k.origin = origin;
-  if (shadow) self8_rows(c, B, 0, self_kv_fp8, &k.bf);   // the whole batch is one chain
-  if (fp8) cross8_rows(c, k.kvB, 0, cross_kv_fp8, &k);
-  const float* dpos = c->arch == 2 ? w->dec_pos : nullptr;
-  const uint8_t* pmask = (c->arch == 2 && c->dec_pos_from_mask) ? prompt_mask : nullptr;
-  return dispatch_dtype(c->dtype, [&](auto t) {
-    using T = decltype(t);
-    hipLaunchKernelGGL(step_embed_kernel<T>, dim3(B), dim3(256), 0, s, ids, (const T*)w->dec_embed, c->d_model, k.bf.h, k.bf.st, pos, dpos, pmask, P);
-    MH_TRY(check_launch("step_embed_kernel"));
-    return enqueue_step<T>(k, s);
-  });
-}
-
-extern "C" int mh_t5_step(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kv_group, const int32_t* ids,
-                          int pos, const uint8_t* prompt_mask, int P, float* logits, void* workspace, int64_t workspace_bytes,
-                          void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return step_impl(c, w, cross_kv, false, nullptr, B, kv_group, ids, pos, prompt_mask, P, logits, workspace, workspace_bytes, stream, "mh_t5_step");
-}
-
-// mh_t5_step with the packed e4m3 copy of cross_kv (mh_t5_quantize_cross_kv over its B / kv_group rows) as one more argument: every
-// cross-attention of the step streams the copy, its scales indexed by the K/V row a decode row reads.  bf16 storage only.
-extern "C" int mh_t5_step_fp8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
-                              int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
-                              void* workspace, int64_t workspace_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return step_impl(c, w, cross_kv, true, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace, workspace_bytes, stream,
-                   "mh_t5_step_fp8");
-}
-
-// self-attention cache rows of every layer: row b <- row src[b] for positions 0 .. n_pos-1 (`cache.reorder_cache(beam_idx)`).
-// scratch: 2 * n_dec * B * inner * n_pos elements of the storage type (mh_t5_reorder_cache_scratch_bytes).
-extern "C" int64_t mh_t5_reorder_cache_scratch_bytes(const MhT5Config* c, int B, int n_pos) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  if (!c || B <= 0 || n_pos <= 0) return -1;
-  return align256(2LL * c->n_dec_layers * B * c->n_heads * 64 * n_pos * es_of(c->dtype));
-}
-extern "C" int mh_t5_reorder_cache(const MhT5Config* c, int B, const int32_t* src, int n_pos, void* workspace, int64_t workspace_bytes,
-                                   void* scratch, int64_t scratch_bytes, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_reorder_cache"));
-  MH_REQUIRE(src && workspace && scratch && B > 0 && B <= 64 && n_pos > 0 && n_pos <= c->tgt_len, "mh_t5_reorder_cache: bad argument");
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B) && scratch_bytes >= mh_t5_reorder_cache_scratch_bytes(c, B, n_pos),
-             "mh_t5_reorder_cache: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int H = c->n_heads;
-  const DecBuffers bf = decode_layout(c, B, workspace).bf;   // (the self-attention caches)
-  void* self_k = bf.self_k;
-  void* self_v = bf.self_v;
-  const long layer_stride = (long)B * H * c->tgt_len * 64;
-  const dim3 grid(B * H, c->n_dec_layers, 2);
-  return dispatch_dtype(c->dtype, [&](auto t) {
-    using T = decltype(t);
-    hipLaunchKernelGGL(cache_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)self_k, (const T*)self_v, (T*)scratch, src, B, H, c->tgt_len, n_pos, layer_stride);
-    hipLaunchKernelGGL(cache_scatter_kernel<T>, grid, dim3(256), 0, s, (T*)self_k, (T*)self_v, (const T*)scratch, B, H, c->tgt_len, n_pos, layer_stride);
-    return check_launch("cache reorder");
-  });
-}
-
-// ---- beam search by index: the self-attention cache stays where it was written ---------------------------------------------
-// The caches of a (chunk, beam) batch are never copied.  A table origin uint8 [B][tgt_len] says, per decode row b and position j, which
-// cache row holds that key / value; the step reads through it (dec_self_attn_qkv_kernel, IDX) and a reorder permutes table rows.  A
-// step writes position `pos` of cache row b and nothing else, so every (cache row, position) is written once and an entry never goes
-// stale.
-namespace mh {
-namespace {
-__global__ __launch_bounds__(256) void beam_index_init_kernel(uint8_t* origin, int tgt, int kv_group, int n_prefilled) {
-  const int b = blockIdx.x;
-  for (int j = threadIdx.x; j < tgt; j += 256) origin[(long)b * tgt + j] = (uint8_t)(j < n_prefilled ? b / kv_group : b);
-}
-// out[b][j] = in[src[b]][j] for j < n_pos, b beyond (src clamped to the batch: a table entry is always a cache row)
-__global__ __launch_bounds__(256) void beam_index_reorder_kernel(const uint8_t* in, uint8_t* out, const int32_t* src, int B, int tgt,
-                                                                int n_pos) {
-  const int b = blockIdx.x;
-  int sb = src[b];
-  sb = sb < 0 ? 0 : (sb >= B ? B - 1 : sb);
-  for (int j = threadIdx.x; j < tgt; j += 256) out[(long)b * tgt + j] = j < n_pos ? in[(long)sb * tgt + j] : (uint8_t)b;
-}
-}  // namespace
-}  // namespace mh
-
-extern "C" int64_t mh_t5_beam_index_bytes(const MhT5Config* c, int B) {
-  if (!c || B <= 0 || B > 64 || c->tgt_len <= 0) return -1;
-  return (int64_t)B * c->tgt_len;
-}
-
-extern "C" int mh_t5_beam_index_init(const MhT5Config* c, int B, int kv_group, int n_prefilled, void* origin, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_beam_index_init"));
-  MH_REQUIRE(origin, "mh_t5_beam_index_init: null argument");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_beam_index_init: batch %d not in [1, 64]", B);
-  MH_REQUIRE(kv_group >= 1 && B % kv_group == 0, "mh_t5_beam_index_init: %d rows are not whole groups of %d", B, kv_group);
-  MH_REQUIRE(n_prefilled >= 0 && n_prefilled < c->tgt_len, "mh_t5_beam_index_init: %d prefilled positions outside the cache (tgt_len %d)",
-             n_prefilled, c->tgt_len);
-  hipLaunchKernelGGL(mh::beam_index_init_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (uint8_t*)origin, c->tgt_len, kv_group,
-                     n_prefilled);
-  return check_launch("beam_index_init_kernel");
-}
-
-extern "C" int mh_t5_reorder_index(const MhT5Config* c, int B, const int32_t* src, int n_pos, const void* origin_in, void* origin_out,
-                                   void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_reorder_index"));
-  MH_REQUIRE(src && origin_in && origin_out, "mh_t5_reorder_index: null argument");
-  MH_REQUIRE(origin_in != origin_out, "mh_t5_reorder_index: origin_in and origin_out must be two tables (the caller ping-pongs)");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_reorder_index: batch %d not in [1, 64]", B);
-  MH_REQUIRE(n_pos > 0 && n_pos <= c->tgt_len, "mh_t5_reorder_index: %d positions outside the cache (tgt_len %d)", n_pos, c->tgt_len);
-  hipLaunchKernelGGL(mh::beam_index_reorder_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)origin_in,
-                     (uint8_t*)origin_out, src, B, c->tgt_len, n_pos);
-  return check_launch("beam_index_reorder_kernel");
-}
-
-// mh_t5_step / mh_t5_step_fp8 (cross_kv_fp8 != NULL) reading the cached keys / values through `origin`
-extern "C" int mh_t5_step_indexed(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
-                                  int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
-                                  void* workspace, int64_t workspace_bytes, const void* origin, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return step_impl(c, w, cross_kv, cross_kv_fp8 != nullptr, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace,
-                   workspace_bytes, stream, "mh_t5_step_indexed", true, (const uint8_t*)origin);
-}
-
-// mh_t5_step_indexed over the caller's e4m3 shadow of the self-attention cache (mh_t5_self_kv_fp8_bytes(cfg, B) bytes): cached rows
-// j < pos are the e4m3 rows of shadow row origin[b][j] with that row's scales; the new row is appended to shadow row b
-extern "C" int mh_t5_step_indexed_skv8(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, const void* cross_kv_fp8, int B,
-                                       int kv_group, const int32_t* ids, int pos, const uint8_t* prompt_mask, int P, float* logits,
-                                       void* workspace, int64_t workspace_bytes, const void* origin, void* self_kv_fp8, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  return step_impl(c, w, cross_kv, cross_kv_fp8 != nullptr, cross_kv_fp8, B, kv_group, ids, pos, prompt_mask, P, logits, workspace,
-                   workspace_bytes, stream, "mh_t5_step_indexed_skv8", true, (const uint8_t*)origin, true, self_kv_fp8);
-}
-
-// positions 0 .. n_pos-1 of cache rows 0 .. n_rows-1 (what mh_t5_step_prefill wrote, n_rows = Bp) of the bf16 self-attention caches of
-// a B-row step workspace -> the B-row shadow, every layer, k and v; nothing else of the shadow is written
-extern "C" int mh_t5_self_kv_fp8_fill(const MhT5Config* c, int B, int n_rows, int n_pos, void* workspace, int64_t workspace_bytes,
-                                      void* self_kv_fp8, void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_self_kv_fp8_fill"));
-  MH_REQUIRE(workspace && self_kv_fp8, "mh_t5_self_kv_fp8_fill: null argument");
-  MH_REQUIRE(c->dtype == MH_BF16, "mh_t5_self_kv_fp8_fill: the e4m3 self-attention cache needs bf16 storage");
-  MH_REQUIRE(c->tgt_len <= dec::kSelfIdxMaxTgt, "mh_t5_self_kv_fp8_fill: the index table covers tgt_len <= %d (got %d)",
-             dec::kSelfIdxMaxTgt, c->tgt_len);
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_self_kv_fp8_fill: batch %d not in [1, 64]", B);
-  MH_REQUIRE(n_rows >= 1 && n_rows <= B, "mh_t5_self_kv_fp8_fill: %d rows not in [1, %d]", n_rows, B);
-  MH_REQUIRE(B % n_rows == 0, "mh_t5_self_kv_fp8_fill: %d rows are not whole groups over %d prompts", B, n_rows);
-  MH_REQUIRE(n_pos >= 1 && n_pos < c->tgt_len, "mh_t5_self_kv_fp8_fill: %d positions outside the cache (tgt_len %d)", n_pos, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_self_kv_fp8_fill: workspace too small");
-  return launch_self_kv_quant_rows(c, B, decode_layout(c, B, workspace).bf, (uint8_t*)self_kv_fp8, n_rows, n_pos, (hipStream_t)stream);
-}
-
-// positions 0 .. n_pos-1 of Bp prompts through the batched prefill (prefill_prompt: HF's one forward over the prompt) into cache rows
-// 0 .. Bp-1 of a B-row step workspace
-extern "C" int mh_t5_step_prefill(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int Bp, const int32_t* prompt,
-                                  const uint8_t* prompt_mask, int P, int n_pos, void* workspace, int64_t workspace_bytes, int B,
-                                  void* stream) {
-  mh::OptionScope option_scope(c ? c->options : nullptr);
-  MH_TRY(check_cfg(c, "mh_t5_step_prefill"));
-  MH_TRY(check_decode_shape(c, "mh_t5_step_prefill"));
-  MH_REQUIRE(w && cross_kv && prompt && workspace, "mh_t5_step_prefill: null argument");
-  MH_REQUIRE(B > 0 && B <= 64, "mh_t5_step_prefill: batch %d not in [1, 64]", B);
-  MH_REQUIRE(Bp > 0 && B % Bp == 0, "mh_t5_step_prefill: %d rows are not whole groups over %d prompts", B, Bp);
-  MH_REQUIRE(n_pos >= 1 && n_pos <= P && n_pos < c->tgt_len, "mh_t5_step_prefill: %d positions outside the prompt (%d columns) or the cache (tgt_len %d)",
-             n_pos, P, c->tgt_len);
-  MH_REQUIRE(workspace_bytes >= mh_t5_decode_workspace_bytes(c, B), "mh_t5_step_prefill: workspace too small");
-  MH_TRY(check_arch2_weights(c, w, "mh_t5_step_prefill"));
-  const DecodeLayout ly = decode_layout(c, B, workspace);
-  PrefillBuf pb;
-  prefill_layout(c, Bp, n_pos, (char*)workspace + ly.end, workspace_bytes - ly.end, &pb);
-  return prefill_prompt(c, w, cross_kv, Bp, Bp, prompt, prompt_mask, P, n_pos, ly.bf.self_k, ly.bf.self_v, pb, (hipStream_t)stream, B);
 }

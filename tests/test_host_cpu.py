@@ -840,6 +840,17 @@ def test_device_code_diff_tells_equal_builds_from_a_changed_instruction(tmp_path
     changed = tmp_path / "changed.so"
     changed.write_bytes(bytes(blob))
     assert dcd.main([lib, str(changed)]) == 1
+    # --kernel: every kernel by instantiation name, function bytes and resource metadata alike (a small fragment keeps it quick)
+    ks = dcd.kernel_texts(lib, "score_rows_kernel")
+    assert ks and dcd.compare_kernels(ks, dict(ks)) == 0
+    name = sorted(ks)[0]
+    for field in (".vgpr_count", ".kernarg_segment_size"):      # ONE metadata value of ONE kernel record altered
+        i = dcd.META.index(field)
+        code, meta = ks[name]
+        assert dcd.compare_kernels(ks, {**ks, name: (code, meta[:i] + (int(meta[i]) + 1,) + meta[i + 1:])}) == 1
+    code, meta = ks[name]
+    assert dcd.compare_kernels(ks, {**ks, name: (code[:-4] + bytes(4), meta)}) == 1      # ... and its last instruction
+    assert dcd.compare_kernels(ks, {k: v for k, v in ks.items() if k != name}) == 1      # ... and the kernel gone
 
 
 def test_mx8_host_packer_oracle_and_torch_restatement_agree():

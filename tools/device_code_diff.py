@@ -7,9 +7,11 @@ the set of kernel symbols.  A host-only change must leave all of them as they we
 usage: device_code_diff.py OLD.so NEW.so      exit status 0: only __hip_cuid_* symbols differ, 1: anything else differs,
                                               3: a tool (llvm-objcopy / -readelf, PyYAML) is missing or failed
        device_code_diff.py --kernel FRAGMENT OLD.so NEW.so
-                                              for a change that adds kernels: the function bytes of every kernel of OLD whose mangled
-                                              name contains FRAGMENT against the same kernel of NEW (0: all equal, 1: one differs or
-                                              is gone)"""
+                                              for a change that adds kernels or moves them between code objects: the function bytes
+                                              and the resource metadata (registers, LDS, scratch, spills, kernarg size: META) of every
+                                              kernel of OLD whose mangled name contains FRAGMENT against the same kernel of NEW, found
+                                              in whichever code object holds it (0: all equal, 1: one differs or is gone; FRAGMENT ""
+                                              compares every kernel)"""
 from __future__ import annotations
 
 import hashlib
@@ -22,6 +24,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from check_kernel_resources import LLVM, code_objects, demangle, kernels_of  # noqa: E402
 
 SECTIONS = (".text", ".rodata", ".note")
+# what a kernel's `.note` record says of its resources (the record also names the kernel and types its arguments: a kernel whose
+# parameter type moved to another namespace keeps all of these)
+META = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count",
+        ".sgpr_spill_count", ".kernarg_segment_size", ".kernarg_segment_align", ".max_flat_workgroup_size", ".wavefront_size")
 
 
 def describe(elf: bytes):
@@ -42,12 +48,18 @@ def describe(elf: bytes):
 
 
 def kernel_texts(lib_path: str, fragment: str):
-    """-> {kernel symbol: the bytes of its function in .text} for every kernel of the library whose mangled name contains `fragment`"""
-    out = {}
+    """-> {instantiation: (the bytes of its function in .text, its META values)} for every kernel of the library whose mangled name
+    contains `fragment`"""
+    out, meta = {}, {}
     for elf in code_objects(lib_path):
-        wanted = {k[".symbol"].removesuffix(".kd") for k in kernels_of(elf) if fragment in k[".symbol"]}
+        recs = {k[".symbol"].removesuffix(".kd"): k for k in kernels_of(elf) if fragment in k[".symbol"]}
+        wanted = set(recs)
         if not wanted:
             continue
+        for sym, k in recs.items():
+            if sym in meta:
+                raise RuntimeError(f"{lib_path}: kernel {sym} is in two code objects")
+            meta[sym] = tuple(k.get(f) for f in META)
         with tempfile.TemporaryDirectory() as td:
             co, sec = os.path.join(td, "a.co"), os.path.join(td, "text.bin")
             open(co, "wb").write(elf)
@@ -72,13 +84,21 @@ def kernel_texts(lib_path: str, fragment: str):
                 return nm[:i]
         return nm
     syms = sorted(out)
-    return {instantiation(nm): out[s] for s, nm in zip(syms, demangle(syms))}
+    res = {instantiation(nm): (out[s], meta[s]) for s, nm in zip(syms, demangle(syms))}
+    if len(res) != len(out):   # two kernels that differ in their parameters only, or one anonymous-namespace name in two units
+        raise RuntimeError(f"{lib_path}: {len(out)} kernels have only {len(res)} distinct instantiation names")
+    return res
 
 
 def main_kernels(old_lib: str, new_lib: str, fragment: str) -> int:
     """--kernel FRAGMENT: a change that ADDS instantiations moves the code object as a whole; what must hold then is that every
     kernel the old build has comes out with the same instructions (branches are pc-relative, so equal code has equal bytes)"""
-    old, new = kernel_texts(old_lib, fragment), kernel_texts(new_lib, fragment)
+    return compare_kernels(kernel_texts(old_lib, fragment), kernel_texts(new_lib, fragment), fragment, old_lib)
+
+
+def compare_kernels(old: dict, new: dict, fragment: str = "", old_lib: str = "the old build") -> int:
+    """{instantiation: (function bytes, META values)} of two builds -> 0: every kernel of `old` is in `new` with the same bytes and
+    metadata, 1: one differs or is gone"""
     if not old:
         raise RuntimeError(f"no kernel matching {fragment!r} in {old_lib}")
     # a change that adds a template flag (defaulted to false, at the end of the list) renames every old instantiation to
@@ -94,10 +114,15 @@ def main_kernels(old_lib: str, new_lib: str, fragment: str) -> int:
     changed = [s for s in sorted(old) if s in new and old[s] != new[s]]
     gone = [s for s in sorted(old) if s not in new]
     for s in changed:
-        print(f"!! {s}: {len(old[s])} bytes {hashlib.sha1(old[s]).hexdigest()[:12]} -> {len(new[s])} bytes {hashlib.sha1(new[s]).hexdigest()[:12]}")
+        (ob, om), (nb, nm) = old[s], new[s]
+        if ob != nb:
+            print(f"!! {s}: {len(ob)} bytes {hashlib.sha1(ob).hexdigest()[:12]} -> {len(nb)} bytes {hashlib.sha1(nb).hexdigest()[:12]}")
+        for f, a, b in zip(META, om, nm):
+            if a != b:
+                print(f"!! {s}: {f} {a} -> {b}")
     for s in gone:
         print(f"!! removed: {s}")
-    print(f"{len(old)} kernels matching {fragment!r} in the old build: {len(old) - len(changed) - len(gone)} with identical bytes, "
+    print(f"{len(old)} kernels matching {fragment!r} in the old build: {len(old) - len(changed) - len(gone)} with identical bytes and metadata, "
           f"{len(changed)} changed, {len(gone)} removed; {len(set(new) - set(old))} added by the new build")
     return 1 if changed or gone else 0
 
