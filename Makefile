@@ -5,9 +5,9 @@ CSRC := mapperatorinator_amd/csrc
 OBJDIR := build/obj
 LIB := mapperatorinator_amd/lib/libmapperhip.so
 SRCS := $(CSRC)/api.hip $(CSRC)/gemm.hip $(CSRC)/mx8.hip $(CSRC)/norm.hip $(CSRC)/attention.hip $(CSRC)/mel.hip $(CSRC)/conv.hip \
-	$(CSRC)/t5_encode.hip $(CSRC)/t5.hip $(CSRC)/t5_generate.hip $(CSRC)/t5_stepwise.hip $(CSRC)/beam.hip $(CSRC)/dit.hip $(CSRC)/slider.hip $(CSRC)/score.hip
+	$(CSRC)/t5_encode.hip $(CSRC)/t5_step.hip $(CSRC)/decode_gemv.hip $(CSRC)/decode_attn_bf16.hip $(CSRC)/decode_attn_f32.hip \
+	$(CSRC)/decode_sample.hip $(CSRC)/t5_generate.hip $(CSRC)/t5_stepwise.hip $(CSRC)/beam.hip $(CSRC)/dit.hip $(CSRC)/slider.hip $(CSRC)/score.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
-HDRS := $(wildcard $(CSRC)/*.hpp) include/mapperhip.h
 # -amdgpu-kernarg-preload-count: leading scalar kernel arguments arrive in SGPRs with the wave launch (gfx950 firmware)
 # instead of through an s_load from the kernarg segment -- one memory round trip off every small dependent kernel
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed -mllvm -amdgpu-kernarg-preload-count=14
@@ -18,9 +18,10 @@ EXTRA_attention := -fno-slp-vectorize
 
 all: $(LIB)
 
-$(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
+# an object depends on the headers it really includes: the compiler writes them beside it (build/obj/%.d)
+$(OBJDIR)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -MMD -MP -c $< -o $@
 
 $(LIB): $(OBJS)
 	@mkdir -p $(dir $(LIB))
@@ -31,9 +32,9 @@ PROF_OBJDIR := build/prof
 PROF_LIB := mapperatorinator_amd/lib/libmapperhip_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(SRCS))
 
-$(PROF_OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
+$(PROF_OBJDIR)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(PROF_OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -DMH_PHASE_STAMPS -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -DMH_PHASE_STAMPS -MMD -MP -c $< -o $@
 
 $(PROF_LIB): $(PROF_OBJS)
 	@mkdir -p $(dir $(PROF_LIB))
@@ -53,5 +54,7 @@ clean:
 # the units, one per line-separated word: tools/build_variant.sh takes its object list from here
 print-srcs:
 	@echo $(SRCS)
+
+-include $(OBJS:.o=.d) $(PROF_OBJS:.o=.d)
 
 .PHONY: all clean prof variant print-srcs

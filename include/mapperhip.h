@@ -640,7 +640,7 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
  * What a slot computes: the batch-1 call mh_t5_generate_rows(B = 1, the window's unpadded prompt and mask, rows[slot]) -- token ids
  *   up to the row's end and its rows of logits_dump, bit for bit (rows are batch-invariant).  The slot sits at its own columns
  *   0 .. n: no left padding, RoPE rows / learned positions / the relative bias are those of the row's own position.
- * Kernels: the token step of mh_t5_generate_rows with two kernels in their slot form (csrc/decode_kernels.hpp, csrc/t5.hip): the
+ * Kernels: the token step of mh_t5_generate_rows with two kernels in their slot form (csrc/decode_self_attn.hpp, csrc/decode_sample.hpp): the
  *   self-attention reads the position of row b from an int32 [S] array (negative: the slot is idle and its workgroups return before
  *   they store anything), the sampler reads and advances that position, the row's prompt length, pos_off, the parity of its score
  *   history and its row of logits_dump; a row that is done writes its finish column, sets its flag and stops (no pad ids, the

@@ -1,4 +1,4 @@
-// The body of the decode self-attention kernels (decode_kernels.hpp), as TEXT: included inside dec_self_attn_qkv_kernel and inside
+// The body of the decode self-attention kernels (decode_self_attn.hpp), as TEXT: included inside dec_self_attn_qkv_kernel and inside
 // dec_slot_self_attn_kernel, which differ in the constant SLOT alone.  (A shared __device__ function -- inlined, arguments by value or
 // by reference -- compiled 112 to 142 of the 144 existing instantiations to other instruction bytes; the text does not.)  In scope where
 // it is included: T, KC, WH, LN, F8, IDX, SLOT; the kernel arguments h_, lnw_, W_, pos_, kc_, vc_, H_, d_, p, hp and f8 (the trailing

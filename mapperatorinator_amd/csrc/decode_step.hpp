@@ -1,18 +1,16 @@
-// What the host units (t5_generate.hip, t5_stepwise.hip, t5_encode.hip) need of the token step (t5.hip): the structs a step is
+// What the host units (t5_step.hip, t5_generate.hip, t5_stepwise.hip, t5_encode.hip) need of the token step: the structs a step is
 // described by, the decode workspace layout, and plain host functions that launch the step's kernels.  No kernel is declared here:
-// every kernel of the token step is instantiated in t5.hip and nowhere else.
+// every kernel of the token step is instantiated in ONE unit -- decode_gemv.hip, decode_attn_bf16.hip, decode_attn_f32.hip,
+// decode_sample.hip -- and the families meet in enqueue_step (t5_step.hip), which is host code.
 #pragma once
 #include <string.h>
 
 #include <type_traits>
 
+#include "decode_params.hpp"
 #include "t5_host.hpp"
 
 namespace mh {
-
-namespace dec {
-constexpr int kSelfIdxMaxTgt = 2560;   // table entries of one row staged in LDS (the released tgt_seq_len)
-}  // namespace dec
 
 constexpr int kMaxChains = 8;
 
@@ -71,7 +69,7 @@ struct DecodeLayout {
   int32_t* pos_off; float* proc; float* hist_scores;
   int64_t end;                        // the batched prompt prefill's region starts here
 };
-// (t5.hip)
+// (t5_step.hip)
 DecodeLayout decode_layout(const MhT5Config* c, int B, void* base);
 
 // Everything ONE enqueue of a token step depends on: enqueue_step() reads this and option(), nothing else, and step_graph_key() makes
@@ -94,7 +92,7 @@ struct StepCall {
                                                  // (global row index; the SLOT kernels), else NULL.  Needs has_rows.
 };
 static_assert(std::is_trivially_copyable<StepCall>::value, "StepCall is keyed by its bytes");
-// (t5.hip: it reads the timing hook, which lives there)
+// (t5_step.hip: it reads the timing hook, which lives there)
 void step_call_init(StepCall* k, const MhT5Config* c, const MhT5Weights* w);
 
 // The first row of the e4m3 shadow of the self-attention cache, and of its scales, at row b0 of a B-row batch (the b0 offsets of the
@@ -125,11 +123,43 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
                    const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s,
                    int cache_rows = 0);
 
-// ---- launches of the token step's kernels (t5.hip) --------------------------------------------------------------------------------
-// Each enqueues on `s` in the storage type `dtype` (MH_F32 / MH_BF16) where the kernel has one, and returns check_launch() under the
-// kernel's name.
+// ---- the token step (t5_step.hip) --------------------------------------------------------------------------------------------------
 // One token step of the chain `k` describes: every layer, the LM head and (k.with_sampler) the sampler
 int enqueue_step(const StepCall& k, hipStream_t s);
+
+// ---- launches of the token step's kernels ------------------------------------------------------------------------------------------
+// Each enqueues on `s` in the storage type `dtype` (MH_F32 / MH_BF16) where the kernel has one, and returns check_launch() under the
+// kernel's name.  Each dispatches to the instantiations its unit holds; a combination that has no kernel is MH_ERR_ARG.
+// (decode_gemv.hip) gemv_kernel<dtype, rows of p.B, waves of p.K, pro, epi, bias>: PRO_* / SK_* of decode_params.hpp, in the seven
+// combinations a step uses -- (PLAIN, RESID, bias or not), (RMSNORM, GEGLU), (RMSNORM | LAYERNORM, GELU_ERF, bias), (RMSNORM |
+// LAYERNORM, LOGITS)
+int launch_gemv(int dtype, int pro, int epi, bool bias, const dec::SkinnyP& p, hipStream_t s);
+// whether dec_tail_kernel covers a chain of B rows of this model (wh: the Whisper family, with its three tail biases), else the three
+// launches run; and the launch: o / wi / wo = the SkinnyP descriptions of the three launches it replaces, (prowi, epiwi, bias) = the
+// form of the wi GEMV, `st` / `layer` = whose hand-off counters, n_chains = chains that may run side by side
+bool tail_covers(const MhT5Config* c, int B, bool wh, const float* b_o, const float* b_fc1, const float* b_fc2);
+int launch_tail(int dtype, int prowi, int epiwi, bool bias, const dec::TailP& p, DecState* st, int layer, int n_chains, hipStream_t s);
+// (decode_attn_bf16.hip / decode_attn_f32.hip: the attention kernels of one storage type each)
+// dec_self_attn_qkv_kernel, or with slot_pos dec_slot_self_attn_kernel, in the form (sa.rope, hp.ln_b) say.  f8 != NULL: over this
+// layer's rows of the e4m3 shadow cache (bf16 storage only); origin != NULL: cached rows through the beam search's index table;
+// slot_pos != NULL: every row at its own position
+int launch_self_attn_bf16(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, const dec::SelfKv8P* f8, const uint8_t* origin,
+                          const int32_t* slot_pos, hipStream_t s);
+int launch_self_attn_f32(const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, const dec::SelfKv8P* f8, const uint8_t* origin,
+                         const int32_t* slot_pos, hipStream_t s);
+inline int launch_self_attn(int dtype, const dec::SelfAttnP& sa, const dec::HeadProjP& hp, int inner, const dec::SelfKv8P* f8,
+                            const uint8_t* origin, const int32_t* slot_pos, hipStream_t s) {
+  return dtype == MH_BF16 ? launch_self_attn_bf16(sa, hp, inner, f8, origin, slot_pos, s) : launch_self_attn_f32(sa, hp, inner, f8, origin, slot_pos, s);
+}
+// dec_cross_attn_q_kernel in the form (ca.scale != 0, hp.ln_b) say; ca.kscale != NULL: over the e4m3 copy (bf16 storage only)
+int launch_cross_attn_bf16(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s);
+int launch_cross_attn_f32(const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s);
+inline int launch_cross_attn(int dtype, const dec::CrossAttnP& ca, const dec::HeadProjP& hp, hipStream_t s) {
+  return dtype == MH_BF16 ? launch_cross_attn_bf16(ca, hp, s) : launch_cross_attn_f32(ca, hp, s);
+}
+// (decode_sample.hip, as everything below) dec_sample_kernel over the logits of k's chain: the uniform form, the per-row form
+// (k.has_rows) or the slot form (k.slot_pos)
+int launch_sample(int dtype, const StepCall& k, hipStream_t s);
 // dec_init_kernel over the chain_rows rows of smp's chain: the processors' state over prompt columns 0 .. start_pos, the chain's
 // DecState, the embedding of the token at start_pos
 int launch_dec_init(int dtype, const SampleP& smp, int chain_rows, int start_pos, hipStream_t s);
@@ -147,5 +177,12 @@ int launch_self_kv_quant_rows(const MhT5Config* c, int B, const DecBuffers& bf, 
 int launch_self_kv_quant_slot(const MhT5Config* c, int S, const DecBuffers& bf, uint8_t* self8, int slot, int n_pos, hipStream_t s);
 // kv_quant_fp8_row_kernel: a window's compact bf16 cross K/V [n_dec][2][1][H][L][64] -> row `slot` of the S-row e4m3 copy cross8
 int launch_cross_kv_quant_row(const MhT5Config* c, int S, const void* cross_kv_row, uint8_t* cross8, int slot, hipStream_t s);
+
+#ifdef MH_PHASE_STAMPS
+// profiling build only: acc (host, uint64 [16][16][2]) += the phase stamps of the unit's kernels; reset: cleared afterwards
+int gemv_phase_stamps(unsigned long long* acc, int reset);
+int attn_bf16_phase_stamps(unsigned long long* acc, int reset);
+int attn_f32_phase_stamps(unsigned long long* acc, int reset);
+#endif
 
 }  // namespace mh

@@ -265,7 +265,7 @@ int small_linear(const float* in, int ldi, const float* W, int ldw, const float*
 // The one-chunk DiT step is 48 GEMMs of 0.06-0.23 GFLOP behind one another (4 per block), and the LDS-tiled kernels take 10-13 us
 // each for them: tools/dit_gemm_probe.py -- 7.6-8.7 us even with every operand hot in L2 and the plain epilogue, because their K
 // loop is 2-6 dependent stages of (global load -> registers -> LDS -> barrier -> a serial chain of 32 exact-f32 MFMAs).  This form
-// is the decode GEMV's (decode_kernels.hpp): a workgroup owns ONE 16-row x 16-column tile, its NWV waves split K, and EVERY operand
+// is the decode GEMV's (decode_gemv.hpp): a workgroup owns ONE 16-row x 16-column tile, its NWV waves split K, and EVERY operand
 // of the tile -- its 16 activation rows and 16 weight rows over the whole K, the epilogue's old values, the modulation vectors --
 // is requested before the first wait: ONE memory round trip, then K / (16 NWV) x 4 MFMAs per wave, a cross-wave sum through LDS in
 // wave order (deterministic) and the epilogue.  The LayerNorm of a consuming GEMM (qkv, fc1) needs no statistics buffers: the

@@ -1,6 +1,6 @@
 // osuT5 on MI355X: the batched passes -- encoder stack, cross-attention K/V projection, the decoder's prompt prefill and the
 // teacher-forced decoder forward / scoring built on it.  All of them are MFMA GEMMs + flash attention over whole sequences; the row
-// kernels between them (conversions, rotate-half RoPE) live here.  The token-by-token decode is t5.hip (kernels, one step) under
+// kernels between them (conversions, rotate-half RoPE) live here.  The token-by-token decode is t5_step.hip and the decode_* units (kernels, one step) under
 // t5_generate.hip / t5_stepwise.hip (host loops).
 //
 // Reference semantics reproduced (see include/mapperhip.h for the per-entry citations):
@@ -411,7 +411,7 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
   // arch 1 (VarWhisperDecoderLayer, modeling_varwhisper.py:633-741) through the same batched form: biased projections,
   // rotate-half RoPE on q and on the cached keys, scores / 8 without a relative bias, fc1 -> gelu(erf) -> fc2.  A local
   // (windowed) layer takes its own rotary table and the causal attention gets the band |k - q| <= local_window on top -- the
-  // keys the token-by-token step attends (decode_kernels.hpp `window`).
+  // keys the token-by-token step attends (decode_params.hpp `window`).
   // arch 2 (HF WhisperDecoderLayer): the same with affine LayerNorms, absolute positions added to the embedding, no rotation
   const bool wh = c->arch >= 1, hf = c->arch == 2;
   if (wh && !hf) MH_REQUIRE(w->dec_rope != nullptr, "prefill: the Whisper family needs its rotary table");

@@ -2,7 +2,7 @@
 // hipGraph replay; the host only polls a 4-byte "rows still running" word.  Chains and their stream pools, the cross-call cache of
 // step graphs, the burst-and-poll launcher, mh_t5_generate* and the in-flight slot session mh_t5_slots_*.
 // Host code only: this unit defines no kernel and launches none itself -- what a step enqueues, and every kernel launch around it,
-// comes from t5.hip through decode_step.hpp (HF GenerationMixin._sample under model_generate, osuT5/osuT5/inference/server.py:83-156).
+// comes from t5_step.hip through decode_step.hpp (HF GenerationMixin._sample under model_generate, osuT5/osuT5/inference/server.py:83-156).
 #include <stdlib.h>
 #include <string.h>
 

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the T5 / Whisper-family units (t5_encode.hip, t5.hip, t5_generate.hip, t5_stepwise.hip):
+// Host-side helpers shared by the T5 / Whisper-family units (t5_encode.hip, t5_step.hip and the decode_* units, t5_generate.hip, t5_stepwise.hip):
 // configuration checks, the storage-type / d_model / attention-form dispatch, the layout of the packed e4m3 K/V copies.
 // Inline, host only: no kernel is declared or instantiated here.
 #pragma once

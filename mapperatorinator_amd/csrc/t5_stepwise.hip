@@ -1,6 +1,6 @@
 // Step-wise decode for host-driven search (beam search): one token step per call over the decode workspace (mh_t5_step*), the
 // self-attention cache reorder by copy and by index table, the e4m3 shadow fill and the step workspace's prompt prefill.  The step
-// itself is t5.hip's (decode_step.hpp); the small copy / table kernels of the search live here.
+// itself is t5_step.hip's (decode_step.hpp); the small copy / table kernels of the search live here.
 #include <stdlib.h>
 #include <string.h>
 

@@ -1,6 +1,6 @@
 """Host side of the osuT5 hot path: weight ingestion from the reference `state_dict()` names into
 packed device buffers, relative-bias lookup tables, and the mel -> encode -> cross-KV -> AR-decode
-driver around libmapperhip (csrc/t5_encode.hip, t5_generate.hip, t5_stepwise.hip over the token step of t5.hip).
+driver around libmapperhip (csrc/t5_encode.hip, t5_generate.hip, t5_stepwise.hip over the token step of t5_step.hip and the decode_* units).
 
 Numerics contract ("rounding points") of the two storage modes:
   fp32 : everything fp32; GEMMs on the exact-f32 MFMA atom (bitwise an fmaf chain).

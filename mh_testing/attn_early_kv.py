@@ -1,6 +1,6 @@
 """TEST SUPPORT: the decode runs behind tests/golden/attn_early_kv_tiny.npz (tests/test_gpu_attn_early_kv.py).
 
-The decode attention's key loop (`attend_keys`, csrc/decode_kernels.hpp) can run its first iteration on K / V rows that the kernel
+The decode attention's key loop (`attend_keys`, csrc/decode_device.hpp) can run its first iteration on K / V rows that the kernel
 requested before the query existed (`FirstKeys`); every sum keeps its operands and its order, so the scores must not move by a bit.
 The fixture holds the processed scores of short teacher-forced decodes as the build BEFORE that change dumped them, and the test
 compares a run of the current build bit for bit.  `run_case` is the one statement of every run, shared by the test and by the

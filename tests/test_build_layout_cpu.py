@@ -1,6 +1,8 @@
-"""Which translation unit owns which kernels, read from the built library: the token step's kernels are instantiated in ONE unit
-(csrc/t5.hip), and the decode host path (csrc/t5_generate.hip) has no device code at all -- so a change to the host path can
-neither move nor recompile a kernel.  Structure only: kernel names, code objects and the host's registration symbols."""
+"""Which translation unit owns which kernels, read from the built library: every decode kernel is instantiated in the ONE unit of its
+family (csrc/decode_gemv.hip, decode_attn_bf16.hip / decode_attn_f32.hip, decode_sample.hip), and the decode host path
+(csrc/t5_step.hip, t5_generate.hip) has no device code at all -- so a change to the host path can neither move nor recompile a kernel,
+and a change to one family recompiles that family alone.  Structure only: kernel names, code objects and the host's registration
+symbols."""
 from __future__ import annotations
 
 import importlib.util
@@ -71,29 +73,61 @@ def test_no_kernel_is_in_two_code_objects(layout):
             seen[nm] = cuid
 
 
-def test_the_token_step_kernels_are_in_one_unit(layout):
-    """every kernel named dec_*, and the GEMV / fused-tail kernels of decode_kernels.hpp, in the code object of t5.hip"""
+# The decode kernels and the unit that instantiates each.  A decode kernel: one whose name starts with `dec_`, or that lives in
+# mh::dec, or the step-wise embed, or one of the three e4m3 quantisers.  The attention kernels are cut by storage type (their first
+# template argument): every instantiation of one type is in that type's unit.
+_ATTN = {"float": "decode_attn_f32.hip", "unsigned short": "decode_attn_bf16.hip"}
+DECODE_KERNELS = {
+    "gemv_kernel": "decode_gemv.hip", "dec_tail_kernel": "decode_gemv.hip",
+    "dec_self_attn_qkv_kernel": _ATTN, "dec_slot_self_attn_kernel": _ATTN, "dec_cross_attn_q_kernel": _ATTN,
+    "dec_sample_kernel": "decode_sample.hip", "dec_init_kernel": "decode_sample.hip", "dec_slot_init_kernel": "decode_sample.hip",
+    "dec_finalize_kernel": "decode_sample.hip", "step_embed_kernel": "decode_sample.hip",
+    "kv_quant_fp8_kernel": "decode_sample.hip", "kv_quant_fp8_row_kernel": "decode_sample.hip",
+    "self_kv_quant_rows_kernel": "decode_sample.hip",
+}
+_QUANTISERS = {"kv_quant_fp8_kernel", "kv_quant_fp8_row_kernel", "self_kv_quant_rows_kernel"}
+
+
+def test_every_decode_kernel_is_in_the_unit_of_its_family(layout):
+    """every instantiation of a decode kernel is in exactly the code object that DECODE_KERNELS names for it, and the decode
+    kernels are exactly the names of that table"""
     unit_cuid, objects = layout
-    step = unit_cuid.get("t5.hip")
-    assert step and step in objects, unit_cuid
     where, other = {}, set()
     for cuid, names in objects.items():
         for nm in names:
             k = _kernel(nm)
-            if k.startswith("dec_") or "mh::dec::" in nm:     # a decode kernel by its name, or by the namespace of decode_kernels.hpp
-                where.setdefault(k, set()).add(cuid)
+            if k.startswith("dec_") or "mh::dec::" in nm or k == "step_embed_kernel" or k in _QUANTISERS:
+                first_arg = re.search(r"<([^,>]*)", nm)
+                where.setdefault((k, first_arg.group(1) if first_arg else None), set()).add(cuid)
             elif "dec_" in k:
                 other.add(k)
     # the one other name that contains "dec_": the diffusion loop's step counter (dit.hip), no kernel of the decode
     assert other == {"loop_dec_kernel"}, other
-    assert {"gemv_kernel", "dec_tail_kernel", "dec_self_attn_qkv_kernel", "dec_slot_self_attn_kernel", "dec_cross_attn_q_kernel",
-            "dec_sample_kernel", "dec_init_kernel", "dec_slot_init_kernel", "dec_finalize_kernel"} <= set(where), sorted(where)
-    assert all(v == {step} for v in where.values()), {k: v for k, v in where.items() if v != {step}}
+    assert {k for k, _ in where} == set(DECODE_KERNELS), sorted(where)
+    wrong = {}
+    for (k, t), cuids in where.items():
+        unit = DECODE_KERNELS[k]
+        if isinstance(unit, dict):
+            assert t in unit, (k, t)
+            unit = unit[t]
+        assert unit_cuid.get(unit), (unit, unit_cuid)
+        if cuids != {unit_cuid[unit]}:
+            wrong[(k, t)] = cuids
+    assert not wrong, wrong
+    for k, unit in DECODE_KERNELS.items():     # an attention kernel has instantiations of both storage types, each in its unit
+        if isinstance(unit, dict):
+            assert {t for kk, t in where if kk == k} == set(unit), k
+    # and the decode units hold nothing else
+    for unit in {u for v in DECODE_KERNELS.values() for u in (v.values() if isinstance(v, dict) else [v])}:
+        assert {_kernel(nm) for nm in objects[unit_cuid[unit]]} <= set(DECODE_KERNELS), unit
 
 
 def test_the_decode_host_path_has_no_device_code(layout):
-    """t5_generate.hip is linked in (its FILE symbol) and registers no code object: no kernel can sit in that unit"""
+    """t5_generate.hip and t5_step.hip (enqueue_step, the operand descriptions) are linked in (their FILE symbols) and register no
+    code object: no kernel can sit in those units"""
     unit_cuid, objects = layout
-    assert "t5_generate.hip" in unit_cuid and "t5.hip" in unit_cuid, sorted(unit_cuid)
-    cuid = unit_cuid["t5_generate.hip"]
-    assert cuid is None or not objects.get(cuid), objects.get(cuid)
+    assert "t5.hip" not in unit_cuid, sorted(unit_cuid)
+    for unit in ("t5_generate.hip", "t5_step.hip"):
+        assert unit in unit_cuid, sorted(unit_cuid)
+        cuid = unit_cuid[unit]
+        assert cuid is None or not objects.get(cuid), (unit, objects.get(cuid))

@@ -1,4 +1,4 @@
-"""-m gpu: the decode attention's first key iteration on K / V rows requested ahead of the query (csrc/decode_kernels.hpp: `FirstKeys`,
+"""-m gpu: the decode attention's first key iteration on K / V rows requested ahead of the query (csrc/decode_device.hpp: `FirstKeys`,
 `attend_keys<..., EARLY>`, `dec_cross_attn_q_kernel`) gives the bits of the build that requested them inside the key loop.
 
 Short teacher-forced decodes of tiny models dump the scores of every column; they equal, bit for bit, what the PARENT build dumped:

@@ -6,7 +6,10 @@ memory round trips; hipcc sometimes sinks loads next to their uses (`L W0 L W0 .
 costs ~1 us each beside the other chain's K/V stream -- this tool is how such schedules are found after an edit.
 (Loops are rotated by the compiler: textual order is not always execution order; read the .s next to it.)
 
-  python tools/isa_mem_signature.py [-DMACRO=..] [--file t5.hip] substr [substr ...]
+  python tools/isa_mem_signature.py [-DMACRO=..] [--file decode_attn_bf16.hip] substr [substr ...]
+
+--file: the unit that instantiates the kernels -- decode_attn_bf16.hip / decode_attn_f32.hip (self- and cross-attention),
+decode_gemv.hip (GEMVs, fused tail), decode_sample.hip (sampler).  Without substrings: the headline kernels of the unit.
 """
 import os
 import re
@@ -20,12 +23,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def main():
     defs = [a for a in sys.argv[1:] if a.startswith("-D")]
     args = [a for a in sys.argv[1:] if not a.startswith("-D")]
-    src = "t5.hip"
+    src = "decode_attn_bf16.hip"
     if "--file" in args:
         i = args.index("--file")
         src = args[i + 1]
         del args[i:i + 2]
-    keys = args or ["gemv_kernelItLi1E", "cross_attn_q_kernelItLi6ELi1ELb0", "self_attn_qkv_kernelItLi6", "dec_sample_kernelIt"]
+    headline = {"decode_attn_bf16.hip": ["cross_attn_q_kernelItLi6ELi1ELb0", "self_attn_qkv_kernelItLi6"],
+                "decode_attn_f32.hip": ["cross_attn_q_kernelIfLi6ELi1ELb0", "self_attn_qkv_kernelIfLi6"],
+                "decode_gemv.hip": ["gemv_kernelItLi1E"], "decode_sample.hip": ["dec_sample_kernelIt"]}
+    keys = args or headline.get(os.path.basename(src), [""])
     with tempfile.TemporaryDirectory() as td:
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed",
                "-mllvm", "-amdgpu-kernarg-preload-count=14", *defs, "-save-temps", "-c",

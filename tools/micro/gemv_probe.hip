@@ -1,4 +1,4 @@
-// Micro-benchmark: what does each part of the decode GEMV (csrc/decode_kernels.hpp: gemv_kernel) cost?
+// Micro-benchmark: what does each part of the decode GEMV (csrc/decode_gemv.hpp: gemv_kernel) cost?
 // Replays a graph of 72 dependent launches of the REAL kernel at the three decode shapes of osuT5-base (o / co
 // projection, wi + gated GELU, wo) on 16 rows, alone and as two concurrent chains, and prints microseconds per kernel.
 // Built several times with -DMH_GEMV_PROBE=<mask> (parts of the kernel switched off: 1 activation loads, 2 weight
@@ -8,7 +8,7 @@
 #include <stdlib.h>
 #include <thread>
 
-#include "../../mapperatorinator_amd/csrc/decode_kernels.hpp"
+#include "../../mapperatorinator_amd/csrc/decode_gemv.hpp"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
