@@ -680,8 +680,8 @@ int mh_t5_generate_rows(const MhT5Config* cfg, const MhT5Weights* w, const void*
  *   step; the caller reads tokens[slot] before it admits the next window there.
  * mh_t5_slots_close: joins the chains and the admissions, releases the graph references, frees the session.
  * Ordering is by events alone (release -> admit -> first step): nothing on the device spins or waits for another launch.  One host
- * thread per session.  Not built: guidance pairs, beams, teacher forcing, several rows per admission; the e4m3 caches are a switch
- * of the session (mh_t5_slots_open_kv8 below), not of this entry and not of a window. */
+ * thread per session.  Not built: beams, teacher forcing, several rows per admission; guidance pairs and the e4m3 caches are sessions
+ * of their own (mh_t5_slots_open_guided, mh_t5_slots_open_kv8 below), not switches of this entry and not of a window. */
 int64_t mh_t5_slots_workspace_bytes(const MhT5Config* cfg, int S);
 int mh_t5_slots_open(const MhT5Config* cfg, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
                      const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
@@ -725,6 +725,54 @@ int mh_t5_slots_open_kv8(const MhT5Config* cfg, const MhT5Weights* w, int S, con
                          const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
                          const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
                          void* stream, void** handle);
+
+/* In-flight slots under classifier-free guidance: a slot is a PAIR (additive at ABI 11: three symbols; the session stays an opaque
+ * handle, no struct changes layout; a library without them is an older 11).  Every slot holds the negative-prompt row and the prompt
+ * row of one window; the pair is admitted, stepped, finished and released together.  Opt-in: the entries above keep every refusal,
+ * guidance included.  mh_t5_slots_run / _release / _close serve the session as they are.
+ * What a slot computes: the batch-1 guided call mh_t5_generate_rows(B = 2, the two prompt rows [negative | prompt] -- the negative
+ *   prompt over the first columns of a copy of the prompt, both rows under the prompt's mask --, one cross K/V row, one MhRowSampling
+ *   entry with the pair's own cfg_scale, the same e4m3 modes): token ids up to the pair's end and the pair's row of logits_dump for
+ *   every column it produced, bit for bit; under the e4m3 modes the slot's rows of both copies hold, below the row's length, the bytes
+ *   and scales of that call's.
+ * Layout: S pairs are 2 S decode rows in the row order of a guided call, slot s = rows s (negative) and S + s (prompt); kvB = S: row
+ *   b streams cross K/V row b % S.  One chain, as every guided call runs (a pair spans both halves of the batch).
+ * Kernels: the token step of the guided mh_t5_generate_rows with the slot self-attention as it is -- one position entry per decode
+ *   row, equal within a pair -- and the sampler in its guided slot form (dec_sample_kernel<.., ROWS, SLOT, PAIR>,
+ *   csrc/decode_sample.hpp): one workgroup per pair; it reads the pair's position and prompt length, returns when the pair is idle or
+ *   done, guides with rows[slot].cfg_scale as uncond + (cond - uncond) * scale, writes the emitted id, the finished flags, the finish
+ *   columns and the advanced position to both rows, embeds the next token for both rows (each with its own position offset, arch 2),
+ *   and writes the pair's row of logits_dump; the last-arriving workgroup recounts the running rows over 2 S flags.
+ * mh_t5_slots_guided_workspace_bytes: the decode workspace of 2 S rows, the slot arrays, the prompt prefill of one pair; -1 for S
+ *   outside [1, 32] (a decode batch holds 64 rows).
+ * mh_t5_slots_open_guided: the argument list of mh_t5_slots_open_kv8 with S = pairs and
+ *     rows            S entries, one per pair, indexed by the slot (rows[slot].cfg_scale is the pair's scale)
+ *     cross_kv_slots  [n_dec][2][S][H][L][64]: one row per pair; may be NULL where sp->cross_kv_fp8 is given
+ *     tokens          int32 [2 S][sp->max_length], rows [negative | prompt]
+ *     logits_dump     optional fp32 [sp->max_length][S][vocab_out]
+ *     sp->cross_kv_fp8 / self_kv_fp8   as in mh_t5_slots_open_kv8: the e4m3 copy of S cross rows, the shadow of 2 S rows; bf16 storage
+ *     workspace       mh_t5_slots_guided_workspace_bytes(cfg, S) bytes
+ *   Requires sp->cfg_scale > 1: guidance on / off is the session's, the scale each pair's own, as in mh_t5_generate_rows.  Refused with
+ *   MH_ERR_ARG and a message in its own name before any device call: sp->cfg_scale <= 1, forced ids, n_cond > 0 without cond_per_row,
+ *   S outside [1, 32], and whatever mh_t5_slots_open / mh_t5_slots_open_kv8 refuse.
+ * mh_t5_slots_admit_pair: prompt_pair = device int32 [2][P], the negative row first; prompt_mask = device uint8 [P] or NULL, shared
+ *   by both rows.  Everything mh_t5_slots_admit does, for both rows: the prompt rows into tokens[slot] and tokens[S + slot], the mask
+ *   into both mask rows; the cross K/V row copied and / or quantised ONCE; both rows' cache rows prefilled with positions 0 .. P-2
+ *   (one B = 1 prefill per row over the same cross row, each run with the GEMM kernels of the B = 2 prefill so that the cache holds
+ *   that call's bits; nothing under option decode_prefill = 0); the shadow's prompt rows quantised for both rows; the one-row init
+ *   for both rows -- both positions are the last words written.  mh_t5_slots_admit on a guided session and mh_t5_slots_admit_pair
+ *   on an unguided one are MH_ERR_ARG with a message; the session stays usable.
+ * mh_t5_slots_run: finished_out / length_out keep S entries, one per pair, read from the prompt row.  mh_t5_slots_release: both rows
+ *   of the pair become idle.
+ * Not built: guided and unguided slots in one session, more than one chain (pairs cut into per-chain blocks), beams, teacher
+ *   forcing, several pairs per admission, skipping an idle slot's cross K/V stream. */
+int64_t mh_t5_slots_guided_workspace_bytes(const MhT5Config* cfg, int S);
+int mh_t5_slots_open_guided(const MhT5Config* cfg, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                            const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                            const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                            void* stream, void** handle);
+int mh_t5_slots_admit_pair(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt_pair, const uint8_t* prompt_mask,
+                           int P, void* stream);
 
 /* (ABI 10) One beam-search step between two decoder positions as ONE kernel (csrc/beam.hip).  Replaces the per-step body of HF
  * `GenerationMixin._beam_search` (third-party, transformers >= 4.50's vectorised form) as the reference reaches it with

@@ -204,6 +204,12 @@ SYMBOLS = {
     # ... over the session's e4m3 copies (sp->cross_kv_fp8 / self_kv_fp8: S-row buffers of the caller's; the same argument list)
     "mh_t5_slots_open_kv8": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), I, C.POINTER(MhSampling), VP, VP, I, VP, VP, VP, VP, VP,
                                  VP, I64, I, VP, C.POINTER(VP)]),
+    # ... of classifier-free guidance pairs: S pairs over 2 S decode rows (the argument list of mh_t5_slots_open_kv8); admit_pair: the
+    # two prompt rows [negative | prompt] of one window
+    "mh_t5_slots_guided_workspace_bytes": (I64, [C.POINTER(MhT5Config), I]),
+    "mh_t5_slots_open_guided": (I, [C.POINTER(MhT5Config), C.POINTER(MhT5Weights), I, C.POINTER(MhSampling), VP, VP, I, VP, VP, VP, VP, VP,
+                                    VP, I64, I, VP, C.POINTER(VP)]),
+    "mh_t5_slots_admit_pair": (I, [VP, I, VP, VP, VP, I, VP]),
     "mh_t5_slots_admit": (I, [VP, I, VP, VP, VP, I, VP]),
     "mh_t5_slots_run": (I, [VP, I, VP, VP, C.POINTER(I)]),
     "mh_t5_slots_release": (I, [VP, I]),

@@ -13,10 +13,12 @@ int launch_sample(int dtype, const StepCall& k, hipStream_t s) {
   return dispatch_dtype(dtype, [&](auto t) -> int {
     using T = decltype(t);
     if (k.slot_pos) {
-      MH_REQUIRE(k.has_rows && smp.pair == 0, "decode: the slot form of the sampler reads row settings and has no guidance");
+      MH_REQUIRE(k.has_rows && (smp.pair == 0 || (smp.b0 == 0 && B == 2 * smp.pair)),
+                 "decode: the slot form of the sampler reads row settings; its guided form is one chain of whole pairs");
       SlotSetP ss{};
       ss.rows = k.rows.rows; ss.eos_tables = k.rows.eos_tables; ss.n_eos_sets = k.rows.n_eos_sets; ss.pos = k.slot_pos; ss.plen = k.slot_plen;
-      hipLaunchKernelGGL((dec_sample_kernel<T, true, true>), dim3(B), dim3(256), 0, s, smp, ss);
+      if (smp.pair > 0) hipLaunchKernelGGL((dec_sample_kernel<T, true, true, true>), dim3(smp.pair), dim3(256), 0, s, smp, ss);   // one workgroup per pair
+      else hipLaunchKernelGGL((dec_sample_kernel<T, true, true>), dim3(B), dim3(256), 0, s, smp, ss);
     } else if (k.has_rows) hipLaunchKernelGGL((dec_sample_kernel<T, true>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, k.rows);
     else hipLaunchKernelGGL((dec_sample_kernel<T, false>), dim3(smp.pair > 0 ? smp.pair : B), dim3(256), 0, s, smp, NoRowSetP{});
     return check_launch("dec_sample_kernel");

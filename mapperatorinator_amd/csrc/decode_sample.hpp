@@ -161,9 +161,16 @@ constexpr int kSampleRegs = 16;   // the register sampling path holds up to 16 i
 // id of its EOS set, or its max_length) writes its finish column, sets its flag and stops: no pad ids afterwards, its position moves no
 // further.  An idle slot (negative position) does nothing.  The last-arriving workgroup recounts n_running and advances nothing.  No
 // guidance (pair = 0) and cond_per_row = 1: checked on the host.
-template <typename T, bool ROWS = false, bool SLOT = false>
+// PAIR (mh_t5_slots_open_guided, on top of SLOT): every slot is a classifier-free guidance pair, one workgroup per pair (grid = p.pair
+// = S): the negative-prompt row s and the prompt row S + s of one window, which share one position, one prompt length and one end.
+// The pair's position, length, flag and state are read from the prompt row; the guidance scale is rs.rows[s]'s own.  The emitted id,
+// the finished flags, the finish columns and the advanced position go to BOTH rows (the self-attention reads the position by row);
+// the next token is embedded for both rows, each with its own pos_off; logits_dump is [max_length][S][V] and the score history is
+// per pair.  The last-arriving workgroup recounts over the 2 S flags.
+template <typename T, bool ROWS = false, bool SLOT = false, bool PAIR = false>
 __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std::conditional<SLOT, SlotSetP, typename std::conditional<ROWS, RowSetP, NoRowSetP>::type>::type rs) {
   static_assert(!SLOT || ROWS, "the slot form always reads rs.rows");
+  static_assert(!PAIR || SLOT, "the pair form is a slot form");
   __shared__ float sf[8];
   __shared__ int si[8];
   __shared__ float s3[12];
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
   __shared__ float s_sum, s_temp;
   __shared__ int s_timed;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const bool cfg = p.pair > 0;
+  const bool cfg = PAIR || p.pair > 0;
   const int nrow = cfg ? 2 : 1;
   const int lneg = blockIdx.x;                 // chain-local row of the negative prompt (CFG only)
   const int lb = cfg ? lneg + p.pair : lneg;   // chain-local returned row (the row whose ids are `input_ids`)
@@ -231,6 +238,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
     if (cfg) nxt[1] = p.tokens[(long)bneg * p.max_length + col];
     if (tid == 0) dec::store_wt(&p.last_ts_val[b], next_ts_state(sp, nxt[0], ltv));
     if constexpr (SLOT) { if (tid == 0) dec::store_wt(&rs.pos[b], pos + 1); }
+    if constexpr (PAIR) { if (tid == 0) dec::store_wt(&rs.pos[bneg], pos + 1); }
   } else {
     if (tid == 0) {
       // ConditionalTemperatureLogitsWarper: the lookback is ROW 0's history for the whole batch
@@ -553,6 +561,7 @@ __global__ __launch_bounds__(256) void dec_sample_kernel(SampleP p, typename std
       }
       dec::store_wt(&p.last_ts_val[b], next_ts_state(sp, nxt[0], ltv));
       if constexpr (SLOT) { if (!done) dec::store_wt(&rs.pos[b], pos + 1); }   // (a row that is done stays where it ended)
+      if constexpr (PAIR) { if (!done) dec::store_wt(&rs.pos[bneg], pos + 1); }   // (both rows of a pair: equal positions always)
     }
   }
   // embedding of the token that the next step consumes (decoder_embedder, modeling_mapperatorinator.py:205-206)

@@ -121,7 +121,7 @@ int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64
 // first sampled token.  Left-pad keys are masked, left-pad query rows produce unused garbage, as in HF.
 int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kvB, const int32_t* prompt,
                    const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s,
-                   int cache_rows = 0);
+                   int cache_rows = 0, int plan_B = 0);
 
 // ---- the token step (t5_step.hip) --------------------------------------------------------------------------------------------------
 // One token step of the chain `k` describes: every layer, the LM head and (k.with_sampler) the sampler

@@ -399,12 +399,15 @@ int64_t prefill_layout(const MhT5Config* c, int B, int np_max, void* base, int64
 // first sampled token.  Left-pad keys are masked, left-pad query rows produce unused garbage, as in HF.
 int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_kv, int B, int kvB, const int32_t* prompt,
                    const uint8_t* prompt_mask, int P, int np, void* self_k, void* self_v, const PrefillBuf& pb, hipStream_t s,
-                   int cache_rows) {
+                   int cache_rows, int plan_B) {
   // P = row stride of `prompt` / `prompt_mask`, np <= P = positions that go through the stack
   // cache_rows: rows of the caches self_k / self_v point into (their layer stride); 0 = B.  More than B (mh_t5_step_prefill): the
   // B prompts fill cache rows 0 .. B-1 of every layer
+  // plan_B > B: these rows are a row block of the prefill of plan_B rows and every GEMM runs the kernel that one would choose, hence
+  // its summation order (mh_t5_slots_admit_pair: one row of a pair at a time computes what the B = 2 prefill computes of it)
   if (cache_rows <= 0) cache_rows = B;
   const int rows = B * np;
+  const int plan_M = plan_B > B ? plan_B * np : 0;
   const int d = c->d_model, H = c->n_heads, inner = H * 64, dff = c->d_ff, L = c->src_len, tgt = c->tgt_len;
   const int es = es_of(c->dtype);
   const int np_pad = round_up(np, 64);
@@ -440,7 +443,7 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
     g.dtype = c->dtype; g.epilogue = MH_EPI_QKV_CACHE; g.n_split = inner; g.C2 = kc; g.C3 = vc; g.C4 = pb.vt; g.kv_B = B;
     g.kv_H = H; g.kv_L = np; g.kv_Lpad = np_pad; g.cache_len = tgt;
     if (wh) g.bias = w->dec_qkv_b[l];
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
     const bool local = is_local_layer(c, l);
     if (wh && !hf) {   // rotate-half RoPE on q (all prompt positions) and on the keys just cached; position = column of the padded prompt
       const long wq = (long)rows * H * 4, wk = (long)B * H * np * 4;
@@ -465,14 +468,14 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
     g.A = pb.attn; g.lda = inner; g.W = w->dec_o[l]; g.ldw = inner; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = inner;
     g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
     if (wh) g.bias = w->dec_o_b[l];
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
     // cross attention of every prompt position over the encoder keys
     MH_TRY(pre_norm(c, pb.h, w->dec_ln2[l], w->dec_ln2_b[l], pb.n, rows, c->dtype, s));
     g = MhGemm{};
     g.A = pb.n; g.lda = d; g.W = w->dec_cq[l]; g.ldw = d; g.C = pb.q; g.ldc = inner; g.M = rows; g.N = inner; g.K = d;
     g.dtype = c->dtype; g.epilogue = MH_EPI_STORE;
     if (wh) g.bias = w->dec_cq_b[l];
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
     for (int b0 = 0; b0 < B; b0 += kvB) {   // under CFG both halves of the batch attend to the same kvB encoder rows
       a = AttnArgs{};
       a.q = (char*)pb.q + (long)b0 * np * inner * es; a.q_rs = (long)inner * es; a.q_bs = (long)np * inner * es;
@@ -488,7 +491,7 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
     g.A = pb.attn; g.lda = inner; g.W = w->dec_co[l]; g.ldw = inner; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = inner;
     g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
     if (wh) g.bias = w->dec_co_b[l];
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
     // feed forward
     MH_TRY(pre_norm(c, pb.h, w->dec_ln3[l], w->dec_ln3_b[l], pb.n, rows, c->dtype, s));
     g = MhGemm{};
@@ -496,12 +499,12 @@ int prefill_prompt(const MhT5Config* c, const MhT5Weights* w, const void* cross_
     g.dtype = c->dtype;
     if (wh) { g.N = dff; g.epilogue = MH_EPI_BIAS_GELU_ERF; g.bias = w->dec_fc1_b[l]; }     // fc1 -> gelu(erf) (modeling_varwhisper.py:633-741)
     else { g.N = 2 * dff; g.epilogue = MH_EPI_GEGLU; }
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
     g = MhGemm{};
     g.A = pb.ff; g.lda = dff; g.W = w->dec_wo[l]; g.ldw = dff; g.C = pb.h; g.ldc = d; g.M = rows; g.N = d; g.K = dff;
     g.dtype = c->dtype; g.epilogue = MH_EPI_RESID;
     if (wh) g.bias = w->dec_fc2_b[l];
-    MH_TRY(gemm(g, s));
+    MH_TRY(gemm(g, s, false, plan_M));
   }
   return MH_OK;
 }

@@ -517,12 +517,18 @@ extern "C" int mh_t5_generate_rows(const MhT5Config* c, const MhT5Weights* w, co
 //     makes it live -- is the last thing its last kernel writes; then it records admitted[chain];
 //   * run() makes the chain's stream wait for admitted[chain] before the first step enqueued after the admission.
 // Events only: nothing on the device spins or waits for another launch.
+//
+// A guided session (mh_t5_slots_open_guided): every slot is a classifier-free guidance PAIR, decode rows s (negative prompt) and S + s
+// (prompt) of R = 2 S rows -- the row order of a guided mh_t5_generate_rows call, so the token step is that call's (kvB = S, pair =
+// S, one chain) with the sampler in its PAIR form.  Every array below that is "per row" has R entries and both rows of a pair always
+// hold the same position; live / freed / the host's view are per slot.  Admission, release and the poll treat the two rows as one.
 namespace mh {
 struct SlotSession {
   const MhT5Config* c = nullptr; const MhT5Weights* w = nullptr;
   int S = 0, n_chains = 0, rows_per = 0, dev = 0, max_length = 0, poll_every = 16;
+  int R = 0; bool guided = false;   // R: decode rows, S or (guided) 2 S
   DecodeLayout ly{};
-  int32_t* pos = nullptr; int32_t* plen = nullptr; uint8_t* mask = nullptr;   // [S], [S], [S][max_length]
+  int32_t* pos = nullptr; int32_t* plen = nullptr; uint8_t* mask = nullptr;   // [R], [R], [R][max_length]
   char* prefill_base = nullptr; int64_t prefill_bytes = 0;
   char* cross_kv = nullptr; int32_t* tokens = nullptr;   // cross_kv: the bf16 / fp32 slot copy, NULL where the steps stream cross8 alone
   uint8_t* cross8 = nullptr; uint8_t* self8 = nullptr;   // mh_t5_slots_open_kv8: the caller's S-row e4m3 copies, or NULL
@@ -544,15 +550,18 @@ struct SlotSession {
     if (caller_ev) (void)hipEventDestroy(caller_ev);
   }
   int chain_of(int slot) const { return slot / rows_per; }
+  int row_of(int slot) const { return guided ? S + slot : slot; }   // the row whose ids are the window's (the prompt row of a pair)
 };
-// the slot buffers behind the decode layout of S rows, then the prompt prefill of ONE row (an admission prefills one window)
-static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession* ss) {
-  const DecodeLayout ly = decode_layout(c, S, base);
+// the slot buffers behind the decode layout of R rows (S, or 2 S of a guided session), then the prompt prefill of ONE window (a row,
+// or the two rows of a pair)
+static int64_t slots_layout(const MhT5Config* c, int S, void* base, SlotSession* ss, bool guided = false) {
+  const int R = guided ? 2 * S : S;
+  const DecodeLayout ly = decode_layout(c, R, base);
   Arena ar(base ? (char*)base + ly.end : nullptr, INT64_MAX);
-  int32_t* pos = (int32_t*)ar.take((int64_t)S * 4);
-  int32_t* plen = (int32_t*)ar.take((int64_t)S * 4);
-  uint8_t* mask = (uint8_t*)ar.take((int64_t)S * c->tgt_len);
-  const int64_t pre = prefill_layout(c, 1, c->tgt_len - 1, nullptr, 0, nullptr);
+  int32_t* pos = (int32_t*)ar.take((int64_t)R * 4);
+  int32_t* plen = (int32_t*)ar.take((int64_t)R * 4);
+  uint8_t* mask = (uint8_t*)ar.take((int64_t)R * c->tgt_len);
+  const int64_t pre = prefill_layout(c, guided ? 2 : 1, c->tgt_len - 1, nullptr, 0, nullptr);
   if (ss) {
     ss->ly = ly; ss->pos = pos; ss->plen = plen; ss->mask = mask;
     ss->prefill_base = (char*)base + ly.end + ar.off; ss->prefill_bytes = pre;
@@ -567,21 +576,32 @@ extern "C" int64_t mh_t5_slots_workspace_bytes(const MhT5Config* c, int S) {
   return mh::slots_layout(c, S, nullptr, nullptr);
 }
 
+extern "C" int64_t mh_t5_slots_guided_workspace_bytes(const MhT5Config* c, int S) {
+  mh::OptionScope option_scope(c ? c->options : nullptr);
+  if (!c || S < 1 || S > 32) return -1;   // a decode batch holds 64 rows
+  return mh::slots_layout(c, S, nullptr, nullptr, true);
+}
+
 namespace mh {
 // mh_t5_slots_open (kv8 = false: the e4m3 caches are refused) and mh_t5_slots_open_kv8 (kv8 = true: sp->cross_kv_fp8 / self_kv_fp8 are
-// the session's S-row copies, filled row by row by the admissions and the token steps)
+// the session's S-row copies, filled row by row by the admissions and the token steps); guided: mh_t5_slots_open_guided, S pairs over
+// 2 S decode rows on one chain (a pair spans both halves of the batch, as in generate_impl), the shadow of 2 S rows, the cross copies
+// of S
 static int slots_open_impl(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
                            const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
                            const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
-                           void* stream, void** handle, bool kv8, const char* who) {
+                           void* stream, void** handle, bool kv8, const char* who, bool guided = false) {
   OptionScope option_scope(c ? c->options : nullptr);
   MH_TRY(check_cfg(c, who));
   MH_REQUIRE(handle, "%s: null argument (handle)", who);
   *handle = nullptr;
-  MH_REQUIRE(S >= 1 && S <= 64, "%s: %d slots not in [1, 64]", who, S);
-  MH_TRY(check_row_set(rows, eos_tables, n_eos_sets, "slot", who));
+  if (guided) MH_REQUIRE(S >= 1 && S <= 32, "%s: %d pairs not in [1, 32] (a decode batch holds 64 rows)", who, S);
+  else MH_REQUIRE(S >= 1 && S <= 64, "%s: %d slots not in [1, 64]", who, S);
+  const int R = guided ? 2 * S : S;
+  MH_TRY(check_row_set(rows, eos_tables, n_eos_sets, guided ? "pair" : "slot", who));
   MH_REQUIRE(sp, "%s: null argument (sp)", who);
-  MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
+  if (guided) MH_REQUIRE(sp->cfg_scale > 1.0f, "%s: needs sp->cfg_scale > 1 (every slot is a guidance pair; the scale is each pair's own, rows[slot].cfg_scale)", who);
+  else MH_REQUIRE(!(sp->cfg_scale > 1.0f), "%s: classifier-free guidance has no slot form (a pair spans two rows of one position)", who);
   MH_REQUIRE(!forced, "%s: teacher forcing (forced ids) has no slot form", who);
   if (!kv8) {
     MH_REQUIRE(!sp->cross_kv_fp8, "%s: the e4m3 copy of the cross K/V (cross_kv_fp8) has no slot form", who);
@@ -594,24 +614,25 @@ static int slots_open_impl(const MhT5Config* c, const MhT5Weights* w, int S, con
   }
   MH_REQUIRE(sp->n_cond == 0 || sp->cond_per_row, "%s: conditional temperature rules need cond_per_row = 1 (every slot is a window of its own)", who);
   // whatever mh_t5_generate_rows refuses of a configuration and its settings (the prompt length is each admission's)
-  MH_TRY(check_decode_call(c, w, sp, S, (cross_kv_slots || (kv8 && sp->cross_kv_fp8)) && tokens && workspace, stream, nullptr, true, who));
-  MH_REQUIRE(workspace_bytes >= slots_layout(c, S, nullptr, nullptr), "%s: workspace too small (mh_t5_slots_workspace_bytes)", who);
+  MH_TRY(check_decode_call(c, w, sp, R, (cross_kv_slots || (kv8 && sp->cross_kv_fp8)) && tokens && workspace, stream, nullptr, true, who));
+  MH_REQUIRE(workspace_bytes >= slots_layout(c, S, nullptr, nullptr, guided), "%s: workspace too small (%s)", who,
+             guided ? "mh_t5_slots_guided_workspace_bytes" : "mh_t5_slots_workspace_bytes");
   MH_TRY(check_arch2_weights(c, w, who));
   hipStream_t s = (hipStream_t)stream;
   int dev = 0;
   MH_TRY(stream_device(s, &dev));
   DeviceGuard device_guard(dev);
   std::unique_ptr<SlotSession> ss(new SlotSession());
-  ss->c = c; ss->w = w; ss->S = S; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
+  ss->c = c; ss->w = w; ss->S = S; ss->R = R; ss->guided = guided; ss->dev = dev; ss->max_length = sp->max_length; ss->poll_every = poll_every <= 0 ? 16 : poll_every;
   ss->cross_kv = (char*)cross_kv_slots; ss->tokens = tokens;
   ss->cross8 = (uint8_t*)sp->cross_kv_fp8; ss->self8 = (uint8_t*)self_kv_fp8;   // (both NULL behind mh_t5_slots_open)
-  slots_layout(c, S, workspace, ss.get());
-  ss->n_chains = pick_chains(S);
-  ss->rows_per = ceil_div(S, ss->n_chains);
+  slots_layout(c, S, workspace, ss.get(), guided);
+  ss->n_chains = guided ? 1 : pick_chains(S);
+  ss->rows_per = ceil_div(R, ss->n_chains);
   // every slot idle: position -1, flag set (the recount of n_running counts clear flags); the chains' control blocks zero
-  if (hipMemsetAsync(ss->pos, 0xff, (size_t)S * 4, s) != hipSuccess || hipMemsetAsync(ss->plen, 0, (size_t)S * 4, s) != hipSuccess ||
-      hipMemsetAsync(ss->ly.bf.finished, 1, (size_t)S, s) != hipSuccess ||
-      hipMemsetAsync(ss->mask, 1, (size_t)S * sp->max_length, s) != hipSuccess ||
+  if (hipMemsetAsync(ss->pos, 0xff, (size_t)R * 4, s) != hipSuccess || hipMemsetAsync(ss->plen, 0, (size_t)R * 4, s) != hipSuccess ||
+      hipMemsetAsync(ss->ly.bf.finished, 1, (size_t)R, s) != hipSuccess ||
+      hipMemsetAsync(ss->mask, 1, (size_t)R * sp->max_length, s) != hipSuccess ||
       hipMemsetAsync(ss->ly.bf.st, 0, (size_t)align256(sizeof(DecState)) * kMaxChains, s) != hipSuccess)
     return check_launch("slot state memset");
   if (hipStreamCreateWithFlags(&ss->admit_stream, hipStreamNonBlocking) != hipSuccess) return check_launch("slot stream create");
@@ -620,7 +641,7 @@ static int slots_open_impl(const MhT5Config* c, const MhT5Weights* w, int S, con
     if (hipEventRecord(ss->freed[b], s) != hipSuccess) return check_launch("slot event record");
   }
   const RowSetP rowset{rows, eos_tables, n_eos_sets};
-  GenerateArgs a{c, w, cross_kv_slots, S, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
+  GenerateArgs a{c, w, cross_kv_slots, R, nullptr, ss->mask, sp->max_length, nullptr, sp, tokens, nullptr, logits_dump, nullptr, workspace,
                  workspace_bytes, poll_every, stream, self_kv_fp8, &rowset, who};
   // prompt_mask: the slot mask rows, stride max_length (call.P); the chains' rows of both e4m3 copies (both pointers are in the key
   // of the step graph: a kv8 session and a plain one never share a graph)
@@ -660,12 +681,20 @@ extern "C" int mh_t5_slots_open_kv8(const MhT5Config* c, const MhT5Weights* w, i
                              workspace_bytes, poll_every, stream, handle, kv8, "mh_t5_slots_open_kv8");
 }
 
-extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
-                                 void* stream) {
+extern "C" int mh_t5_slots_open_guided(const MhT5Config* c, const MhT5Weights* w, int S, const MhSampling* sp, const MhRowSampling* rows,
+                                       const uint8_t* eos_tables, int n_eos_sets, void* cross_kv_slots, int32_t* tokens, float* logits_dump,
+                                       const int32_t* forced, void* self_kv_fp8, void* workspace, int64_t workspace_bytes, int poll_every,
+                                       void* stream, void** handle) {
+  const bool kv8 = (sp && sp->cross_kv_fp8) || self_kv_fp8;
+  return mh::slots_open_impl(c, w, S, sp, rows, eos_tables, n_eos_sets, cross_kv_slots, tokens, logits_dump, forced, self_kv_fp8, workspace,
+                             workspace_bytes, poll_every, stream, handle, kv8, "mh_t5_slots_open_guided", true);
+}
+
+// mh_t5_slots_admit (one row) and mh_t5_slots_admit_pair (n_rows = 2: `prompt` is [2][P], the negative row first; the rows of the pair
+// are decode rows slot and S + slot, one cross K/V row and one mask for both)
+static int slots_admit_impl(mh::SlotSession* ss, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
+                            void* stream, const char* who) {
   using namespace mh;
-  SlotSession* ss = (SlotSession*)handle;
-  const char* who = "mh_t5_slots_admit";
-  MH_REQUIRE(ss, "%s: null handle", who);
   OptionScope option_scope(ss->c->options);
   MH_REQUIRE(cross_kv_row && prompt, "%s: null argument", who);
   MH_REQUIRE(slot >= 0 && slot < ss->S, "%s: slot %d not in [0, %d)", who, slot, ss->S);
@@ -688,29 +717,56 @@ extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_ro
     return check_launch("admit cross K/V copy");
   // ... and, quantised, -> row `slot` of the S-row e4m3 copy (bytes and scales; no other row is touched)
   if (ss->cross8) MH_TRY(launch_cross_kv_quant_row(c, ss->S, cross_kv_row, ss->cross8, slot, as));
-  int32_t* trow = ss->tokens + (long)slot * ss->max_length;
-  uint8_t* mrow = ss->mask + (long)slot * ss->max_length;
-  if (hipMemcpyAsync(trow, prompt, (size_t)P * 4, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit prompt copy");
-  if (hipMemsetAsync(mrow, 1, (size_t)ss->max_length, as) != hipSuccess) return check_launch("admit mask set");
-  if (prompt_mask && hipMemcpyAsync(mrow, prompt_mask, (size_t)P, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit mask copy");
+  const int n_rows = ss->guided ? 2 : 1;
+  const int row[2] = {slot, ss->S + slot};   // (a plain session: row[0] alone)
+  for (int j = 0; j < n_rows; ++j) {
+    int32_t* trow = ss->tokens + (long)row[j] * ss->max_length;
+    uint8_t* mrow = ss->mask + (long)row[j] * ss->max_length;
+    if (hipMemcpyAsync(trow, prompt + (long)j * P, (size_t)P * 4, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit prompt copy");
+    if (hipMemsetAsync(mrow, 1, (size_t)ss->max_length, as) != hipSuccess) return check_launch("admit mask set");
+    if (prompt_mask && hipMemcpyAsync(mrow, prompt_mask, (size_t)P, hipMemcpyDeviceToDevice, as) != hipSuccess) return check_launch("admit mask copy");
+  }
   int start_pos = 0;
   if (P > 1 && option(OPT_DECODE_PREFILL) != 0) {   // positions 0 .. P-2 into the slot's cache rows: the B = 1 prefill of a uniform call
     PrefillBuf pb;
     prefill_layout(c, 1, P - 1, ss->prefill_base, ss->prefill_bytes, &pb);
-    const long cache_row = (long)slot * inner * c->tgt_len * es;
-    MH_TRY(prefill_prompt(c, ss->w, cross_kv_row, 1, 1, prompt, prompt_mask, P, P - 1, (char*)ss->ly.bf.self_k + cache_row,
-                          (char*)ss->ly.bf.self_v + cache_row, pb, as, ss->S));
     start_pos = P - 1;
-    // the prefilled positions 0 .. P-2 of the slot's cache rows -> the same places of the S-row shadow, every layer, k and v (the pass a
-    // uniform call makes after its prefill); nothing else of the shadow is written
-    if (ss->self8) MH_TRY(launch_self_kv_quant_slot(c, ss->S, ss->ly.bf, ss->self8, slot, start_pos, as));
+    // (a pair: one row after the other through the same buffers, each as a row block of the B = 2 prefill of the guided call -- the
+    // GEMM kernels that call would run, so the cache rows hold its bits)
+    for (int j = 0; j < n_rows; ++j) {
+      const long cache_row = (long)row[j] * inner * c->tgt_len * es;
+      MH_TRY(prefill_prompt(c, ss->w, cross_kv_row, 1, 1, prompt + (long)j * P, prompt_mask, P, P - 1, (char*)ss->ly.bf.self_k + cache_row,
+                            (char*)ss->ly.bf.self_v + cache_row, pb, as, ss->R, n_rows));
+      // the prefilled positions 0 .. P-2 of the slot's cache rows -> the same places of the R-row shadow, every layer, k and v (the pass a
+      // uniform call makes after its prefill); nothing else of the shadow is written
+      if (ss->self8) MH_TRY(launch_self_kv_quant_slot(c, ss->R, ss->ly.bf, ss->self8, row[j], start_pos, as));
+    }
   }
   const SampleP& smp = ss->calls[ci].smp;
-  MH_TRY(launch_dec_slot_init(c->dtype, smp, slot, P, start_pos, ss->pos, ss->plen, as));
+  for (int j = 0; j < n_rows; ++j)   // (a pair: the negative row, then the prompt row -- the positions stay the last words written)
+    MH_TRY(launch_dec_slot_init(c->dtype, smp, row[j], P, start_pos, ss->pos, ss->plen, as));
   if (hipEventRecord(ss->admitted[ci], as) != hipSuccess) return check_launch("admit record");
   ss->pending[ci] = true;
   ss->live[slot] = true;
   return MH_OK;
+}
+
+extern "C" int mh_t5_slots_admit(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt, const uint8_t* prompt_mask, int P,
+                                 void* stream) {
+  mh::SlotSession* ss = (mh::SlotSession*)handle;
+  const char* who = "mh_t5_slots_admit";
+  MH_REQUIRE(ss, "%s: null handle", who);
+  MH_REQUIRE(!ss->guided, "%s: the session is guided (mh_t5_slots_open_guided): its slots are pairs, admitted by mh_t5_slots_admit_pair", who);
+  return slots_admit_impl(ss, slot, cross_kv_row, prompt, prompt_mask, P, stream, who);
+}
+
+extern "C" int mh_t5_slots_admit_pair(void* handle, int slot, const void* cross_kv_row, const int32_t* prompt_pair, const uint8_t* prompt_mask,
+                                      int P, void* stream) {
+  mh::SlotSession* ss = (mh::SlotSession*)handle;
+  const char* who = "mh_t5_slots_admit_pair";
+  MH_REQUIRE(ss, "%s: null handle", who);
+  MH_REQUIRE(ss->guided, "%s: the session is not guided (mh_t5_slots_open_guided opens one): its slots are rows, admitted by mh_t5_slots_admit", who);
+  return slots_admit_impl(ss, slot, cross_kv_row, prompt_pair, prompt_mask, P, stream, who);
 }
 
 extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out, int32_t* length_out, int32_t* steps_out) {
@@ -752,10 +808,11 @@ extern "C" int mh_t5_slots_run(void* handle, int n_steps, uint8_t* finished_out,
       return check_launch("slot poll");
     if (rc == MH_OK && word[1] != 0) rc = mh_t5_decode_tail_status(word[1]);
   }
-  for (int b = 0; b < ss->S; ++b) {
-    const bool fin = ss->live[b] && ss->host_fin[b] != 0;
+  for (int b = 0; b < ss->S; ++b) {   // (a pair: read from its prompt row)
+    const int r = ss->row_of(b);
+    const bool fin = ss->live[b] && ss->host_fin[r] != 0;
     finished_out[b] = fin ? 1 : 0;
-    length_out[b] = !ss->live[b] ? 0 : (fin ? ss->host_col[b] + 1 : ss->host_pos[b] + 1);
+    length_out[b] = !ss->live[b] ? 0 : (fin ? ss->host_col[r] + 1 : ss->host_pos[r] + 1);
   }
   if (steps_out) *steps_out = total;
   return rc;
@@ -776,9 +833,12 @@ extern "C" int mh_t5_slots_release(void* handle, int slot) {
     ss->pending[ci] = false;
   }
   // on the chain's stream, behind the slot's last step: idle again (negative position, flag set), then the event an admission waits for
-  if (hipMemsetAsync(ss->pos + slot, 0xff, 4, cs) != hipSuccess || hipMemsetAsync(ss->ly.bf.finished + slot, 1, 1, cs) != hipSuccess ||
-      hipEventRecord(ss->freed[slot], cs) != hipSuccess)
+  if (hipMemsetAsync(ss->pos + slot, 0xff, 4, cs) != hipSuccess || hipMemsetAsync(ss->ly.bf.finished + slot, 1, 1, cs) != hipSuccess)
     return check_launch("slot release");
+  if (ss->guided && (hipMemsetAsync(ss->pos + ss->S + slot, 0xff, 4, cs) != hipSuccess ||   // both rows of the pair
+                     hipMemsetAsync(ss->ly.bf.finished + ss->S + slot, 1, 1, cs) != hipSuccess))
+    return check_launch("slot release");
+  if (hipEventRecord(ss->freed[slot], cs) != hipSuccess) return check_launch("slot release");
   ss->live[slot] = false;
   return MH_OK;
 }

@@ -56,7 +56,8 @@ def _left_pad(rows, pad_id: int, dtype):
 
 class SequentialWindowScheduler:
     def __init__(self, model, tokenizer, *, encode_batch: int = 32, decode_batch: int = 32, merge_kwargs: bool = False,
-                 inflight: bool = False, inflight_steps: int = 16, inflight_kv_fp8: Optional[str] = None):
+                 inflight: bool = False, inflight_steps: int = 16, inflight_kv_fp8: Optional[str] = None,
+                 inflight_guided: bool = False):
         if decode_batch > 64 or decode_batch < 1:
             raise ValueError("decode_batch must be in [1, 64] (32 at most when windows run under classifier-free guidance)")
         if inflight_kv_fp8 not in self._INFLIGHT_KV_FP8:
@@ -64,6 +65,9 @@ class SequentialWindowScheduler:
         if inflight_kv_fp8 is not None and not inflight:
             raise ValueError(f"inflight_kv_fp8={inflight_kv_fp8!r} is a switch of the slot session: it needs inflight=True (a wave takes "
                              "cross_kv_fp8 / self_kv_fp8 from its generate_kwargs)")
+        if inflight_guided and not inflight:
+            raise ValueError("inflight_guided=True is a switch of the slot session: it needs inflight=True (a wave takes guidance from "
+                             "its generate_kwargs)")
         self.model, self.tokenizer = model, tokenizer
         self.engine = model.engine
         self.encode_batch, self.decode_batch = int(encode_batch), int(decode_batch)
@@ -82,6 +86,10 @@ class SequentialWindowScheduler:
         # is chosen, and not by a job or a window.  fp32 storage is refused now, before anything is encoded.
         self.inflight_kv_fp8 = dict(zip(("cross_kv_fp8", "self_kv_fp8"), self._INFLIGHT_KV_FP8[inflight_kv_fp8]))
         DecodeModes.of(self.inflight_kv_fp8, getattr(self.engine, "dtype", None))
+        # inflight_guided (off by default): the session's slots are classifier-free guidance PAIRS (T5Engine.open_guided_slots):
+        # decode_batch // 2 slots, as a guided wave holds half the windows; every job and every window must then be guided (cfg_scale
+        # > 1 and a negative_prompt), each window under its own scale.  Off: guidance is refused under inflight as ever.
+        self.inflight_guided = bool(inflight_guided)
 
     # ---- stage 1: everything that depends on the audio only ------------------------------------------------
     @torch.no_grad()
@@ -218,6 +226,12 @@ class SequentialWindowScheduler:
 
     def _check_inflight(self, gk: dict, what: str) -> None:
         for name, on, words in self._INFLIGHT_REFUSED:
+            if name == "cfg_scale" and self.inflight_guided:
+                if not on(gk):
+                    raise ValueError(f"inflight_guided: {what} is not guided (cfg_scale={gk.get('cfg_scale', 1.0)!r}): every slot of the "
+                                     "session is a guidance pair, so every job and window needs cfg_scale > 1 and a negative_prompt; "
+                                     "run unguided jobs with inflight_guided=False")
+                continue
             if on(gk):
                 raise ValueError(f"inflight: {what} asks for {words} ({name}={gk.get(name)!r}), which has no slot form: "
                                  "run it with inflight=False"
@@ -245,7 +259,10 @@ class SequentialWindowScheduler:
         served; every row decodes under its own kwargs (`build_row_sampling`), as the default policy's batch-1 call for that window
         would: explicit seeds with this scheduler's own call counter, RNG row 0, no left padding (so no redo path).  The per-call
         settings (`row_call_key`) must agree over all jobs; beams, guidance, the fp8 caches as a job's or a window's kwargs (they
-        are the session's: `inflight_kv_fp8`) and injected samplers are refused -- both before anything is encoded."""
+        are the session's: `inflight_kv_fp8`) and injected samplers are refused -- both before anything is encoded.
+        `inflight_guided=True`: decode_batch // 2 slots, every one a guidance pair (negative-prompt row and prompt row of one window,
+        `T5Engine.open_guided_slots`); every job and window must be guided (cfg_scale > 1, a negative_prompt), each window under
+        its own scale; a window decodes as the default policy's guided batch-1 call for it would."""
         eng, tok = self.engine, self.tokenizer
         keys = set()
         for n, j in enumerate(jobs):
@@ -255,20 +272,26 @@ class SequentialWindowScheduler:
             raise ValueError("inflight: the jobs differ in a per-call setting (server.row_call_key: do_sample, types_first, pad_token_id, "
                              "precision, ...): such jobs need schedulers of their own")
         start = time.perf_counter()
-        kvs = self.encode_all(jobs)
-        pad_id = int(getattr(tok, "pad_id", 0))
-        S = self.decode_batch
-        self.stats.setdefault("admissions", 0)
-        self.stats.setdefault("decode_steps", 0)
 
         def ask_of(i, w):
             ask = dict(jobs[i].prompt_fn(w))
             gk = dict(jobs[i].generate_kwargs, **ask.pop("generate_kwargs", {}))
             self._check_inflight(gk, f"window {w} of job {i}")
+            if self.inflight_guided and ask.get("negative_prompt") is None:
+                raise ValueError(f"inflight_guided: window {w} of job {i} has no negative_prompt (cfg_scale > 1 needs one for every window)")
             return ask, gk
+        # (inflight_guided: every song's first window is asked for, and refused without a negative prompt, before anything is encoded)
+        first = {i: ask_of(i, 0) for i in range(len(jobs))} if self.inflight_guided else None
+        kvs = self.encode_all(jobs)
+        pad_id = int(getattr(tok, "pad_id", 0))
+        # guidance doubles the decode rows (a slot is a pair): half as many slots, as a guided wave holds half the windows
+        S = max(1, self.decode_batch // 2) if self.inflight_guided else self.decode_batch
+        self.stats.setdefault("admissions", 0)
+        self.stats.setdefault("decode_steps", 0)
         # the session's per-call settings: those of every song's first window (window 0 depends on nothing), and -- types_first --
         # of the same windows with a lookback, which the later windows of a song carry
-        first = {i: ask_of(i, 0) for i in range(len(jobs))}
+        if first is None:
+            first = {i: ask_of(i, 0) for i in range(len(jobs))}
         probe = []
         for _, gk in first.values():
             # (seed_call_index -1: no window's own kwargs equal a probe entry's, so a window is always a group of its own -- RNG row
@@ -282,7 +305,7 @@ class SequentialWindowScheduler:
         sp0 = build_row_sampling(tok, probe, self.model.config.max_target_positions)[0]
         sp0.max_length = int(self.model.config.max_target_positions)
         # (a switch at its default is not passed: engines written against the narrower signature keep working)
-        slots = eng.open_slots(S, sp0, **{k: True for k, on in self.inflight_kv_fp8.items() if on})
+        slots = (eng.open_guided_slots if self.inflight_guided else eng.open_slots)(S, sp0, **{k: True for k, on in self.inflight_kv_fp8.items() if on})
         occupant = [None] * S                       # slot -> (job, window, ask, admitted at)
         ready = list(range(len(jobs)))              # songs whose next window may enter, first come first served
         next_w = [0] * len(jobs)
@@ -297,7 +320,8 @@ class SequentialWindowScheduler:
                     _, row, eos_table = self._inflight_row(probe, self._call_kwargs(gk), sp0)
                     ids = ask["decoder_input_ids"].reshape(-1)
                     mask = ask.get("decoder_attention_mask")
-                    slots.admit(slot, kvs[i][:, :, w], ids, None if mask is None else mask.reshape(-1), row, eos_table)
+                    slots.admit(slot, kvs[i][:, :, w], ids, None if mask is None else mask.reshape(-1), row, eos_table,
+                                **({"negative_prompt": ask["negative_prompt"].reshape(-1)} if self.inflight_guided else {}))
                     occupant[slot] = (i, w, ask, time.perf_counter())
                     self.stats["admissions"] += 1
                 if all(o is None for o in occupant):

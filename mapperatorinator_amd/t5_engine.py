@@ -509,8 +509,18 @@ class T5Engine:
         `cross_kv_fp8` / `self_kv_fp8`: switches of the SESSION (`mh_t5_slots_open_kv8`; bf16 storage only): the token steps stream
         an S-row e4m3 copy of the slots' cross K/V, which every admission fills for its slot -- the session then holds no bf16 copy
         of it at all -- and / or attend an S-row e4m3 shadow of the self-attention cache.  A slot then computes what the batch-1
-        `decode` computes under the same switches, bit for bit."""
+        `decode` computes under the same switches, bit for bit.  Guidance: `open_guided_slots`."""
         return DecodeSlots(self, int(S), sampling, dump_logits, poll_every, cross_kv_fp8, self_kv_fp8)
+
+    def open_guided_slots(self, S: int, sampling: _lib.MhSampling, dump_logits: bool = False, poll_every: int = 16,
+                          cross_kv_fp8: bool = False, self_kv_fp8: bool = False) -> "DecodeSlots":
+        """`open_slots` under classifier-free guidance (`mh_t5_slots_open_guided`): every slot is a PAIR -- the negative-prompt row and
+        the prompt row of one window (`guided_rows`), admitted with `admit(..., negative_prompt=)`, stepped, finished and taken
+        together; S in [1, 32] pairs over 2 S decode rows on one chain, `sampling.cfg_scale > 1` (the scale is each pair's own: its
+        row entry's).  A slot computes what the 2-row guided `decode(row_sampling=)` of the window alone computes, bit for bit, under
+        the same `cross_kv_fp8` / `self_kv_fp8` switches.  Every window of the session is guided; `open_slots` refuses guidance as
+        ever.  (A method of its own: the argument list of `open_slots` is pinned.)"""
+        return DecodeSlots(self, int(S), sampling, dump_logits, poll_every, cross_kv_fp8, self_kv_fp8, guided=True)
 
     def quantize_kv_rows(self, rows: torch.Tensor):
         """`mh_quantize_kv_rows`: bf16 (..., 64) on the device -> (e4m3 bytes uint8 (..., 64), fp32 scales (...)), the row form of the
@@ -631,16 +641,24 @@ class DecodeSlots:
         slots.close()
 
     A slot computes what `T5Engine.decode(row_sampling=...)` computes for the window alone (B = 1, its unpadded prompt, its own
-    row entry), bit for bit.  `stats`: admissions and graph replays so far."""
+    row entry), bit for bit.  `stats`: admissions and graph replays so far.
+    `guided`: S pairs over R = 2 S decode rows, `tokens` (2 S, max_length) as [negative rows | prompt rows], slot s = rows s and S + s;
+    `logits` (max_length, S, vocab_out); `take` returns the prompt row."""
 
     def __init__(self, engine: "T5Engine", S: int, sampling: _lib.MhSampling, dump_logits: bool, poll_every: int,
-                 cross_kv_fp8: bool = False, self_kv_fp8: bool = False):
+                 cross_kv_fp8: bool = False, self_kv_fp8: bool = False, guided: bool = False):
+        self.guided = bool(guided)
+        if self.guided and not 1 <= S <= 32:
+            raise ValueError(f"open_guided_slots: {S} pairs not in [1, 32] (a decode batch holds 64 rows)")
+        if self.guided and not sampling.cfg_scale > 1.0:
+            raise ValueError("open_guided_slots: needs sampling.cfg_scale > 1 (the scale itself is each pair's own)")
         if not 1 <= S <= 64:
             raise ValueError(f"open_slots: {S} slots not in [1, 64]")
         if getattr(engine, "_slot_session", None) is not None:
             raise RuntimeError("open_slots: this engine has an open slot session (its buffers are the engine's): close it first")
         self.modes = DecodeModes.of(dict(cross_kv_fp8=cross_kv_fp8, self_kv_fp8=self_kv_fp8), engine.dtype)   # (the storage refusals)
         self.engine, self.S, self.sampling = engine, S, sampling
+        self.R = R = 2 * S if self.guided else S      # decode rows
         self._handle = C.c_void_p()
         p = engine.packed
         dev, lib = engine.device, engine.lib
@@ -666,14 +684,14 @@ class DecodeSlots:
         else:
             self.cross_kv = engine._workspace("slot_cross_kv", d.n_dec_layers * 2 * S * d.n_heads * p.src_len * 64 * es)
         if self.modes.self_kv_fp8:
-            self.self_kv8 = engine._workspace("slot_skv8", lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), S))
-        self.tokens = engine._workspace("slot_tokens", 64 * p.tgt_len * 4)[:S * maxlen * 4].view(torch.int32).view(S, maxlen)
+            self.self_kv8 = engine._workspace("slot_skv8", lib.mh_t5_self_kv_fp8_bytes(C.byref(p.cfg), R))
+        self.tokens = engine._workspace("slot_tokens", 64 * p.tgt_len * 4)[:R * maxlen * 4].view(torch.int32).view(R, maxlen)
         self.logits = None
         if dump_logits:
             n = maxlen * S * p.vocab_out
             self.logits = engine._workspace("slot_logits", n * 4)[:n * 4].view(torch.float32).view(maxlen, S, p.vocab_out)
             self.logits.zero_()
-        ws = engine._workspace("slots", lib.mh_t5_slots_workspace_bytes(C.byref(p.cfg), S))
+        ws = engine._workspace("slots", (lib.mh_t5_slots_guided_workspace_bytes if self.guided else lib.mh_t5_slots_workspace_bytes)(C.byref(p.cfg), S))
         self._hold = [None] * S          # what an admission reads, kept until the slot is taken
         self._lengths = [0] * S
         self._finished = [False] * S
@@ -681,6 +699,8 @@ class DecodeSlots:
         self.stats = dict(admissions=0, steps=0, runs=0)
         kv8 = self.cross_kv8 is not None or self.self_kv8 is not None
         entry = "mh_t5_slots_open_kv8" if kv8 else "mh_t5_slots_open"        # the new entry only when a switch is on
+        if self.guided:
+            entry = "mh_t5_slots_open_guided"
         sampling.cross_kv_fp8 = _lib.ptr(self.cross_kv8)
         engine._enter()
         try:
@@ -694,15 +714,25 @@ class DecodeSlots:
         engine._slot_session = self
 
     def admit(self, slot: int, cross_kv_row: torch.Tensor, prompt: torch.Tensor, prompt_mask: Optional[torch.Tensor],
-              row: _lib.MhRowSampling, eos_table: torch.Tensor) -> None:
+              row: _lib.MhRowSampling, eos_table: torch.Tensor, negative_prompt: Optional[torch.Tensor] = None) -> None:
         """One window into an idle slot: `cross_kv_row` its cross K/V (n_dec, 2, [1,] H, L, 64), `prompt` its own ids (P,) or (1, P)
         without padding, `prompt_mask` or None, `row` its settings (an entry of `server.build_row_sampling(...)[1]`) and
-        `eos_table` uint8 (vocab_out,) its EOS set.  Returns at once; the slot's chain picks the window up at its next step."""
+        `eos_table` uint8 (vocab_out,) its EOS set.  Returns at once; the slot's chain picks the window up at its next step.
+        `negative_prompt` (n,) or (1, n), n <= P: required on a guided session, refused on a plain one -- the pair is built by
+        `guided_rows` (both rows under `prompt_mask`) and admitted as one; `row.cfg_scale` is the pair's scale."""
         eng, p = self.engine, self.engine.packed
         if not 0 <= slot < self.S or self.live[slot]:
             raise ValueError(f"admit: slot {slot} is not an idle slot of this session")
+        if self.guided and negative_prompt is None:
+            raise ValueError("admit: a guided session admits pairs: negative_prompt is required")
+        if not self.guided and negative_prompt is not None:
+            raise ValueError("admit: negative_prompt on a session without guidance (open_guided_slots opens a guided one)")
+        if self.guided and not row.cfg_scale > 1.0:
+            raise ValueError(f"admit: a guided session needs row.cfg_scale > 1, got {row.cfg_scale}")
         prompt = prompt.reshape(-1)
         P = int(prompt.shape[0])
+        if self.guided:      # [negative | prompt], (2, P)
+            prompt = guided_rows(prompt.reshape(1, -1), None, negative_prompt.reshape(1, -1))[0]
         if not (1 <= P < row.max_length <= self.max_length) or not row.temperature > 0:
             raise ValueError(f"admit: prompt length {P} < row.max_length {row.max_length} <= {self.max_length} and temperature > 0 expected")
         d = eng.dims
@@ -718,8 +748,8 @@ class DecodeSlots:
                 self._rows_d[slot * sz:(slot + 1) * sz].copy_(torch.frombuffer(bytearray(bytes(entry)), dtype=torch.uint8))
                 self._eos_d[slot * p.vocab_out:(slot + 1) * p.vocab_out].copy_(torch.as_tensor(eos_table, dtype=torch.uint8).reshape(-1))
                 self._hold[slot] = (kv, prompt_d, mask_d)
-                _lib.check(eng.lib.mh_t5_slots_admit(self._handle, slot, kv.data_ptr(), prompt_d.data_ptr(), _lib.ptr(mask_d), P, eng._s()),
-                           "mh_t5_slots_admit")
+                name = "mh_t5_slots_admit_pair" if self.guided else "mh_t5_slots_admit"
+                _lib.check(getattr(eng.lib, name)(self._handle, slot, kv.data_ptr(), prompt_d.data_ptr(), _lib.ptr(mask_d), P, eng._s()), name)
         finally:
             eng._leave()
         self.live[slot], self._finished[slot], self._lengths[slot] = True, False, P
@@ -742,7 +772,7 @@ class DecodeSlots:
         """The slot's row as of the last `run` -- int64 CPU (length,), the prompt included -- and the slot is idle again."""
         if not 0 <= slot < self.S or not self.live[slot]:
             raise ValueError(f"take: slot {slot} is not a live slot of this session")
-        out = self.tokens[slot, :self._lengths[slot]].to(torch.int64).cpu()
+        out = self.tokens[self.S + slot if self.guided else slot, :self._lengths[slot]].to(torch.int64).cpu()
         _lib.check(self.engine.lib.mh_t5_slots_release(self._handle, slot), "mh_t5_slots_release")
         self.live[slot], self._hold[slot], self._lengths[slot], self._finished[slot] = False, None, 0, False
         return out

@@ -14,12 +14,17 @@ Policies, alternating in one process, round 0 as warm-up, medians of --reps roun
                 (`SequentialWindowScheduler(inflight_kv_fp8=<mode>)`, `mh_t5_slots_open_kv8`); `vs_inflight` = its wall time against
                 plain in-flight.  `--only-inflight` leaves the two wave policies out; `--new-tokens LO HI` moves the drawn range (a
                 workload of long windows: with `--tgt` large enough to hold them).
+  --guided      the same constructed workload under classifier-free guidance: every window carries a negative prompt (sos alone) and
+                cfg_scale = 2.  Two policies at the same `decode_batch` (--slots decode ROWS, so half as many windows): guided_merge_kwargs
+                (guided waves, `merge_kwargs=True`: wave w in row-settings calls of slots / 2 pairs) against inflight_guided
+                (`SequentialWindowScheduler(inflight=True, inflight_guided=True)`, `mh_t5_slots_open_guided`: slots / 2 pair slots kept
+                full).  `ideal_steps` = all new tokens / (slots / 2) pairs.
 Reported per policy: wall time of the whole run (encode of all windows + decode), generated tokens/s, the span of the rounds, and the
 token steps: DERIVED on the host for the wave policies (sum over calls of the longest row's new tokens: what the call replays, up to
 its poll granularity) and COUNTED for in-flight (graph replays, summed over the chains, and per chain).  `ideal_steps` = all new
 tokens / 32 slots: what no policy can beat.
     python tools/inflight_bench.py [--reps 5] [--waves-reps 1] [--songs 32] [--steps 16] [--kv-fp8 cross both] [--only-inflight]
-                                   [--new-tokens 96 512] [--tgt 640] [--out FILE]"""
+                                   [--new-tokens 96 512] [--tgt 640] [--guided] [--out FILE]"""
 import argparse, importlib.util, json, os, random, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -36,7 +41,7 @@ def _median(xs):
     return sorted(xs)[len(xs) // 2]
 
 
-def run(model, tok, frames, n_songs, reps, waves_reps, steps, slots, kv_fp8=(), only_inflight=False, new_tokens=(96, 512)):
+def run(model, tok, frames, n_songs, reps, waves_reps, steps, slots, kv_fp8=(), only_inflight=False, new_tokens=(96, 512), guided=False):
     from mapperatorinator_amd import server
     from mapperatorinator_amd.scheduler import SequentialWindowScheduler, SongJob
     from mh_testing import synthetic_audio_varied
@@ -53,12 +58,16 @@ def run(model, tok, frames, n_songs, reps, waves_reps, steps, slots, kv_fp8=(), 
         for i, n in enumerate(counts):
             def prompt_fn(w, i=i, n=n):
                 return dict(decoder_input_ids=torch.tensor([[tok.sos_id, 40 + (i + w) % 50]]),
+                            **(dict(negative_prompt=torch.tensor([[tok.sos_id]])) if guided else {}),
                             generate_kwargs=dict(lookback_time=500 if w else 0, lookahead_time=500 if w != n - 1 else 0,
                                                  max_length=P + new[i][w]))
             out.append(SongJob(frames=audio[:n], prompt_fn=prompt_fn, on_result=lambda w, row, st: None,
-                               generate_kwargs=dict(do_sample=False, num_beams=1, temperature=1.0, pad_token_id=0)))
+                               generate_kwargs=dict(do_sample=False, num_beams=1, temperature=1.0, pad_token_id=0,
+                                                    **(dict(cfg_scale=2.0) if guided else {}))))
         return out
     waves = [[new[i][w] for i in range(n_songs) if w < counts[i]] for w in range(max(counts))]
+    if guided:
+        return _run_guided(model, tok, jobs, counts, waves, total, reps, steps, slots, new_tokens)
     res = {"workload": f"{n_songs} songs x {min(counts)}..{max(counts)} windows, {sum(counts)} windows, new tokens per window {new_tokens[0]}..{new_tokens[1]} (seed 7), "
                        f"{total} new tokens, {slots} rows / slots", "window_counts": counts, "new_tokens": total,
            "ideal_steps": -(-total // slots),
@@ -101,6 +110,41 @@ def run(model, tok, frames, n_songs, reps, waves_reps, steps, slots, kv_fp8=(), 
     return res
 
 
+def _run_guided(model, tok, jobs, counts, waves, total, reps, steps, slots, new_tokens):
+    """--guided: guided waves (merge_kwargs) against guided slots, alternating, round 0 as warm-up, medians of `reps` rounds"""
+    from mapperatorinator_amd.scheduler import SequentialWindowScheduler
+    pairs = max(1, slots // 2)
+    calls = [w[a:a + pairs] for w in waves for a in range(0, len(w), pairs)]        # a guided wave: calls of slots / 2 windows
+    res = {"workload": f"CONSTRUCTED, guided (cfg_scale 2, negative prompt = sos): {len(counts)} songs x {min(counts)}..{max(counts)} windows, "
+                       f"{sum(counts)} windows, new tokens per window {new_tokens[0]}..{new_tokens[1]} (seed 7), {total} new tokens, "
+                       f"decode_batch {slots} rows = {pairs} pairs", "window_counts": counts, "new_tokens": total,
+           "ideal_steps": -(-total // pairs),
+           "derived_steps": {"guided_merge_kwargs": sum(max(c) for c in calls), "note": "sum over calls of the longest row"}}
+    policies = {"guided_merge_kwargs": dict(merge_kwargs=True),
+                "inflight_guided": dict(inflight=True, inflight_guided=True, inflight_steps=steps)}
+    runs = {k: [] for k in policies}
+    for r in range(reps + 1):
+        for name, kw in policies.items():
+            sched = SequentialWindowScheduler(model, tok, encode_batch=32, decode_batch=slots, **kw)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = sched.run(jobs())
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            assert st["windows"] == sum(counts), st
+            if r:
+                runs[name].append((wall, dict(st)))
+    for name in policies:
+        walls = [w for w, _ in runs[name]]
+        st = runs[name][0][1]
+        res[name] = {"rounds": len(walls), "wall_s": round(_median(walls), 3), "wall_s_span": [round(min(walls), 3), round(max(walls), 3)],
+                     "tokens_per_s": round(total / _median(walls), 1), "decode_calls": st["decode_calls"]}
+    st = runs["inflight_guided"][0][1]
+    res["inflight_guided"].update(admissions=st["admissions"], replays=st["decode_steps"], chains=1, pair_slots=pairs)
+    res["inflight_guided_vs_guided_merge_kwargs"] = round(res["guided_merge_kwargs"]["wall_s"] / res["inflight_guided"]["wall_s"], 3)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -113,13 +157,14 @@ if __name__ == "__main__":
                     help="also run in-flight over the session's e4m3 caches, one policy per mode given")
     ap.add_argument("--only-inflight", action="store_true", help="leave the wave policies out")
     ap.add_argument("--new-tokens", type=int, nargs=2, default=[96, 512], metavar=("LO", "HI"))
+    ap.add_argument("--guided", action="store_true", help="the workload under classifier-free guidance: guided waves against guided slots")
     ap.add_argument("--out", default="", help="also append the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     with torch.no_grad():
         model, tok, dims, frames = _sbd().build("varwhisper-small", a.tgt, dev)
         line = json.dumps({"inflight_decode": run(model, tok, frames, a.songs, a.reps, a.waves_reps, a.steps, a.slots, a.kv_fp8, a.only_inflight,
-                                                     tuple(a.new_tokens))})
+                                                     tuple(a.new_tokens), a.guided)})
         print(line, flush=True)
         if a.out:
             with open(a.out, "a") as f:
